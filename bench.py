@@ -16,6 +16,8 @@ Frames are independent, so ranks shard the job with no collective (rgbd_pl_slam_
 every rank processes its own frames_in_flight).  Prints ONE JSON line on rank 0; at N = 1 the default config also carries the
 secondary figures (config 3 as specified, single-frame and tracking-call latency, frames/s against frames in flight, the same step on natural-image-like frames
 (`natural`) and on windows of REAL photographs (`real_photos`: tests/golden/real), PCIe-inclusive rate through the product's batch driver, CPU baseline).
+--dump-outputs DIR writes what the last timed step of the headline computed (a fixed seeded sample of its frames) as DIR/<name>.npy: the inputs are seeded, so
+two builds run with the same arguments can be compared output for output.
 """
 import argparse
 import json
@@ -290,6 +292,56 @@ def timed(pipe, steps, warmup, dist=None):
         reg_ms += ms_; reg_launches += n_
     pipe.check()
     return elapsed, reg_ms, reg_launches
+
+
+DUMP_BYTES, DUMP_FRAMES, DUMP_SEED = 64_000_000, 256, 2024
+
+
+def dump_outputs(pipe, out_dir):
+    """`--dump-outputs DIR`: what the last timed step handed its caller, as DIR/<name>.npy, for a fixed seeded sample of the batch's frames (at most
+    DUMP_FRAMES and DUMP_BYTES in all; the same frames for the same --batch, so that two builds compare output for output).  Key points + descriptors,
+    lines + descriptors + line equations, the four matchers' results and every count.  Entries past a frame's count are padding no caller reads: zeroed
+    (matches: -1).  Integers become float32, exactly (key point octave / class_id, line class_id / octave / numOfPixels, descriptor bytes, indices,
+    counts); line equations stay float64.  Call it right after timed(), before anything else runs on the pipeline."""
+    import numpy as np
+    torch = pipe.torch
+    bs = pipe.bufs[(pipe.k - 1) & 1]          # (step k wrote buffer set k & 1; flush() ran its matchers and timed() synchronised)
+    cap, nl = pipe.cap, pipe.nlines
+    per_frame = 4 * (cap * (7 + 32 + 2) + nl * (17 + 32 + 2) + 6) + 8 * (3 * nl + 1)
+    n = max(1, min(pipe.B, DUMP_FRAMES, DUMP_BYTES // per_frame))
+    idx = np.sort(np.random.default_rng(DUMP_SEED).permutation(pipe.B)[:n])
+    sel = torch.from_numpy(idx).to(bs["nk"].device)
+    if sel.is_cuda:       # (tests/test_bench_dump.py hands it host tensors)
+        torch.cuda.synchronize()
+    get = lambda key: bs[key].index_select(0, sel).cpu().numpy()
+    nk, nln = get("nk"), get("nl")
+    kvalid = np.arange(cap)[None, :] < nk[:, None]
+    lvalid = np.arange(nl)[None, :] < nln[:, None]
+
+    def with_ints(a, cols):
+        f = a.copy()
+        f[..., cols] = a.view(np.int32)[..., cols].astype(np.float32)
+        return f
+
+    def masked(a, valid, pad=0):
+        a = np.array(a, dtype=np.float64 if a.dtype == np.float64 else np.float32)
+        a[~valid] = pad
+        return a
+
+    out = {"frame_index": idx.astype(np.float64), "keypoint_count": nk.astype(np.float32), "line_count": nln.astype(np.float32),
+           "keypoints": masked(with_ints(get("kps"), [5, 6]), kvalid), "descriptors": masked(get("desc"), kvalid),
+           "lines": masked(with_ints(get("lines"), [1, 2, 16]), lvalid), "line_descriptors": masked(get("ldesc"), lvalid),
+           "line_equations": masked(get("leq"), lvalid)}
+    for name, key, valid in (("points_map", "kp", kvalid), ("points_last_frame", "kp_last", kvalid), ("lines_map", "ln", lvalid),
+                             ("lines_last_frame", "ln_last", lvalid)):
+        out[name + "_matches"] = masked(get("match_" + key), valid, -1)
+        out[name + "_match_count"] = get("nm_" + key).astype(np.float32)
+    total = sum(a.nbytes for a in out.values())
+    assert total <= DUMP_BYTES, total
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in out.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+    return {"dir": out_dir, "frames": int(n), "of_frames": pipe.B, "bytes": int(total), "arrays": sorted(out)}
 
 
 def _frame_fn(family):
@@ -615,7 +667,13 @@ def main():
     ap.add_argument("--serial", action="store_true", help="diagnostic: everything on one stream (solo kernel durations under rocprofv3)")
     ap.add_argument("--pcie", action="store_true", help="time the PCIe-INCLUSIVE leg instead (plf_batch_extract: pinned host frames in, features + local-map matches "
                     "out in host memory) on every rank; value = aggregate frames/s, plus the aggregate host read rate")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="after the timed steps, write what the last one computed as DIR/<name>.npy (a fixed seeded sample of "
+                    "the frames, at most 64 MB; rank 0's frames)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    if args.dump_outputs and args.pcie:
+        ap.error("--dump-outputs covers the device-resident step, not --pcie")
 
     import torch
     rank = int(os.environ.get("RANK", "0")); local_rank = int(os.environ.get("LOCAL_RANK", "0")); world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -644,6 +702,8 @@ def main():
     out, pipe, fps, elapsed, B = run_headline(args, dist, rank, local_rank, world, B, W, H, NFEAT, NLINES, label, make_pipe)
 
     if rank == 0:
+        if args.dump_outputs:
+            out["dump_outputs"] = dump_outputs(pipe, args.dump_outputs)
         if world > 1:
             out["extras"] = "skipped: tiled32 / fps_vs_in_flight / config3_as_specified / single_frame_latency / natural / pcie_inclusive / cpu_baseline are N = 1 figures"
         out["region_chain_length"] = pipe.chain_stats()

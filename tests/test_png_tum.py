@@ -1,6 +1,7 @@
 """The PNG reader and association parser behind tools/run_tum.py (the harness for the TUM sequences BASELINE configs[0,1,4] name; no image
 library ships with the image, so the decoder is in-tree): round trips through every scan-line filter, the formats the TUM sequences use
 (8-bit RGB colour, 16-bit depth), and the association file of the reference."""
+import hashlib
 import os
 import zlib
 
@@ -55,10 +56,10 @@ def test_association_file_format(tmp_path):
         png.read_associations(p)
 
 
-def test_reference_association_file_parses_if_present():
-    """573 rows in the reference's own file (only in the build container: /root/reference does not exist on the GPU box)"""
-    ref = "/root/reference/Examples/RGB-D/associations/fr1_desk.txt"
-    if not os.path.exists(ref):
-        pytest.skip("reference snapshot not present")
+def test_reference_association_file_parses():
+    """573 rows in the reference's own file (Examples/RGB-D/associations/fr1_desk.txt, stored as tests/golden/fr1_desk_associations.txt)"""
+    ref = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "fr1_desk_associations.txt")
+    with open(ref, "rb") as fh:
+        assert hashlib.sha256(fh.read()).hexdigest() == "86dfcf237cf092cc7466ee2c67dfc0a3a507fe879a1bbe063b962d8a7442c536"
     a = png.read_associations(ref)
     assert len(a) == 573 and a[0][1].startswith("rgb/") and a[0][2].startswith("depth/") and all(a[i][0] < a[i + 1][0] for i in range(len(a) - 1))
