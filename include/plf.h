@@ -205,6 +205,26 @@ int plf_line_profile(plf_line *h, int32_t enable, int32_t reset, double *ms_tota
 /* Test hook: all LSD segments (x1,y1,x2,y2) of frame `frame` in detection order, before the top-N cut. */
 int plf_line_get_segments(plf_line *h, int32_t frame, float *segs, int32_t capacity, int32_t *n_out);
 
+/* Test hook (tests/test_gpu_math.py): the libm-dependent expressions of the parity path (rgbd_pl_slam_amd/csrc/plf_math.h), evaluated on the device.
+ * out_dev[j] = helper `op` at input first + j of the op's domain, j < n; out_dev is caller-owned device memory.  The index -> input maps, the domain sizes
+ * and the element types are listed in oracle/math_oracle.c, which computes the same outputs with glibc.  params: PLF_MATH_PREDICT (log scale factor, nlevels),
+ * PLF_MATH_NFA_TABLE / PLF_MATH_NFA (see there).  stream NULL: synchronous.  PLF_E_BADARG for an unknown op or a range outside the domain. */
+enum {
+    PLF_MATH_CS = 0,          /* LSD pre-pass cs: cos / sin of the float-rounded angle (double2) */
+    PLF_MATH_CS0 = 1,         /* LSD pre-pass cs0: float cos / sin of the angle (float2) */
+    PLF_MATH_RECT_DIR = 2,    /* region2rect direction (double2) */
+    PLF_MATH_LBD_DIR = 3,     /* LBD direction (float2) */
+    PLF_MATH_PREDICT = 4,     /* PredictScale level (int8) */
+    PLF_MATH_SINCOSF = 5,     /* ORB steering angle, glibc's sincosf (float2: sin, cos) */
+    PLF_MATH_KL_ANGLE = 6,    /* KeyLine angle, sampled end points (float) */
+    PLF_MATH_KL_ANGLE_GRID = 7, /* KeyLine angle, integer differences and signed zeros (float) */
+    PLF_MATH_LGAMMA = 8,      /* LSD log_gamma, evaluated on the device (double) */
+    PLF_MATH_LGAMMA_TABLE = 9, /* the log_gamma table the line handles upload, entries 1 .. 65535 (double) */
+    PLF_MATH_NFA_TABLE = 10,  /* the NFA table the line handles upload for LOG_NT = params[0] (double) */
+    PLF_MATH_NFA = 11         /* LSD nfa on the device, sampled (n, k, p); params: LOG_NT, log2 of the largest n / 512 (double) */
+};
+int plf_debug_math(int32_t op, const double *params, int64_t first, int64_t n, void *out_dev, int32_t device, void *stream);
+
 /* ------------------------------------------------------------------------------------------------
  * Matchers -- replace ORB_SLAM2::ORBmatcher / LSDmatcher tracking overloads
  * ---------------------------------------------------------------------------------------------- */

@@ -365,6 +365,16 @@ static double nfa(const lsd_t *L, int n, int k, double p)
     return -log10(bin_tail) - LOG_NT;
 }
 
+/* tests/test_math_host.py, tests/test_gpu_math.py (via math_oracle.c): the two functions above, callable on their own */
+double orc_log_gamma(double x) { return log_gamma(x); }
+double orc_lsd_nfa(double log_nt, int n, int k, double p)
+{
+    lsd_t L;
+    memset(&L, 0, sizeof(L));
+    L.LOG_NT = log_nt;
+    return nfa(&L, n, k, p);
+}
+
 typedef struct { int x, y, taken; } edge_t;
 
 static double rect_nfa(const lsd_t *L, const rect_t *rec)

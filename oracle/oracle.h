@@ -234,6 +234,15 @@ void orc_is_in_frustum_line(const float *xw, const float *normal, const float *m
                             const float *tcw, const float *Ow, const float *cam, const float *bounds, float bf, float log_scale_factor,
                             int nlevels, float cos_limit, float *out6, int32_t *level, float *view_cos, uint8_t *in_view);
 
+/* ---- device-math parity (math_oracle.c; lsd_oracle.c for the LSD functions): the libm-dependent expressions of rgbd_pl_slam_amd/csrc/plf_math.h as the
+ * oracle computes them with glibc, enumerated over the same domains as the test hook plf_debug_math (include/plf.h) */
+double orc_log_gamma(double x);
+double orc_lsd_nfa(double log_nt, int n, int k, double p);
+int64_t orc_math_domain(int32_t op);
+int32_t orc_math_elem_size(int32_t op);
+int orc_math_ref(int32_t op, const double *params, int64_t first, int64_t n, void *out);
+int64_t orc_math_cmp(int32_t op, const double *params, int64_t first, int64_t n, const void *got, int64_t *first_bad, int32_t nbad);
+
 /* ---- CPU baseline driver (bench_oracle.c) */
 double orc_frontend_throughput(const uint8_t *imgs, int n_distinct, int w, int h, int n_frames, int threads, int nfeatures, int nlines,
                                const orc_mappoints *MP, const orc_maplines *ML, float th, float nnratio, long *checksum);

@@ -139,10 +139,7 @@ __global__ void __launch_bounds__(256) k_frustum_points(const float *__restrict_
     const float viewCos = (float)(dot / (double)dist);
     if (viewCos < cos_limit) return;
     const float ratio = max_dist[i] / dist;
-    // logf of the reference's libm is (almost always) the correctly rounded value; the double log rounded to float is too
-    int nScale = (int)ceilf((float)log((double)ratio) / log_scale_factor);
-    if (nScale < 0) nScale = 0;
-    else if (nScale >= nlevels) nScale = nlevels - 1;
+    const int nScale = plf_predict_level(ratio, log_scale_factor, nlevels);
     in_view[i] = 1;
     // mTrackProjXR = u - mbf * invz is contracted as well (so@0xf5dec: vfnmadd132ss)
     proj_x[i] = u; proj_xr[i] = fmaf(-cam.bf, invz, u); proj_y[i] = v; level[i] = nScale; view_cos[i] = viewCos;
@@ -244,9 +241,7 @@ __global__ void __launch_bounds__(256) k_frustum_lines(const float *__restrict__
     const float viewCos = (float)(dot / (double)dist);
     if (viewCos < cos_limit) return;
     const float ratio = max_dist[i] / dist;
-    int nScale = (int)ceilf((float)log((double)ratio) / log_scale_factor);
-    if (nScale < 0) nScale = 0;
-    else if (nScale >= nlevels) nScale = nlevels - 1;
+    const int nScale = plf_predict_level(ratio, log_scale_factor, nlevels);
     in_view[i] = 1;
     x1[i] = u1; y1[i] = v1; x2[i] = u2; y2[i] = v2; level[i] = nScale; view_cos[i] = viewCos;
     if (x1r) x1r[i] = r1;

@@ -8,9 +8,47 @@
 #include <algorithm>
 #include <vector>
 #include <chrono>
+#include <map>
+#include <mutex>
+#include <thread>
 #include <hipcub/hipcub.hpp>
 #include "plf_common.h"
 #include "lsd_geom.h"
+
+// ---- the host-filled tables of the NFA validation (lsd_geom.h).  log_gamma_d and nfa_d of plf_math.h compiled for the host, i.e. against the host's libm: the
+// oracle's.  The device library's exp / log / pow / sinh differ from glibc's in the last bit for some arguments (tests/test_gpu_math.py), so tables filled by the
+// device would carry those differences into every lookup.  Computed once per process (the NFA table once per LOG_NT, ~1.4 M values on up to 11 threads) and kept.
+const double *plf_lgamma_table_host()
+{
+    static const std::vector<double> tab = [] {
+        std::vector<double> t(LGAM_N);
+        t[0] = 0.0;
+        for (int i = 1; i < LGAM_N; i++) t[i] = log_gamma_d((double)i);
+        return t;
+    }();
+    return tab.data();
+}
+
+const double *plf_nfa_table_host(double log_nt)
+{
+    static std::mutex mu;
+    static std::map<double, std::vector<double>> cache;
+    std::lock_guard<std::mutex> lock(mu);
+    auto it = cache.find(log_nt);
+    if (it != cache.end()) return it->second.data();
+    std::vector<double> tab((size_t)NFA_TAB_P * NFA_TAB_ROW);
+    const double *lgam = plf_lgamma_table_host();
+    std::vector<std::thread> th;
+    for (int j = 0; j < NFA_TAB_P; j++)
+        th.emplace_back([&tab, lgam, log_nt, j] {
+            double p = 0.125;
+            for (int q = 0; q < j; q++) p /= 2;
+            for (int n = 0; n < NFA_TAB_N; n++)
+                for (int k = 0; k <= n; k++) tab[(size_t)j * NFA_TAB_ROW + n * (n + 1) / 2 + k] = nfa_d(lgam, log_nt, n, k, p);
+        });
+    for (auto &t : th) t.join();
+    return cache.emplace(log_nt, std::move(tab)).first->second.data();
+}
 
 __global__ void k_lsd_pre(const uint8_t *, ptrdiff_t, ptrdiff_t, float *, double *, double2 *, float2 *, LsdGeom, LsdTaps, const int *, const float2 *,
                           const int *, const float2 *, int *);
@@ -25,7 +63,6 @@ __global__ void k_lsd_spec_grow_budget(float *, const double *, const double2 *,
 __global__ void k_lsd_spec_commit_budget(float *, const double *, const double2 *, const float2 *, uint32_t *, LsdRect *, int *, int *, LsdGeom, SpecBufs, int *);
 __global__ void k_lsd_maxgrad(const float *, const double *, double *, LsdGeom);
 __global__ void k_lsd_seedkeys(const float *, const double *, const double *, uint32_t *, LsdGeom);
-__global__ void k_lsd_lgamma_table(double *);
 __global__ void k_lsd_count_used(const float *, int *, LsdGeom);
 struct NfaEntry { LsdRect r; int frame, nprec, pad0, pad1; };
 struct NfaCounts { int total, alg[6], pad; };
@@ -37,7 +74,6 @@ __global__ void k_nfa_count1(const float *, const NfaEntry *, const int *, int, 
 __global__ void k_nfa_count_w(const float *, const NfaEntry *, const int *, int, int, NfaCounts *, LsdGeom);
 __global__ void k_nfa_count1_w(const float *, const NfaEntry *, const int *, int, int, NfaCounts *, LsdGeom);
 __global__ void k_nfa_eval(int, const double *, const double *, const NfaCounts *, const NfaEntry *, const int *, double *, LsdGeom);
-__global__ void k_nfa_table(double *, const double *, double);
 __global__ void k_nfa_small(const float *, const double *, const LsdRect *, const int *, uint8_t *, float4 *, NfaEntry *, NfaState *, int *, int *, LsdGeom, int, NfaState *, int *, int);
 __global__ void k_nfa_small2(const float *, const double *, const LsdRect *, uint8_t *, float4 *, NfaEntry *, NfaState *, int *, int *, LsdGeom, int, const NfaState *, const int *, int);
 __global__ void k_nfa_math(int, const double *, const NfaEntry *, const NfaState *, NfaState *, NfaEntry *, int *, float4 *, uint8_t *, LsdGeom);
@@ -83,7 +119,7 @@ struct LineTune {
     int nfa_small;        // PLF_NFA_SMALL        2: rect_improve of the rectangles the table covers in one launch (k_nfa_small), 16 lanes per rectangle; 1: only for more
                           //                      than nfa_fused frames in flight (one frame: 4.41 ms with it, 4.63 ms with k_nfa_fused); 0: off
     int nfa_two_pass;     // PLF_NFA_TWO_PASS     1: above nfa_fused frames in flight k_nfa_small only runs stage 0 and queues the undecided rectangles for k_nfa_small2 (stages 1-4)
-    int nfa_table;        // PLF_NFA_TABLE        1: NFA values of rectangles of fewer than 512 pixels come from the per-image-size table (k_nfa_table)
+    int nfa_table;        // PLF_NFA_TABLE        1: NFA values of rectangles of fewer than 512 pixels come from the per-image-size table (plf_nfa_table_host)
     int balance;          // PLF_LSD_BALANCE      1: large batches -- the frames are dealt to the waves of k_lsd_regions2 by chain length (k_lsd_balance); 0: in batch order
     float slow_factor;    // PLF_LSD_SLOW_FACTOR  PLF_W_SLOW: a host-output call that takes more than this many times the median per-frame time of the recent calls (10; 0: off)
     float slow_floor_ms;  // PLF_LSD_SLOW_FLOOR_MS  ... and more than this per frame (20 ms)
@@ -140,7 +176,7 @@ struct plf_line {
     hipStream_t stream;
     uint8_t *d_in, *d_keep, *d_ldesc;
     double *d_modgrad, *d_lineeq, *d_lgam;
-    double *d_nfa_tab;        // nfa(n, k, p) of small rectangles (k_nfa_table), valid for scaled images with LOG_NT == nfa_tab_log_nt
+    double *d_nfa_tab;        // nfa(n, k, p) of small rectangles (plf_nfa_table_host), valid for scaled images with LOG_NT == nfa_tab_log_nt
     double nfa_tab_log_nt;
     // seed_order = 1 only: per-frame max gradient, (bin, pixel) keys before / after the segmented sort, segment offsets, sort scratch
     double *d_maxgrad;
@@ -430,7 +466,7 @@ extern "C" int plf_line_create(const plf_line_params *p, plf_line **out)
     (void)hipFuncSetAttribute((const void *)k_lsd_spec_commit_budget, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024);
     (void)hipFuncSetAttribute((const void *)k_lsd_spec_fused_budget, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024);
     (void)hipGetLastError();
-    hipLaunchKernelGGL(k_lsd_lgamma_table, dim3(65536 / 256), dim3(256), 0, h->stream, h->d_lgam);
+    if (hipMemcpy(h->d_lgam, plf_lgamma_table_host(), LGAM_N * sizeof(double), hipMemcpyHostToDevice) != hipSuccess) { line_free(h); free(h); return PLF_E_HIP; }
     if (hipMemcpy(h->d_lbd, &h->lbd, sizeof(LbdCoefs), hipMemcpyHostToDevice) != hipSuccess) { line_free(h); free(h); return PLF_E_HIP; }
     h->cur_w = -1; h->cur_h = -1;
     rc = line_configure(h, p->max_width, p->max_height);
@@ -696,7 +732,8 @@ static int line_enqueue(plf_line *h, const uint8_t *d_gray, int B, ptrdiff_t pit
     // kernels: first evaluation + 5 search stages, each = (wave-parallel pixel count, lane-parallel NFA math) over work lists compacted over the batch
     const int nfa_fused_max = T.nfa_fused;
     if (T.nfa_table && h->nfa_tab_log_nt != g.log_nt) {   // (first batch of this image size)
-        hipLaunchKernelGGL(k_nfa_table, dim3(NFA_TAB_N, NFA_TAB_P), dim3(256), 0, s, h->d_nfa_tab, h->d_lgam, g.log_nt);
+        // (a host table that lives until the process ends: the copy may run after this call has returned)
+        PLF_HIP_TRY(hipMemcpyAsync(h->d_nfa_tab, plf_nfa_table_host(g.log_nt), (size_t)NFA_TAB_P * NFA_TAB_ROW * sizeof(double), hipMemcpyHostToDevice, s));
         h->nfa_tab_log_nt = g.log_nt;
     }
     const bool small_first = T.nfa_table && (T.nfa_small >= 2 || (T.nfa_small == 1 && B > nfa_fused_max));

@@ -54,7 +54,7 @@ __global__ void __launch_bounds__(256) k_lsd_finalize(const float4 *__restrict__
         const int x0 = __float2int_rn(e0), y0 = __float2int_rn(e1), x1 = __float2int_rn(e2), y1 = __float2int_rn(e3);
         const int dx = abs(x1 - x0), dy = abs(y1 - y0);
         kl.numOfPixels = (dx > dy ? dx : dy) + 1;
-        kl.angle = (float)atan2((double)(kl.endPointY - kl.startPointY), (double)(kl.endPointX - kl.startPointX));
+        kl.angle = plf_keyline_angle(kl.endPointY - kl.startPointY, kl.endPointX - kl.startPointX);
         kl.class_id = k;
         kl.octave = 0;
         kl.size = (kl.endPointX - kl.startPointX) * (kl.endPointY - kl.startPointY);
@@ -327,7 +327,8 @@ __global__ void PLF_LBD_OCC __launch_bounds__(64) k_lbd(const short2 *__restrict
     const short halfWidth = (short)((lengthOfLSP - 1) / 2);
     const float lineMiddlePointX = (float)(0.5 * (double)(kl.sPointInOctaveX + kl.ePointInOctaveX));
     const float lineMiddlePointY = (float)(0.5 * (double)(kl.sPointInOctaveY + kl.ePointInOctaveY));
-    const float dL0 = (float)cos((double)kl.angle), dL1 = (float)sin((double)kl.angle);
+    float dL0, dL1;
+    plf_lbd_dir(kl.angle, &dL0, &dL1);
     const float dO0 = -dL1, dO1 = dL0;
     if (t < 63) {
         float sCorX = -dL0 * (float)halfWidth + dL1 * (float)halfHeight + lineMiddlePointX;

@@ -100,8 +100,12 @@ struct SpecBufs {
     int *band_ticks;    // [frame][band][2]: run time of the band wave in 100 MHz ticks, accepted pixels it logged (diagnostics: how well the band shares are balanced)
 };
 
-// NFA table (k_nfa_table): rectangles of fewer than NFA_TAB_N pixels, p = 1/8 * 2^-j for j < NFA_TAB_P
+// NFA table (filled on the host: line_host.hip, plf_nfa_table_host): rectangles of fewer than NFA_TAB_N pixels, p = 1/8 * 2^-j for j < NFA_TAB_P
 #ifndef NFA_TAB_N
 #define NFA_TAB_N 512
 #endif
 #define NFA_TAB_P 11
+#define NFA_TAB_ROW (NFA_TAB_N * (NFA_TAB_N + 1) / 2)   // (n, k <= n) -> n (n + 1) / 2 + k; table index j * NFA_TAB_ROW + n (n + 1) / 2 + k, p = 2^-(3 + j)
+// host-filled tables (line_host.hip), computed once per process (the NFA table once per LOG_NT) and kept: uploaded by every line handle and by plf_debug_math
+const double *plf_lgamma_table_host();
+const double *plf_nfa_table_host(double log_nt);

@@ -243,15 +243,11 @@ __global__ void __launch_bounds__(PRE_NT) k_lsd_pre(const uint8_t *__restrict__ 
         const float deg = plf_fast_atan2_1div(s_fx[i], s_fy[i]);
         angf[o] = deg;
         s_angt[loc] = deg;
-        const double ad = (double)deg * DEG2RAD_D;
-        const double af = (double)(float)ad;
-        double sf, cf;
-        sincos(af, &sf, &cf);   // cs: cos / sin of the FLOAT-rounded angle, the increments region_grow adds
+        double cf, sf;
+        float c0, s0;
+        plf_lsd_cs(deg, &cf, &sf, &c0, &s0);   // cs: cos / sin of the FLOAT-rounded angle; cs0: float cos / sin of the un-rounded one (plf_math.h)
         csf[o] = make_double2(cf, sf);
-        // cs0: float(cos(ad)), float(sin(ad)) of the un-rounded angle.  ad = af + eps with |eps| <= 2^-25 |ad|: the second-order expansion around af is
-        // within ~2 ulp (double) of cos / sin (ad), i.e. as close to the correctly rounded value as a second libm call is, at a twentieth of its cost
-        const double eps = ad - af, h = 0.5 * eps * eps;
-        cs0f[o] = make_float2((float)(cf - eps * sf - h * cf), (float)(sf + eps * cf - h * sf));
+        cs0f[o] = make_float2(c0, s0);
     }
     // Static singles (LsdGeom::sgl; see singles_run in the region-growing section): one BIT per pixel, set iff the pixel has an angle and none of its 8
     // neighbours can pass the first alignment test of a region seeded there -- no neighbour's angle is within the tolerance + 0.001 degrees of the pixel's
@@ -483,24 +479,7 @@ __device__ __forceinline__ int wave_max_i(int v) { PLF_DPP_REDUCE(v, max, dpp_mo
 __device__ __forceinline__ double wave_min_d(double v) { PLF_DPP_REDUCE(v, fmin, dpp_mov_d) return readlane_d(v, 63); }
 __device__ __forceinline__ double wave_max_d(double v) { PLF_DPP_REDUCE(v, fmax, dpp_mov_d) return readlane_d(v, 63); }
 
-// Thresholds of the cheap alignment pre-test of region_grow (see there): t1 <= tan(prec - delta), t2 >= tan(prec + delta), delta = 0.05 degrees.
-// The pre-test only sorts candidates into "surely aligned", "surely not" and "border" (decided by the reference's own test), so ANY t1 below and
-// t2 above those tangents is sound: single-precision tanf with a 1e-4 relative safety factor (its error is ~1e-7; the band is ~2.5e-3 wide) keeps
-// the double-precision tan -- a double-double routine that alone costs ~40 VGPRs -- out of this kernel.
-// NaN thresholds switch the pre-test off (every decision is then taken by the exact test): both comparisons of the classification are false for a NaN, which
-// leaves no lane "surely aligned" and none "surely not" -- without a test of its own in the accept loop.
-struct GrowTh { float t1, t2; };
-__device__ __forceinline__ GrowTh grow_thresholds(double prec)
-{
-    const double delta = 8.7266462599716e-4;
-    GrowTh t;
-    t.t1 = __uint_as_float(0x7FC00000u); t.t2 = t.t1;
-    if (prec - delta > 0.0 && prec + delta < 1.55) {
-        t.t1 = tanf((float)(prec - delta)) * (1.0f - 1.0e-4f);
-        t.t2 = tanf((float)(prec + delta)) * (1.0f + 1.0e-4f);
-    }
-    return t;
-}
+// (GrowTh, grow_thresholds: plf_math.h)
 
 // 3x3 neighbourhood data of up to 7 queued region points: lane = slot * 9 + k9, neighbours in (yy, xx) order
 struct Grp { uint32_t w; uint32_t fl; double csx, csy; int a; uint32_t xy; };   // w: angle word, fl: USED flag of the bitmap mode (candidate iff w < 0x80000000, fl == 0 and the lane is valid)
@@ -822,7 +801,8 @@ __device__ void region2rect(RegCtx &C, int n, double reg_angle, double prec, dou
         if (d < 0) d = -d;
         if (d > prec) theta += PI_D;
     }
-    const double dx = cos(theta), dy = sin(theta);
+    double dx, dy;
+    plf_rect_dir(theta, &dx, &dy);
     double l_min = 0, l_max = 0, w_min = 0, w_max = 0;
     for (int i = lane; i < n; i += 64) {
         const uint32_t q = rxy_get(C, i);
@@ -2806,116 +2786,13 @@ extern "C" void plf_lsd_timing_dump()
 // ------------------------------------------------------------------------------------------------
 // NFA validation (one wave per rectangle)
 // ------------------------------------------------------------------------------------------------
-__device__ __forceinline__ double log_gamma_d(double x)
-{
-    if (x > 15.0) return 0.918938533204673 + (x - 0.5) * log(x) - x + 0.5 * x * log(x * sinh(1 / x) + 1 / (810.0 * pow(x, 6.0)));
-    const double q[7] = {75122.6331530, 80916.6278952, 36308.2951477, 8687.24529705, 1168.92649479, 83.8676043424, 2.50662827511};
-    double a = (x + 0.5) * log(x + 5.5) - (x + 5.5);
-    double b = 0;
-    for (int n = 0; n < 7; ++n) {
-        a -= log(x + (double)n);
-        b += q[n] * pow(x, (double)n);
-    }
-    return a + log(b);
-}
-
-__device__ __forceinline__ bool double_equal_d(double a, double b)
-{
-    if (a == b) return true;
-    const double abs_diff = fabs(a - b), aa = fabs(a), bb = fabs(b);
-    double abs_max = (aa > bb) ? aa : bb;
-    if (abs_max < 2.2250738585072014e-308) abs_max = 2.2250738585072014e-308;
-    return (abs_diff / abs_max) <= (100.0 * 2.2204460492503131e-16);
-}
-
-// log_gamma(i) for integer i in [0, LGAM_N): filled once per handle by k_lsd_lgamma_table with the very same
-// device function, so a lookup is bit-identical to evaluating it in place (3 calls x ~15 transcendentals saved
-// per NFA evaluation).
-#define LGAM_N 65536
-__device__ const double *g_lgam_table = nullptr;
-
-__global__ void k_lsd_lgamma_table(double *tab)
-{
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < LGAM_N) tab[i] = i > 0 ? log_gamma_d((double)i) : 0.0;
-}
-
-__device__ __forceinline__ double log_gamma_int(const double *__restrict__ tab, int i)
-{
-    return (i > 0 && i < LGAM_N) ? tab[i] : log_gamma_d((double)i);
-}
-
-// The rest of the binomial tail cannot change the result any more: the ratio term(i+1) / term(i) = mult_term falls with i, so once it is below 1 every later term is
-// smaller than this one, and a term below bin_tail * 2^-54 is less than half an ulp of bin_tail -- every remaining `bin_tail += term` returns bin_tail unchanged
-// (round to nearest), and whichever way the loop ends it returns -log10(bin_tail) - LOG_NT of this very bin_tail.  (A rectangle of a few thousand pixels with more
-// aligned pixels than n p -- any real edge -- spends nearly all of upstream's n / 2 - k iterations adding such terms.  If bin_tail * 2^-54 underflows the test
-// never fires and the loop runs as upstream's.)
-#define NFA_DEAD_TAIL(mult, term, bin_tail) ((mult) < 1.0 && (term) < (bin_tail) * 0x1p-54)
-
-__device__ double nfa_d(const double *__restrict__ lgam, double LOG_NT, int n, int k, double p)
-{
-    if (n == 0 || k == 0) return -LOG_NT;
-    if (n == k) return -LOG_NT - (double)n * log10(p);
-    const double p_term = p / (1 - p);
-    const double log1term = log_gamma_int(lgam, n + 1) - log_gamma_int(lgam, k + 1) - log_gamma_int(lgam, n - k + 1) +
-                            (double)k * log(p) + (double)(n - k) * log(1.0 - p);
-    double term = exp(log1term);
-    if (double_equal_d(term, 0)) {
-        if ((double)k > (double)n * p) return -log1term / 2.30258509299404568402 - LOG_NT;
-        return -LOG_NT;
-    }
-    double bin_tail = term;
-    const double tolerance = 0.1;
-    int i = k + 1;
-    // While bin_term >= 1 (i.e. n - i + 1 >= i) the reference's loop has no exit test: such iterations are taken four at a time so that the four
-    // divisions -- independent of the running product -- overlap; the product / sum chain itself is unchanged, operation for operation.
-    while (i + 7 <= n && n - (i + 7) + 1 >= i + 7) {
-        double b[8], m[8];
-#pragma unroll
-        for (int q = 0; q < 8; q++) b[q] = (double)(n - i - q + 1) / (double)(i + q);
-#pragma unroll
-        for (int q = 0; q < 8; q++) m[q] = b[q] * p_term;
-#pragma unroll
-        for (int q = 0; q < 8; q++) { term *= m[q]; bin_tail += term; }
-        i += 8;
-        if (NFA_DEAD_TAIL(m[7], term, bin_tail)) return -log10(bin_tail) - LOG_NT;
-    }
-    while (i + 3 <= n && n - (i + 3) + 1 >= i + 3) {
-        const double b0 = (double)(n - i + 1) / (double)i, b1 = (double)(n - i) / (double)(i + 1), b2 = (double)(n - i - 1) / (double)(i + 2),
-                     b3 = (double)(n - i - 2) / (double)(i + 3);
-        const double m0 = b0 * p_term, m1 = b1 * p_term, m2 = b2 * p_term, m3 = b3 * p_term;
-        term *= m0; bin_tail += term;
-        term *= m1; bin_tail += term;
-        term *= m2; bin_tail += term;
-        term *= m3; bin_tail += term;
-        i += 4;
-        if (NFA_DEAD_TAIL(m3, term, bin_tail)) return -log10(bin_tail) - LOG_NT;
-    }
-    for (; i <= n; ++i) {
-        const double bin_term = (double)(n - i + 1) / (double)i;
-        const double mult_term = bin_term * p_term;
-        term *= mult_term;
-        bin_tail += term;
-        if (bin_term < 1) {
-            const double err = term * ((1 - pow(mult_term, (double)(n - i + 1))) / (1 - mult_term) - 1);
-            if (err < tolerance * fabs(-log10(bin_tail) - LOG_NT) * bin_tail) break;
-        }
-    }
-    return -log10(bin_tail) - LOG_NT;
-}
+// (log_gamma_d, log_gamma_int, nfa_d, nfa_head / nfa_tail: plf_math.h)
 
 // NFA values of small rectangles, tabulated: rect_improve asks for nfa(n, k, p) tens of millions of times per large batch (9,600 values per VGA frame), nearly
 // always with a pixel count n of a few dozen to a few hundred and always with p = 1/8 * 2^-j, j = 0..10 (region2rect's p, halved by the two precision stages).  The
-// table holds nfa_d's own result for every n < NFA_TAB_N, k <= n and those eleven p -- filled by k_nfa_table with the very same device function (the lgamma table's
-// argument: a lookup is bit-identical to evaluating in place), once per scaled-image size (LOG_NT enters the loop's exit test, so the values depend on it).
-#define NFA_TAB_ROW (NFA_TAB_N * (NFA_TAB_N + 1) / 2)   // (n, k <= n) -> n (n + 1) / 2 + k
-__global__ void __launch_bounds__(256) k_nfa_table(double *__restrict__ tab, const double *__restrict__ lgam, double log_nt)
-{
-    const int n = blockIdx.x, j = blockIdx.y;
-    double p = 0.125;
-    for (int q = 0; q < j; q++) p /= 2;
-    for (int k = threadIdx.x; k <= n; k += 256) tab[(size_t)j * NFA_TAB_ROW + n * (n + 1) / 2 + k] = nfa_d(lgam, log_nt, n, k, p);
-}
+// table holds nfa_d's result for every n < NFA_TAB_N, k <= n and those eleven p, once per scaled-image size (LOG_NT enters the loop's exit test, so the values
+// depend on it).  It is filled on the HOST with the same nfa_d compiled against the host's libm -- the oracle's -- and uploaded (line_host.hip, plf_nfa_table_host):
+// the device library's exp / log / pow differ from glibc's in the last bit (tests/test_gpu_math.py), the host's do not.  Likewise the log_gamma table.
 
 // true (and v) if (n, k, p) is tabulated
 __device__ __forceinline__ bool nfa_lookup(const double *__restrict__ tab, int n, int k, double p, double &v)
@@ -3422,7 +3299,7 @@ __global__ void __launch_bounds__(64) k_nfa_math(int stage, const double *__rest
 // ------------------------------------------------------------------------------------------------
 // rect_improve of one SMALL rectangle by a group of 16 lanes, all five stages in one launch (large batches).  Two thirds of a frame's ~550 rectangles are small
 // regions that fail the first test and walk through all five stages (22 pixel counts, 21 NFA values each) only to be rejected; with the staged kernels above that is
-// 17 grid-wide launches whose eval / math steps mostly move 112-byte work-list entries around.  Here every NFA value is one load from k_nfa_table's table and the
+// 17 grid-wide launches whose eval / math steps mostly move 112-byte work-list entries around.  Here every NFA value is one load from the NFA table and the
 // "keep it if better" chain stays in registers (the same chain as k_nfa_math, the same rect_count).  A rectangle with a candidate the table does not hold (512 pixels
 // or more) is handed, untouched, to the staged kernels through their stage-0 work list, exactly as k_nfa_init would have queued it.
 // ------------------------------------------------------------------------------------------------
@@ -3592,32 +3469,7 @@ __device__ __forceinline__ double nfa_bcast(double v, int src) { return shfl_d(v
 // iterations per NFA value, and the fp64 division -- 14 of the 17 instructions of an iteration -- does not depend on the running product at all.  So the up to six
 // chains of a step (lanes 0..5) run in lock step and ALL 64 lanes compute the divisions of the next 512 iterations of every chain into LDS first; the chain lanes
 // then only multiply and add.  Every operation and its order inside a chain are those of nfa_d (the division is the same IEEE operation whichever lane does it).
-struct NfaIt { double term, bin_tail, p_term, val; int i, n, iend; bool live; };
 #define NFA_COOP_BLK 512
-
-__device__ __forceinline__ NfaIt nfa_head(const double *__restrict__ lgam, double LOG_NT, int n, int k, double p)
-{
-    NfaIt it;
-    it.live = false; it.term = it.bin_tail = it.p_term = 0.0; it.i = it.iend = 0; it.n = n;
-    if (n == 0 || k == 0) { it.val = -LOG_NT; return it; }
-    if (n == k) { it.val = -LOG_NT - (double)n * log10(p); return it; }
-    it.p_term = p / (1 - p);
-    const double log1term = log_gamma_int(lgam, n + 1) - log_gamma_int(lgam, k + 1) - log_gamma_int(lgam, n - k + 1) +
-                            (double)k * log(p) + (double)(n - k) * log(1.0 - p);
-    const double term = exp(log1term);
-    if (double_equal_d(term, 0)) {
-        it.val = ((double)k > (double)n * p) ? -log1term / 2.30258509299404568402 - LOG_NT : -LOG_NT;
-        return it;
-    }
-    it.live = true; it.term = term; it.bin_tail = term;
-    int i = k + 1;
-    it.i = i;
-    // the iterations nfa_d takes without an exit test (its blocks of 8, then of 4)
-    while (i + 7 <= n && n - (i + 7) + 1 >= i + 7) i += 8;
-    while (i + 3 <= n && n - (i + 3) + 1 >= i + 3) i += 4;
-    it.iend = i;
-    return it;
-}
 
 // all 64 lanes; `it` of a lane that runs no chain has live == false.  tab: NFA_COOP_BLK doubles per chain lane (lanes 0..5)
 __device__ __forceinline__ void nfa_coop(NfaIt &it, LDS_PTR(double) tab, double LOG_NT)
@@ -3668,25 +3520,6 @@ __device__ __forceinline__ void nfa_coop(NfaIt &it, LDS_PTR(double) tab, double 
     }
 }
 
-__device__ __forceinline__ double nfa_tail(const NfaIt &it, double LOG_NT)
-{
-    if (!it.live) return it.val;
-    const int n = it.n;
-    double term = it.term, bin_tail = it.bin_tail;
-    const double p_term = it.p_term, tolerance = 0.1;
-    for (int i = it.iend; i <= n; ++i) {
-        const double bin_term = (double)(n - i + 1) / (double)i;
-        const double mult_term = bin_term * p_term;
-        term *= mult_term;
-        bin_tail += term;
-        if (bin_term < 1) {
-            const double err = term * ((1 - pow(mult_term, (double)(n - i + 1))) / (1 - mult_term) - 1);
-            if (err < tolerance * fabs(-log10(bin_tail) - LOG_NT) * bin_tail) break;
-        }
-    }
-    return -log10(bin_tail) - LOG_NT;
-}
-
 // wave-uniform condition as a scalar: the compiler cannot see that the NFA values are the same in every lane and would turn `if (c) { rect = r; }` into 24 selects
 // (v_cndmask_b32_e32 back to back: 17-40 cycles each, profiles/r03_valu_issue.json) instead of a branch over 24 moves
 __device__ __forceinline__ bool uni(bool c) { return __builtin_amdgcn_readfirstlane((int)c) != 0; }
@@ -3695,7 +3528,7 @@ __device__ __forceinline__ bool uni(bool c) { return __builtin_amdgcn_readfirstl
 __device__ __forceinline__ NfaIt nfa_head_tab(const double *__restrict__ lgam, const double *__restrict__ nfatab, double LOG_NT, int n, int k, double p)
 {
     double v;
-    if (nfatab && nfa_lookup(nfatab, n, k, p, v)) {   // (k_nfa_table's value: bit-identical to evaluating here)
+    if (nfatab && nfa_lookup(nfatab, n, k, p, v)) {   // (the host-filled table: nfa_d against glibc, i.e. the oracle's value)
         NfaIt it;
         it.live = false; it.term = it.bin_tail = it.p_term = 0.0; it.i = it.iend = 0; it.n = n; it.val = v;
         return it;

@@ -479,10 +479,7 @@ __global__ void __launch_bounds__(256) k_match_lastframe(const FrameDev *__restr
                 const float maxDistance = 1.2f * RL.max_dist[i], minDistance = 0.8f * RL.min_dist[i];
                 if (dist3D < minDistance || dist3D > maxDistance) act = false;
                 const float ratio = RL.max_dist[i] / dist3D;
-                // logf of the reference's libm is (almost always) the correctly rounded value; the double log rounded to float is too
-                lvl = (int)ceilf((float)log((double)ratio) / RL.log_scale);
-                if (lvl < 0) lvl = 0;
-                else if (lvl >= F.nlevels) lvl = F.nlevels - 1;
+                lvl = plf_predict_level(ratio, RL.log_scale, F.nlevels);
             }
             if (act) pr = make_float4(u, v, invzc, th * F.scale_factors[RL.on ? lvl : Lf.keys[i].octave]);
         }
@@ -842,9 +839,7 @@ __device__ __forceinline__ bool project_gate(const FrameDev &F, const Pts3Dev &P
     }
     // MapPoint::PredictScale(float, KeyFrame*) so@0x8fb60 (logf of glibc: the correctly rounded value, see k_match_lastframe)
     const float ratio = P.max_dist[i] / dist3D;
-    lvl = (int)ceilf((float)log((double)ratio) / C.log_scale);
-    if (lvl < 0) lvl = 0;
-    else if (lvl >= F.nlevels) lvl = F.nlevels - 1;
+    lvl = plf_predict_level(ratio, C.log_scale, F.nlevels);
     radius = th * F.scale_factors[lvl];
     return true;
 }

@@ -1,0 +1,326 @@
+// plf_math.h -- every libm-dependent expression of the parity path, defined once.
+//
+// The kernels call these helpers, the test hook plf_debug_math (math_debug.hip) evaluates them over their whole input domain on the device, and
+// tests/cpp/math_host.cpp compiles this very header with g++ against glibc -- the library the oracle (oracle/*.c) and the reference binary use -- so
+// that the formulas themselves can be checked exhaustively on the CPU.  Outside HIP the device intrinsics are shimmed by their IEEE definitions.
+#pragma once
+#include <math.h>
+#include <stdint.h>
+
+#if defined(__HIPCC__)
+#include <hip/hip_runtime.h>
+#define PLF_MATH __host__ __device__ __forceinline__
+#define PLF_MATH_CALL static __host__ __device__   // (not forced inline: called from many sites)
+#else
+#include <string.h>
+#define PLF_MATH static inline
+#define PLF_MATH_CALL static
+static inline float __fdiv_rn(float a, float b) { return a / b; }
+static inline uint32_t __float_as_uint(float f) { uint32_t u; memcpy(&u, &f, 4); return u; }
+static inline float __uint_as_float(uint32_t u) { float f; memcpy(&f, &u, 4); return f; }
+#endif
+
+#define PLF_PI_D 3.1415926535897932384626433832795
+#define PLF_DEG2RAD_D (PLF_PI_D / 180)
+
+// cv::fastAtan2 (OpenCV 3.3 scalar path), degrees in [0,360].  Plain mul/add, no FMA (-ffp-contract=off).
+PLF_MATH float plf_fast_atan2(float y, float x)
+{
+    const float p1 = (float)(0.9997878412794807 * (180 / 3.14159265358979323846));
+    const float p3 = (float)(-0.3258083974640975 * (180 / 3.14159265358979323846));
+    const float p5 = (float)(0.1555786518463281 * (180 / 3.14159265358979323846));
+    const float p7 = (float)(-0.04432655554792128 * (180 / 3.14159265358979323846));
+    const float eps = (float)2.2204460492503131e-16;
+    float ax = fabsf(x), ay = fabsf(y);
+    float a, c, c2;
+    if (ax >= ay) {
+        c = __fdiv_rn(ay, ax + eps);
+        c2 = c * c;
+        a = (((p7 * c2 + p5) * c2 + p3) * c2 + p1) * c;
+    } else {
+        c = __fdiv_rn(ax, ay + eps);
+        c2 = c * c;
+        a = 90.f - (((p7 * c2 + p5) * c2 + p3) * c2 + p1) * c;
+    }
+    if (x < 0) a = 180.f - a;
+    if (y < 0) a = 360.f - a;
+    return a;
+}
+// the same arithmetic with ONE division (the two branches above each carry their own ~12-instruction IEEE division): numerator = the smaller of |x|, |y|,
+// denominator = the larger + eps; for |x| == |y| both forms divide the same numbers
+PLF_MATH float plf_fast_atan2_1div(float y, float x)
+{
+    const float p1 = (float)(0.9997878412794807 * (180 / 3.14159265358979323846));
+    const float p3 = (float)(-0.3258083974640975 * (180 / 3.14159265358979323846));
+    const float p5 = (float)(0.1555786518463281 * (180 / 3.14159265358979323846));
+    const float p7 = (float)(-0.04432655554792128 * (180 / 3.14159265358979323846));
+    const float eps = (float)2.2204460492503131e-16;
+    const float ax = fabsf(x), ay = fabsf(y);
+    const bool xge = ax >= ay;
+    const float c = __fdiv_rn(xge ? ay : ax, (xge ? ax : ay) + eps);
+    const float c2 = c * c;
+    const float t = (((p7 * c2 + p5) * c2 + p3) * c2 + p1) * c;
+    float a = xge ? t : 90.f - t;
+    if (x < 0) a = 180.f - a;
+    if (y < 0) a = 360.f - a;
+    return a;
+}
+
+// sincosf as the reference's libm computes it (glibc >= 2.28 sysdeps/ieee754/flt-32/s_sincosf.c: quadrant
+// reduction and two degree-7/8 polynomials evaluated in double, result rounded to float).  The reference
+// binary calls sincosf@plt for the BRIEF steering angle (so@0x77803); a merely "correctly rounded" sin/cos
+// differs from it by 1 ulp for a few percent of the angles, which can move a sample by one pixel.  This is the
+// same sequence of IEEE double operations (no FMA), verified bit-identical to glibc 2.35 on 2*10^8 angles
+// (oracle/orb_oracle.c: orc_sincosf_glibc, tests/test_oracle_props.py) and on every ORB angle of the device
+// (tests/test_gpu_math.py).  Valid for 0 <= |y| < 120.
+PLF_MATH void plf_sincosf_glibc(float y, float *sinp, float *cosp)
+{
+    const double hpi_inv = 0x1.45F306DC9C883p+23, hpi = 0x1.921FB54442D18p0;
+    const double C0 = 0x1p0, C1 = -0x1.ffffffd0c621cp-2, C2 = 0x1.55553e1068f19p-5, C3 = -0x1.6c087e89a359dp-10,
+                 C4 = 0x1.99343027bf8c3p-16, S1 = -0x1.555545995a603p-3, S2 = 0x1.1107605230bc4p-7, S3 = -0x1.994eb3774cf24p-13;
+    double x = (double)y;
+    const uint32_t top = (__float_as_uint(y) >> 20) & 0x7ff;
+    int n = 0;
+    double sgn = 1.0, flip = 1.0;  // flip = -1 selects the negated cosine table (quadrants 2,3)
+    if (top < ((0x3f490fdbu >> 20) & 0x7ff)) {  // |y| < pi/4 (compared on the top 12 bits, as glibc does)
+        if (top < ((0x39800000u >> 20) & 0x7ff)) { *sinp = y; *cosp = 1.0f; return; }  // |y| < 2^-12
+    } else {
+        const double r = x * hpi_inv;
+        n = ((int)r + 0x800000) >> 24;
+        x = x - (double)n * hpi;
+        const int q = n & 3;
+        sgn = (q == 1 || q == 2) ? -1.0 : 1.0;
+        if (n & 2) flip = -1.0;
+    }
+    const double xr = x;      // reduced argument (x*x uses the unsigned one)
+    const double xs = x * sgn;
+    const double x2 = xr * xr;
+    const double c0 = C0 * flip, c1k = C1 * flip, c2k = C2 * flip, c3k = C3 * flip, c4k = C4 * flip;  // exact sign flips
+    const double x4 = x2 * x2;
+    const double x3 = x2 * xs;
+    const double c2 = c3k + x2 * c4k;
+    const double s1 = S2 + x2 * S3;
+    const double c1 = c0 + x2 * c1k;
+    const double x5 = x3 * x2;
+    const double x6 = x4 * x2;
+    const double s = xs + x3 * S1;
+    const double c = c1 + x4 * c2k;
+    const float sv = (float)(s + x5 * s1), cv = (float)(c + x6 * c2);
+    if (n & 1) { *sinp = cv; *cosp = sv; } else { *sinp = sv; *cosp = cv; }
+}
+
+// Thresholds of the cheap alignment pre-test of region_grow (lsd_kernels.hip): t1 <= tan(prec - delta), t2 >= tan(prec + delta), delta = 0.05 degrees.
+// The pre-test only sorts candidates into "surely aligned", "surely not" and "border" (decided by the reference's own test), so ANY t1 below and
+// t2 above those tangents is sound: single-precision tanf with a 1e-4 relative safety factor (its error is ~1e-7; the band is ~2.5e-3 wide) keeps
+// the double-precision tan -- a double-double routine that alone costs ~40 VGPRs -- out of this kernel.
+// NaN thresholds switch the pre-test off (every decision is then taken by the exact test): both comparisons of the classification are false for a NaN, which
+// leaves no lane "surely aligned" and none "surely not" -- without a test of its own in the accept loop.
+struct GrowTh { float t1, t2; };
+PLF_MATH GrowTh grow_thresholds(double prec)
+{
+    const double delta = 8.7266462599716e-4;
+    GrowTh t;
+    t.t1 = __uint_as_float(0x7FC00000u); t.t2 = t.t1;
+    if (prec - delta > 0.0 && prec + delta < 1.55) {
+        t.t1 = tanf((float)(prec - delta)) * (1.0f - 1.0e-4f);
+        t.t2 = tanf((float)(prec + delta)) * (1.0f + 1.0e-4f);
+    }
+    return t;
+}
+
+// LSD pre-pass, per pixel with a level-line angle `deg` (fastAtan2 degrees, [0, 360]); the reference keeps angle = double(deg) * pi / 180.
+//   cs  = cos / sin of the FLOAT-rounded angle (`sumdx += cos(float(angle))`, ::cos(double)): the increments region_grow adds to its float sums
+//   cs0 = float(cos(angle)), float(sin(angle)) of the un-rounded angle: the initial sums of a region seeded at the pixel
+// cs0 comes from a second-order expansion around af = double(float(ad)): ad = af + eps with |eps| <= 2^-25 |ad|, so the expansion is within ~2 ulp
+// (double) of cos / sin (ad) in RELATIVE terms wherever the result is not much smaller than |eps| -- i.e. everywhere except within a few float ulps of a
+// multiple of pi/2, where the function it approximates has a root and the two terms cancel (deg = 90 and 180 come out 1 float ulp off: the gradients of
+// axis-aligned edges).  There (|d| < 2^-12, d = ad - k pi/2 in double-double, exact subtraction by Sterbenz) the component with the root is
+// +-sin(d) = +-(d - d^3 / 6), whose truncation is below 2^-55 relative; the other component is within 2^-24 of +-1 and keeps the expansion.
+PLF_MATH void plf_lsd_cs(float deg, double *cfp, double *sfp, float *c0p, float *s0p)
+{
+    const double ad = (double)deg * PLF_DEG2RAD_D;
+    const double af = (double)(float)ad;
+    double sf, cf;
+    sincos(af, &sf, &cf);
+    *cfp = cf; *sfp = sf;
+    const double eps = ad - af, h = 0.5 * eps * eps;
+    float c0 = (float)(cf - eps * sf - h * cf), s0 = (float)(sf + eps * cf - h * sf);
+    const int k = (int)(ad * 0x1.45f306dc9c883p-1 + 0.5);   // nearest multiple of pi/2 (ad in [0, 2 pi])
+    const double hi = k == 1 ? 0x1.921fb54442d18p+0 : k == 2 ? 0x1.921fb54442d18p+1 : k == 3 ? 0x1.2d97c7f3321d2p+2 : k == 4 ? 0x1.921fb54442d18p+2 : 0.0;
+    const double lo = k == 1 ? 0x1.1a62633145c07p-54 : k == 2 ? 0x1.1a62633145c07p-53 : k == 3 ? 0x1.a79394c9e8a0ap-53 : k == 4 ? 0x1.1a62633145c07p-52 : 0.0;
+    const double d = (ad - hi) - lo;
+    if (fabs(d) < 0x1p-12) {
+        const float r = (float)(d - d * d * d * (1.0 / 6));   // sin(d)
+        if (k & 1) c0 = k == 1 ? -r : r;                    // cos(pi/2 + d) = -sin d, cos(3 pi/2 + d) = sin d
+        else s0 = k == 2 ? -r : r;                          // sin(d), sin(pi + d) = -sin d, sin(2 pi + d) = sin d
+    }
+    *c0p = c0; *s0p = s0;
+}
+
+// region2rect: the direction of the rectangle, theta in radians (double(fastAtan2 degrees) * pi / 180, plus pi when it points against the region angle)
+PLF_MATH void plf_rect_dir(double theta, double *dx, double *dy)
+{
+    *dx = cos(theta);
+    *dy = sin(theta);
+}
+
+// KeyLine::angle = (float)atan2((double)(endPointY - startPointY), (double)(endPointX - startPointX)), given the two float differences
+PLF_MATH float plf_keyline_angle(float dy, float dx) { return (float)atan2((double)dy, (double)dx); }
+
+// LBD direction of a line: dL = ((float)cos((double)angle), (float)sin((double)angle)) (::cos(double) under the reference's compiler)
+PLF_MATH void plf_lbd_dir(float angle, float *c, float *s)
+{
+    *c = (float)cos((double)angle);
+    *s = (float)sin((double)angle);
+}
+
+// MapPoint::PredictScale / MapLine::PredictScale: ceilf(logf(ratio) / log_scale_factor) clamped to [0, nlevels).  The double log rounded to float differs from
+// glibc's logf on some ratios, but the LEVEL does not: equal for every positive finite float ratio at scale factors 1.1, 1.2 and 1.3 with 8 levels, with glibc
+// (tests/test_math_host.py) and with the device library (tests/test_gpu_math.py).
+PLF_MATH int plf_predict_level(float ratio, float log_scale, int nlevels)
+{
+    int lvl = (int)ceilf((float)log((double)ratio) / log_scale);
+    if (lvl < 0) lvl = 0;
+    else if (lvl >= nlevels) lvl = nlevels - 1;
+    return lvl;
+}
+
+// LSD's log_gamma: Windschitl above 15, Lanczos below (OpenCV 3.3 lsd.cpp log_gamma_windschitl / log_gamma_lanczos)
+PLF_MATH double log_gamma_d(double x)
+{
+    if (x > 15.0) return 0.918938533204673 + (x - 0.5) * log(x) - x + 0.5 * x * log(x * sinh(1 / x) + 1 / (810.0 * pow(x, 6.0)));
+    const double q[7] = {75122.6331530, 80916.6278952, 36308.2951477, 8687.24529705, 1168.92649479, 83.8676043424, 2.50662827511};
+    double a = (x + 0.5) * log(x + 5.5) - (x + 5.5);
+    double b = 0;
+    for (int n = 0; n < 7; ++n) {
+        a -= log(x + (double)n);
+        b += q[n] * pow(x, (double)n);
+    }
+    return a + log(b);
+}
+
+// ---- NFA (OpenCV 3.3 lsd.cpp nfa()), restructured without changing an operation of the reference's chain
+
+PLF_MATH bool double_equal_d(double a, double b)
+{
+    if (a == b) return true;
+    const double abs_diff = fabs(a - b), aa = fabs(a), bb = fabs(b);
+    double abs_max = (aa > bb) ? aa : bb;
+    if (abs_max < 2.2250738585072014e-308) abs_max = 2.2250738585072014e-308;
+    return (abs_diff / abs_max) <= (100.0 * 2.2204460492503131e-16);
+}
+
+// log_gamma(i) for integer i: the table (i in [0, LGAM_N), filled on the host: lsd_geom.h) or the direct evaluation above it
+#ifndef LGAM_N
+#define LGAM_N 65536
+#endif
+PLF_MATH double log_gamma_int(const double *__restrict__ tab, int i)
+{
+    return (i > 0 && i < LGAM_N) ? tab[i] : log_gamma_d((double)i);
+}
+
+// The rest of the binomial tail cannot change the result any more: the ratio term(i+1) / term(i) = mult_term falls with i, so once it is below 1 every later term is
+// smaller than this one, and a term below bin_tail * 2^-54 is less than half an ulp of bin_tail -- every remaining `bin_tail += term` returns bin_tail unchanged
+// (round to nearest), and whichever way the loop ends it returns -log10(bin_tail) - LOG_NT of this very bin_tail.  (A rectangle of a few thousand pixels with more
+// aligned pixels than n p -- any real edge -- spends nearly all of upstream's n / 2 - k iterations adding such terms.  If bin_tail * 2^-54 underflows the test
+// never fires and the loop runs as upstream's.)
+#define NFA_DEAD_TAIL(mult, term, bin_tail) ((mult) < 1.0 && (term) < (bin_tail) * 0x1p-54)
+
+PLF_MATH_CALL double nfa_d(const double *__restrict__ lgam, double LOG_NT, int n, int k, double p)
+{
+    if (n == 0 || k == 0) return -LOG_NT;
+    if (n == k) return -LOG_NT - (double)n * log10(p);
+    const double p_term = p / (1 - p);
+    const double log1term = log_gamma_int(lgam, n + 1) - log_gamma_int(lgam, k + 1) - log_gamma_int(lgam, n - k + 1) +
+                            (double)k * log(p) + (double)(n - k) * log(1.0 - p);
+    double term = exp(log1term);
+    if (double_equal_d(term, 0)) {
+        if ((double)k > (double)n * p) return -log1term / 2.30258509299404568402 - LOG_NT;
+        return -LOG_NT;
+    }
+    double bin_tail = term;
+    const double tolerance = 0.1;
+    int i = k + 1;
+    // While bin_term >= 1 (i.e. n - i + 1 >= i) the reference's loop has no exit test: such iterations are taken four at a time so that the four
+    // divisions -- independent of the running product -- overlap; the product / sum chain itself is unchanged, operation for operation.
+    while (i + 7 <= n && n - (i + 7) + 1 >= i + 7) {
+        double b[8], m[8];
+#pragma unroll
+        for (int q = 0; q < 8; q++) b[q] = (double)(n - i - q + 1) / (double)(i + q);
+#pragma unroll
+        for (int q = 0; q < 8; q++) m[q] = b[q] * p_term;
+#pragma unroll
+        for (int q = 0; q < 8; q++) { term *= m[q]; bin_tail += term; }
+        i += 8;
+        if (NFA_DEAD_TAIL(m[7], term, bin_tail)) return -log10(bin_tail) - LOG_NT;
+    }
+    while (i + 3 <= n && n - (i + 3) + 1 >= i + 3) {
+        const double b0 = (double)(n - i + 1) / (double)i, b1 = (double)(n - i) / (double)(i + 1), b2 = (double)(n - i - 1) / (double)(i + 2),
+                     b3 = (double)(n - i - 2) / (double)(i + 3);
+        const double m0 = b0 * p_term, m1 = b1 * p_term, m2 = b2 * p_term, m3 = b3 * p_term;
+        term *= m0; bin_tail += term;
+        term *= m1; bin_tail += term;
+        term *= m2; bin_tail += term;
+        term *= m3; bin_tail += term;
+        i += 4;
+        if (NFA_DEAD_TAIL(m3, term, bin_tail)) return -log10(bin_tail) - LOG_NT;
+    }
+    for (; i <= n; ++i) {
+        const double bin_term = (double)(n - i + 1) / (double)i;
+        const double mult_term = bin_term * p_term;
+        term *= mult_term;
+        bin_tail += term;
+        if (bin_term < 1) {
+            const double err = term * ((1 - pow(mult_term, (double)(n - i + 1))) / (1 - mult_term) - 1);
+            if (err < tolerance * fabs(-log10(bin_tail) - LOG_NT) * bin_tail) break;
+        }
+    }
+    return -log10(bin_tail) - LOG_NT;
+}
+
+// nfa_d in pieces for the wave-cooperative kernels (lsd_kernels.hip, nfa_coop): nfa_head stops where nfa_d's exit-free blocks end (it.i .. it.iend: the
+// iterations nfa_coop shares out), nfa_tail finishes a chain from it.iend.  nfa_head, then the exit-free iterations in order, then nfa_tail is nfa_d's chain.
+struct NfaIt { double term, bin_tail, p_term, val; int i, n, iend; bool live; };
+
+PLF_MATH NfaIt nfa_head(const double *__restrict__ lgam, double LOG_NT, int n, int k, double p)
+{
+    NfaIt it;
+    it.live = false; it.term = it.bin_tail = it.p_term = 0.0; it.i = it.iend = 0; it.n = n;
+    if (n == 0 || k == 0) { it.val = -LOG_NT; return it; }
+    if (n == k) { it.val = -LOG_NT - (double)n * log10(p); return it; }
+    it.p_term = p / (1 - p);
+    const double log1term = log_gamma_int(lgam, n + 1) - log_gamma_int(lgam, k + 1) - log_gamma_int(lgam, n - k + 1) +
+                            (double)k * log(p) + (double)(n - k) * log(1.0 - p);
+    const double term = exp(log1term);
+    if (double_equal_d(term, 0)) {
+        it.val = ((double)k > (double)n * p) ? -log1term / 2.30258509299404568402 - LOG_NT : -LOG_NT;
+        return it;
+    }
+    it.live = true; it.term = term; it.bin_tail = term;
+    int i = k + 1;
+    it.i = i;
+    // the iterations nfa_d takes without an exit test (its blocks of 8, then of 4)
+    while (i + 7 <= n && n - (i + 7) + 1 >= i + 7) i += 8;
+    while (i + 3 <= n && n - (i + 3) + 1 >= i + 3) i += 4;
+    it.iend = i;
+    return it;
+}
+
+PLF_MATH double nfa_tail(const NfaIt &it, double LOG_NT)
+{
+    if (!it.live) return it.val;
+    const int n = it.n;
+    double term = it.term, bin_tail = it.bin_tail;
+    const double p_term = it.p_term, tolerance = 0.1;
+    for (int i = it.iend; i <= n; ++i) {
+        const double bin_term = (double)(n - i + 1) / (double)i;
+        const double mult_term = bin_term * p_term;
+        term *= mult_term;
+        bin_tail += term;
+        if (bin_term < 1) {
+            const double err = term * ((1 - pow(mult_term, (double)(n - i + 1))) / (1 - mult_term) - 1);
+            if (err < tolerance * fabs(-log10(bin_tail) - LOG_NT) * bin_tail) break;
+        }
+    }
+    return -log10(bin_tail) - LOG_NT;
+}

@@ -501,3 +501,40 @@ def assign_grid(x, y, bounds):
     cs = np.zeros(64 * 48 + 1, np.int32); ci = np.zeros(max(n, 1), np.int32)
     L.orc_assign_grid(C.byref(F), p(cs), p(ci))
     return cs, ci[:cs[-1]]
+
+
+# ---- device-math parity (oracle/math_oracle.c): op numbers = PLF_MATH_* of include/plf.h
+MATH_CS, MATH_CS0, MATH_RECT_DIR, MATH_LBD_DIR, MATH_PREDICT, MATH_SINCOSF, MATH_KL_ANGLE, MATH_KL_ANGLE_GRID, MATH_LGAMMA, MATH_LGAMMA_TABLE, MATH_NFA_TABLE, \
+    MATH_NFA = range(12)
+
+
+def math_domain(op):
+    L = lib(); L.orc_math_domain.restype = C.c_int64
+    return int(L.orc_math_domain(C.c_int32(op)))
+
+
+def math_elem_size(op):
+    return int(lib().orc_math_elem_size(C.c_int32(op)))
+
+
+def math_cmp(op, params, first, got, nbad=8):
+    """(mismatches, smallest mismatching indices) of the outputs `got` (a buffer of n elements of op's type, host memory) for inputs first .. first + n - 1"""
+    L = lib(); L.orc_math_cmp.restype = C.c_int64
+    got = np.ascontiguousarray(got)
+    es = math_elem_size(op)
+    assert got.nbytes % es == 0
+    n = got.nbytes // es
+    par = np.asarray(params if params is not None else [0.0, 0.0], np.float64)
+    bad = np.full(nbad, -1, np.int64)
+    r = L.orc_math_cmp(C.c_int32(op), par.ctypes.data_as(C.c_void_p), C.c_int64(first), C.c_int64(n), got.ctypes.data_as(C.c_void_p),
+                       bad.ctypes.data_as(C.c_void_p), C.c_int32(nbad))
+    assert r >= 0, "bad op / range"
+    return int(r), [int(b) for b in bad if b >= 0]
+
+
+def math_ref(op, params, first, out):
+    """the oracle's outputs of op for inputs first .. first + n - 1 into the array `out` (n elements of op's type)"""
+    L = lib()
+    par = np.asarray(params if params is not None else [0.0, 0.0], np.float64)
+    n = out.nbytes // math_elem_size(op)
+    return L.orc_math_ref(C.c_int32(op), par.ctypes.data_as(C.c_void_p), C.c_int64(first), C.c_int64(n), out.ctypes.data_as(C.c_void_p))
