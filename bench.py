@@ -13,9 +13,11 @@ Workloads (--config, numbering = BASELINE.json configs[] counted from 1):
   3            configs[2]: 640x480, 2000 ORB + 200 lines, 8 frames in flight on one GPU
   4            configs[3]: 1280x960, 4000 ORB + 400 lines, batch 64 sharded over 8 GPUs = 8 frames in flight per GPU
 Frames are independent, so ranks shard the job with no collective (rgbd_pl_slam_amd.batch.shard = plf_batch_shard; weak scaling:
-every rank processes its own frames_in_flight).  Prints ONE JSON line on rank 0; at N = 1 the default config also carries the
-secondary figures (config 3 as specified, single-frame and tracking-call latency, frames/s against frames in flight, the same step on natural-image-like frames
-(`natural`) and on windows of REAL photographs (`real_photos`: tests/golden/real), PCIe-inclusive rate through the product's batch driver, CPU baseline).
+every rank processes its own frames_in_flight).  Prints ONE JSON line on rank 0.  A plain run does only what the headline needs: it sets up, warms up, times
+the steps, dumps (--dump-outputs) and prints.  With --full, at N = 1 the default config also carries the secondary figures, each timed in runs of its own (the
+headline step on 32 distinct frames, config 3 as specified, single-frame and tracking-call latency, frames/s against frames in flight, the same step on
+natural-image-like frames (`natural`) and on windows of REAL photographs (`real_photos`: tests/golden/real), PCIe-inclusive rate through the product's batch
+driver, CPU baseline).
 --dump-outputs DIR writes what the last timed step of the headline computed (a fixed seeded sample of its frames) as DIR/<name>.npy: the inputs are seeded, so
 two builds run with the same arguments can be compared output for output.
 """
@@ -656,8 +658,10 @@ def main():
     ap.add_argument("--config", type=int, default=2, choices=sorted(CONFIGS), help="BASELINE.json configs[] entry, counted from 1 (2 = the headline metric)")
     ap.add_argument("--batch", type=int, default=0, help="frames in flight per GPU and step (0: the config's own value)")
     ap.add_argument("--distinct", type=int, default=1024, help="independently seeded frames per GPU, tiled to the batch (the extra key tiled32 repeats the run with 32)")
-    ap.add_argument("--cpu-seconds", type=float, default=24.0, help="target duration of the CPU baseline sample (0: skip)")
-    ap.add_argument("--no-extras", action="store_true", help="skip the secondary figures (config 3 as specified, latency, PCIe-inclusive rate)")
+    ap.add_argument("--full", action="store_true", help="also measure the secondary figures after the headline (tiled32, fps_vs_in_flight, config 3 as specified, "
+                    "latency, PCIe-inclusive rate, natural and real-photograph frames, CPU baseline); off: the headline alone")
+    ap.add_argument("--cpu-seconds", type=float, default=24.0, help="with --full: target duration of the CPU baseline sample (0: skip)")
+    ap.add_argument("--no-extras", action="store_true", help="with --full: skip the secondary figures on the GPU (config 3 as specified, latency, PCIe-inclusive rate)")
     ap.add_argument("--line-handles", type=int, default=1, help="line extractor handles used alternately (1 or 2)")
     ap.add_argument("--no-front-wait", action="store_true", help="diagnostic: let ORB start together with the line front stages")
     ap.add_argument("--no-defer-match", action="store_true", help="diagnostic: enqueue the matchers of step k in step k (default: behind the line front stages of "
@@ -704,11 +708,13 @@ def main():
     if rank == 0:
         if args.dump_outputs:
             out["dump_outputs"] = dump_outputs(pipe, args.dump_outputs)
-        if world > 1:
+        if world > 1 and args.full:
             out["extras"] = "skipped: tiled32 / fps_vs_in_flight / config3_as_specified / single_frame_latency / natural / pcie_inclusive / cpu_baseline are N = 1 figures"
+        # (--full: the secondary figures below, each in runs of its own after the headline; a plain run skips them all)
+        extras = args.full and world == 1 and args.config == 2 and not args.no_extras and not args.serial
         out["region_chain_length"] = pipe.chain_stats()
         out["nfa_rectangles_per_frame"] = pipe.rect_stats()
-        if world == 1 and args.config == 2 and not args.no_extras and not args.serial and pipe.ndist > 32:
+        if extras and pipe.ndist > 32:
             # the round-2 workload (32 distinct frames tiled to the batch), same pipeline object, same run: how much input diversity costs
             pipe.load_images(32)
             e32, r32, n32 = timed(pipe, args.steps, 1)
@@ -717,7 +723,7 @@ def main():
                               "what": "the same step on 32 distinct frames tiled to the batch (the round-1/2 workload)"}
         mp, ml = pipe.mp, pipe.ml
         pipe.close(); del pipe
-        if world == 1 and args.config == 2 and not args.no_extras and not args.serial:
+        if extras:
             # where the 5,000 frames/s of BASELINE.json's target is crossed: the same step with fewer frames in flight (the few-frames schedules of the line
             # extractor take over below ~640)
             curve = []
@@ -731,7 +737,7 @@ def main():
                 pn.close(); del pn
             curve.append({"frames_in_flight": B, "value": round(fps, 1), "ms_per_step": round(1e3 * elapsed / args.steps, 3)})
             out["fps_vs_in_flight"] = {"unit": "frames/s", "points": curve, "what": "the default step (config 2 workload) at fewer frames in flight, same run"}
-        if world == 1 and args.config == 2 and not args.no_extras and not args.serial:
+        if extras:
             # secondary figures, driver-timed in the same run
             p3 = Pipeline(*CONFIGS[3][:5], local_rank, 20_000)
             e3, r3, n3 = timed(p3, 30, 5)
@@ -745,7 +751,7 @@ def main():
                                             "config2_natural": tracking_call_latency(local_rank, 2, family="natural")}
             out["pcie_inclusive"] = pcie_inclusive(local_rank, W, H, NFEAT, NLINES, 16384, 4096, mp, ml)
             out["pcie_inclusive"].pop("elapsed_max", None)
-        if world == 1 and args.config == 2 and not args.no_extras and not args.serial:
+        if extras:
             # natural-image-like frames (synth.natural_frame) through the same step: large batch, 8 in flight, one frame
             nat = {"what": "the default step on natural-image-like frames (1/f texture + lens-blurred scene + shot / read noise: synth.natural_frame) instead of "
                            "the hard-edged polygon scenes; same workload, same run"}
@@ -782,7 +788,7 @@ def main():
             if args.cpu_seconds > 0:
                 rp["cpu_port_single_thread"] = cpu_baseline(min(8.0, float(args.cpu_seconds)), 1, W, H, NFEAT, NLINES, family="photo", single_only=True)
             out["real_photos"] = rp
-        if world == 1 and args.cpu_seconds > 0:
+        if args.full and world == 1 and args.cpu_seconds > 0:
             cores = len(os.sched_getaffinity(0)) if hasattr(os, "sched_getaffinity") else (os.cpu_count() or 1)
             out["cpu_baseline"] = cpu_baseline(float(args.cpu_seconds), cores, W, H, NFEAT, NLINES)
         print(json.dumps(out))

@@ -15,7 +15,7 @@ bash tools/kernel_resources.sh > $O/r04_kernel_resources.txt 2>&1
 ( python tools/spec_redo.py 1 24; python tools/spec_redo.py 8 12 ) > $O/r04_spec_redo.txt 2>&1
 ( python tools/sweep_nfa_few.py 1; python tools/sweep_nfa_few.py 8 ) > $O/r04_nfa_few.txt 2>&1
 timeout 1200 python tools/soak_large.py 9000 3000 > $O/r04_soak.txt 2>&1
-timeout 1500 python bench.py > $O/r04_bench_default.json 2> $O/r04_bench_default.err
+timeout 1500 python bench.py --full > $O/r04_bench_default.json 2> $O/r04_bench_default.err
 python - <<'PY'
 import json
 d=json.loads(open("gpurun_out/r04_bench_default.json").read().strip().splitlines()[-1])

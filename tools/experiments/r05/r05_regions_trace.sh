@@ -1,7 +1,8 @@
 #!/bin/bash
 # every launch of k_lsd_regions2 of a full bench.py run (all extras), in order: is there a slow mode?
+ROOT=$(cd "$(dirname "$0")/../../.." && pwd)
 cd /tmp && export TMPDIR=/tmp; rm -rf /tmp/rt
-rocprofv3 --kernel-trace --output-format csv -d /tmp/rt -- python $GRAFT_REPO_ROOT/bench.py --cpu-seconds 0 > /tmp/rt.json 2>/dev/null
+rocprofv3 --kernel-trace --output-format csv -d /tmp/rt -- python "$ROOT/bench.py" --full --cpu-seconds 0 > /tmp/rt.json 2>/dev/null
 python3 - <<'PY'
 import csv, glob, json
 fn = glob.glob('/tmp/rt/**/*kernel_trace.csv', recursive=True)[0]

@@ -23,7 +23,7 @@ timeout 300 python tools/soak_match.py 90 9000 >> $O/r05_soak.txt 2>&1
 bash tools/r05_regions_trace.sh > $O/r05_regions_trace.txt 2>&1
 ( bash tools/lsd_timing.sh && python tools/lsd_timing2.py polygons 0 && python tools/lsd_timing2.py natural 0 ) 2>&1 | grep -v amdgpu.ids > $O/r05_timing.txt
 timeout 1500 python tools/baseline_table.py r05 > $O/r05_baseline_table.log 2>&1
-timeout 1500 python bench.py > $O/r05_bench_default.json 2> $O/r05_bench_default.err
+timeout 1500 python bench.py --full > $O/r05_bench_default.json 2> $O/r05_bench_default.err
 python - <<'PY'
 import json
 d=json.loads(open("gpurun_out/r05_bench_default.json").read().strip().splitlines()[-1])

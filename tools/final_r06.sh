@@ -31,7 +31,7 @@ timeout 300 python tools/soak_match.py 90 11000 >> profiles/r06_soak.txt 2>&1
 timeout 1500 python tools/baseline_table.py r06 > $O/r06_baseline_table.log 2>&1
 cp $O/r06_baseline_table.json profiles/r06_baseline_table.json 2>/dev/null
 # the full default bench (with extras and the CPU baseline) and the GPU test suite on the final code
-timeout 1500 python bench.py > profiles/r06_bench_default.json 2> $O/r06_bench_default.err
+timeout 1500 python bench.py --full > profiles/r06_bench_default.json 2> $O/r06_bench_default.err
 timeout 2400 python -m pytest tests -q -m gpu 2>&1 | tail -4 > profiles/r06_gputests.txt
 mkdir -p $O/profiles_r06; cp profiles/r06_* $O/profiles_r06/
 python - <<'PY'

@@ -8,7 +8,7 @@ timeout 1500 python tools/baseline_table.py r06 > $O/r06_baseline_table.log 2>&1
 cp $O/r06_baseline_table.json profiles/r06_baseline_table.json 2>/dev/null
 bash tools/latency_profile.sh r06 > /dev/null 2>&1
 for f in $O/r06_latency_*; do cp $f profiles/ 2>/dev/null; done
-timeout 1800 python bench.py > profiles/r06_bench_default.json 2> $O/r06_bench_default.err
+timeout 1800 python bench.py --full > profiles/r06_bench_default.json 2> $O/r06_bench_default.err
 timeout 2400 python -m pytest tests -q -m gpu 2>&1 | tail -4 > profiles/r06_gputests.txt
 mkdir -p $O/profiles_r06; cp profiles/r06_* $O/profiles_r06/
 python - <<'PY'
