@@ -668,6 +668,65 @@ int plf_fill(void *dst_device, int32_t byte_value, size_t bytes, void *stream);
 int plf_host_alloc(size_t bytes, void **out);
 void plf_host_free(void *p);
 
+/* ------------------------------------------------------------------------------------------------
+ * DBoW2 vocabulary -- replaces ORBVocabulary::transform / score (Thirdparty/DBoW2/DBoW2/TemplatedVocabulary.h:1151-1283,
+ * BowVector.cpp, FeatureVector.cpp, ScoringObject.cpp), i.e. Frame::ComputeBoW (include/Frame.h:80) and
+ * KeyFrame::ComputeBoW (include/KeyFrame.h:77): the step between the extractor and the SearchByBoW matchers above.
+ * ---------------------------------------------------------------------------------------------- */
+enum { PLF_BOW_TF_IDF = 0, PLF_BOW_TF = 1, PLF_BOW_IDF = 2, PLF_BOW_BINARY = 3 };                       /* DBoW2::WeightingType (BowVector.h) */
+enum { PLF_BOW_L1_NORM = 0, PLF_BOW_L2_NORM = 1, PLF_BOW_CHI_SQUARE = 2, PLF_BOW_KL = 3, PLF_BOW_BHATTACHARYYA = 4,
+       PLF_BOW_DOT_PRODUCT = 5 };                                                                         /* DBoW2::ScoringType */
+enum { PLF_BOW_MAX_CAPACITY = 8192 };   /* largest `capacity` of plf_bow_transform_batch: what the per-frame sort holds in LDS */
+
+/* A vocabulary tree in HOST memory.  Node 0 is the root (its descriptor, weight and is_leaf entry are unused); node ids are the
+ * reference's NodeIds (line numbers of a text file, starting at 1); word ids count the leaves in node order. */
+typedef struct {
+    int32_t k, L, scoring, weighting;   /* the header of a text file: branching factor, depth levels, PLF_BOW_* enums */
+    int32_t n_nodes;                    /* root included */
+    int32_t *parent;                    /* n_nodes */
+    uint8_t *desc;                      /* n_nodes x 32 */
+    double *weight;                     /* n_nodes (the word weight of a leaf) */
+    uint8_t *is_leaf;                   /* n_nodes */
+} plf_vocab_desc;
+
+/* bool TemplatedVocabulary::loadFromTextFile(const std::string&)  TemplatedVocabulary.h:1362-1448 -- host only, no device.  PLF_E_EMPTY: the file
+ * cannot be read; PLF_E_BADARG: the header fails the reference's range check (:1383) or a node line is malformed.  Blank lines are skipped (the
+ * reference turns a trailing one into a child of the root with an indeterminate descriptor).  The arrays are released by plf_vocab_desc_free. */
+int plf_vocab_parse_text(const char *path, plf_vocab_desc *out);
+void plf_vocab_desc_free(plf_vocab_desc *d);
+
+typedef struct plf_vocab plf_vocab;
+typedef struct { int32_t k, L, scoring, weighting, n_nodes, n_words, min_leaf_depth; } plf_vocab_info_t;
+
+/* Validates the tree on the host (parents precede children, every inner node has 1 .. 32 children, leaves have none, no leaf deeper than L:
+ * PLF_E_BADARG otherwise), then uploads it repacked in child order.  PLF_E_HIP without a device. */
+int plf_vocab_create(const plf_vocab_desc *desc, int32_t device, plf_vocab **out);
+int plf_vocab_load_text(const char *path, int32_t device, plf_vocab **out);   /* = plf_vocab_parse_text + plf_vocab_create */
+void plf_vocab_destroy(plf_vocab *v);
+int plf_vocab_info(const plf_vocab *v, plf_vocab_info_t *out);
+
+/* void TemplatedVocabulary::transform(const std::vector<TDescriptor>&, BowVector&, FeatureVector&, int levelsup)  TemplatedVocabulary.h:1151-1218
+ * for n_frames independent frames.  Frame f reads desc + f * capacity * 32 and n_desc[f] (the layout plf_orb_extract_batch writes; both in in_mem)
+ * and writes, in out_mem: the BowVector as word_id / word_val at f * capacity (ascending word id; n_words[f] entries) and the FeatureVector
+ * as node_id at f * capacity (ascending; n_nodes[f] entries), node_start at f * (capacity + 1) (n_nodes[f] + 1 CSR starts) and feat at
+ * f * capacity (feature indices, ascending inside a node) -- the arrays plf_bow_view / plf_tri_view read.  Values are bit-equal to the
+ * reference's doubles (sequential += per word, norm summed in ascending word id).  capacity <= PLF_BOW_MAX_CAPACITY.
+ * A levelsup for which a leaf of the tree lies above level L - levelsup (the reference leaves its NodeId uninitialised there) is PLF_E_BADARG. */
+int plf_bow_transform_batch(plf_vocab *v, const uint8_t *desc, const int32_t *n_desc, int32_t n_frames, int32_t capacity, int32_t levelsup,
+                            int32_t in_mem, int32_t out_mem, uint32_t *word_id, double *word_val, int32_t *n_words, uint32_t *node_id,
+                            int32_t *node_start, int32_t *feat, int32_t *n_nodes, void *stream);
+/* One frame of n descriptors (capacity = n, n_desc passed by value).  A convenience: because the count has to be staged in device memory,
+ * this form waits for its work even with device memory on both sides; a pipeline uses plf_bow_transform_batch with n_frames = 1. */
+int plf_bow_transform(plf_vocab *v, const uint8_t *desc, int32_t n, int32_t levelsup, int32_t in_mem, int32_t out_mem, uint32_t *word_id,
+                      double *word_val, int32_t *n_words, uint32_t *node_id, int32_t *node_start, int32_t *feat, int32_t *n_nodes, void *stream);
+
+/* double TemplatedVocabulary::score(const BowVector&, const BowVector&)  TemplatedVocabulary.h:1223 (ScoringObject.cpp:23-68 L1, :73-120 L2,
+ * :271-311 dot product) of one query vector against M stored vectors in CSR form (db_start: M + 1 entries) -- the loop body of
+ * KeyFrameDatabase::DetectRelocalizationCandidates (include/KeyFrameDatabase.h:58).  Every vector in ascending word id; all pointers in `mem`.
+ * PLF_E_BADARG for a vocabulary whose scoring type is CHI_SQUARE, KL or BHATTACHARYYA. */
+int plf_bow_score(plf_vocab *v, const uint32_t *q_word_id, const double *q_val, int32_t q_n, const uint32_t *db_word_id, const double *db_val,
+                  const int32_t *db_start, int32_t M, double *out, int32_t mem, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -450,6 +450,58 @@ private:
     bool has_map_ = false;
 };
 
+// ORB_SLAM2::ORBVocabulary = DBoW2::TemplatedVocabulary<FORB::TDescriptor, FORB> (include/ORBVocabulary.h, Thirdparty/DBoW2/DBoW2/TemplatedVocabulary.h):
+// loadFromTextFile, transform (Frame::ComputeBoW include/Frame.h:80, KeyFrame::ComputeBoW include/KeyFrame.h:77) and score on the GPU.
+struct BowFlat {   // one frame's BowVector and FeatureVector as flat arrays (the layout plf_bow_view / plf_tri_view read)
+    std::vector<uint32_t> word_id; std::vector<double> word_val;           // ascending word id
+    std::vector<uint32_t> node_id; std::vector<int32_t> node_start, feat;  // ascending node id, CSR starts (nodes + 1), feature indices
+};
+class ORBVocabulary {
+public:
+    explicit ORBVocabulary(int device = 0) : device_(device) {}
+    ~ORBVocabulary() { plf_vocab_destroy(v_); }
+    ORBVocabulary(const ORBVocabulary &) = delete;
+    ORBVocabulary &operator=(const ORBVocabulary &) = delete;
+    // bool loadFromTextFile(const std::string &filename)  TemplatedVocabulary.h:1362 -- false for an unreadable or malformed file, as the reference;
+    // a missing GPU is not a property of the file and throws.
+    bool loadFromTextFile(const std::string &filename)
+    {
+        plf_vocab_destroy(v_); v_ = nullptr;
+        const int st = plf_vocab_load_text(filename.c_str(), device_, &v_);
+        if (st == PLF_E_BADARG || st == PLF_E_EMPTY) return false;
+        check(st, "plf_vocab_load_text");
+        return true;
+    }
+    void create(const plf_vocab_desc &d) { plf_vocab_destroy(v_); v_ = nullptr; check(plf_vocab_create(&d, device_, &v_), "plf_vocab_create"); }
+    bool empty() const { return v_ == nullptr; }
+    plf_vocab_info_t info() const { plf_vocab_info_t i{}; check(plf_vocab_info(v_, &i), "plf_vocab_info"); return i; }
+    unsigned size() const { return empty() ? 0u : (unsigned)info().n_words; }
+    plf_vocab *handle() const { return v_; }
+    // transform(features, v, fv, levelsup)  TemplatedVocabulary.h:1151 -- desc: n x 32 bytes in HOST memory; flat vectors out
+    void transform(const uint8_t *desc, int n, BowFlat &out, int levelsup) const
+    {
+        out = BowFlat();
+        if (empty() || n <= 0) return;   // :1158
+        out.word_id.resize(n); out.word_val.resize(n); out.node_id.resize(n); out.node_start.resize((size_t)n + 1); out.feat.resize(n);
+        int32_t nw = 0, nn = 0;
+        check(plf_bow_transform(v_, desc, n, levelsup, PLF_MEM_HOST, PLF_MEM_HOST, out.word_id.data(), out.word_val.data(), &nw, out.node_id.data(),
+                                out.node_start.data(), out.feat.data(), &nn, nullptr), "plf_bow_transform");
+        out.word_id.resize(nw); out.word_val.resize(nw); out.node_id.resize(nn); out.node_start.resize((size_t)nn + 1);
+        out.feat.resize(out.node_start[nn]);
+    }
+    // double score(const BowVector &v1, const BowVector &v2)  TemplatedVocabulary.h:1223 -- flat vectors, ascending word id
+    double score(const std::vector<uint32_t> &id1, const std::vector<double> &val1, const std::vector<uint32_t> &id2, const std::vector<double> &val2) const
+    {
+        const int32_t start[2] = {0, (int32_t)id2.size()};
+        double out = 0.0;
+        check(plf_bow_score(v_, id1.data(), val1.data(), (int32_t)id1.size(), id2.data(), val2.data(), start, 1, &out, PLF_MEM_HOST, nullptr), "plf_bow_score");
+        return out;
+    }
+protected:
+    plf_vocab *v_ = nullptr;
+    int device_;
+};
+
 }  // namespace plf
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -755,6 +807,38 @@ private:
     float mfNNratio;
     bool mbCheckOrientation;
     int device_;
+};
+// include/ORBVocabulary.h: ORBVocabulary::transform / score with the reference's signatures.  BowVectorT = DBoW2::BowVector (a std::map<WordId, WordValue>),
+// FeatureVectorT = DBoW2::FeatureVector (a std::map<NodeId, std::vector<unsigned int>>): templates, so that this header needs no DBoW2 header.
+class ORBVocabulary : public plf::ORBVocabulary {
+public:
+    using plf::ORBVocabulary::ORBVocabulary;
+    using plf::ORBVocabulary::transform;
+    using plf::ORBVocabulary::score;
+    // void transform(const std::vector<TDescriptor> &features, BowVector &v, FeatureVector &fv, int levelsup) const   TemplatedVocabulary.h:1151
+    template <class BowVectorT, class FeatureVectorT>
+    void transform(const std::vector<cv::Mat> &features, BowVectorT &v, FeatureVectorT &fv, int levelsup) const
+    {
+        v.clear(); fv.clear();
+        std::vector<uint8_t> d(features.size() * 32);
+        for (size_t i = 0; i < features.size(); i++) memcpy(&d[i * 32], features[i].data, 32);   // FORB::TDescriptor: 1 x 32 CV_8U
+        plf::BowFlat f;
+        plf::ORBVocabulary::transform(d.data(), (int)features.size(), f, levelsup);
+        for (size_t i = 0; i < f.word_id.size(); i++) v.insert(v.end(), typename BowVectorT::value_type(f.word_id[i], f.word_val[i]));
+        for (size_t j = 0; j < f.node_id.size(); j++) {
+            auto &dst = fv[f.node_id[j]];
+            dst.assign(f.feat.begin() + f.node_start[j], f.feat.begin() + f.node_start[j + 1]);
+        }
+    }
+    // double score(const BowVector &a, const BowVector &b) const   TemplatedVocabulary.h:1223
+    template <class BowVectorT>
+    double score(const BowVectorT &a, const BowVectorT &b) const
+    {
+        std::vector<uint32_t> ia, ib; std::vector<double> va, vb;
+        for (const auto &e : a) { ia.push_back(e.first); va.push_back(e.second); }
+        for (const auto &e : b) { ib.push_back(e.first); vb.push_back(e.second); }
+        return plf::ORBVocabulary::score(ia, va, ib, vb);
+    }
 };
 }  // namespace ORB_SLAM2_PLF
 #endif

@@ -6,3 +6,4 @@ from .orb import ORBextractor  # noqa: F401
 from .lines import LineSegment  # noqa: F401
 from .matcher import Matcher, DescriptorDistance  # noqa: F401
 from . import frame  # noqa: F401
+from .bow import Vocabulary  # noqa: F401

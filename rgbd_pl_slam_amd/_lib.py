@@ -140,3 +140,36 @@ def vp(a):
     if hasattr(a, "data_ptr"):
         return C.c_void_p(a.data_ptr())
     return a.ctypes.data_as(C.c_void_p)
+
+
+# ---- DBoW2 vocabulary (include/plf.h, "DBoW2 vocabulary")
+BOW_TF_IDF, BOW_TF, BOW_IDF, BOW_BINARY = 0, 1, 2, 3
+BOW_L1_NORM, BOW_L2_NORM, BOW_CHI_SQUARE, BOW_KL, BOW_BHATTACHARYYA, BOW_DOT_PRODUCT = 0, 1, 2, 3, 4, 5
+BOW_MAX_CAPACITY = 8192
+
+
+class VocabDesc(C.Structure):
+    _fields_ = [("k", C.c_int32), ("L", C.c_int32), ("scoring", C.c_int32), ("weighting", C.c_int32), ("n_nodes", C.c_int32),
+                ("parent", C.c_void_p), ("desc", C.c_void_p), ("weight", C.c_void_p), ("is_leaf", C.c_void_p)]
+
+
+class VocabInfo(C.Structure):
+    _fields_ = [("k", C.c_int32), ("L", C.c_int32), ("scoring", C.c_int32), ("weighting", C.c_int32), ("n_nodes", C.c_int32),
+                ("n_words", C.c_int32), ("min_leaf_depth", C.c_int32)]
+
+
+def bow_prototypes(l):
+    """argument types of the vocabulary entry points (pointers are 64-bit: ctypes' default int would cut them)"""
+    P, I = C.c_void_p, C.c_int32
+    l.plf_vocab_parse_text.argtypes = [C.c_char_p, C.POINTER(VocabDesc)]
+    l.plf_vocab_desc_free.argtypes = [C.POINTER(VocabDesc)]
+    l.plf_vocab_desc_free.restype = None
+    l.plf_vocab_create.argtypes = [C.POINTER(VocabDesc), I, C.POINTER(P)]
+    l.plf_vocab_load_text.argtypes = [C.c_char_p, I, C.POINTER(P)]
+    l.plf_vocab_destroy.argtypes = [P]
+    l.plf_vocab_destroy.restype = None
+    l.plf_vocab_info.argtypes = [P, C.POINTER(VocabInfo)]
+    l.plf_bow_transform_batch.argtypes = [P, P, P, I, I, I, I, I, P, P, P, P, P, P, P, P]
+    l.plf_bow_transform.argtypes = [P, P, I, I, I, I, P, P, P, P, P, P, P, P]
+    l.plf_bow_score.argtypes = [P, P, P, I, P, P, P, I, P, I, P]
+    return l
