@@ -727,6 +727,42 @@ int plf_bow_transform(plf_vocab *v, const uint8_t *desc, int32_t n, int32_t leve
 int plf_bow_score(plf_vocab *v, const uint32_t *q_word_id, const double *q_val, int32_t q_n, const uint32_t *db_word_id, const double *db_val,
                   const int32_t *db_start, int32_t M, double *out, int32_t mem, void *stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * Map -- void MapPoint::ComputeDistinctiveDescriptors() include/MapPoint.h:75 (so@0x94460) and void MapLine::ComputeDistinctiveDescriptors()
+ * include/MapLine.h:93: the step LocalMapping runs on every point / line that Fuse or triangulation touched, between the calls that change
+ * observation sets and the matchers that read the representative descriptor (the `desc` arrays of plf_mappoint_view, plf_points3d_view,
+ * plf_mapline_view).  The rule, from the binary: the descriptors of the observations whose keyframe is not isBad() (so@0x94706), in the
+ * iteration order of mObservations; all pairwise ORBmatcher::DescriptorDistance (so@0x94add; the diagonal is 0); per row the median
+ * sorted[(int)(0.5 * (N - 1))] (so@0x94dd0, 0x94ec7, 0x94edd); the row with the smallest median, the earliest on ties (strict < from INT_MAX,
+ * so@0x94b4e); without a valid observation mDescriptor is left alone.  The MapLine routine has no body anywhere in the reference: it is
+ * taken as the same rule over mLdesc with LSDmatcher::DescriptorDistance (the same 256-bit Hamming distance) -- PARITY UNPINNED.
+ * Stateless; every pointer is DEVICE memory; asynchronous on `stream` (NULL = the null stream).
+ * ---------------------------------------------------------------------------------------------- */
+typedef struct {
+    int32_t n_points;
+    const int32_t *obs_start;        /* n_points + 1, CSR; inside a point: the caller's iteration order of mObservations (ties resolve by it) */
+    /* the descriptors, in exactly one of two forms -- packed: */
+    const uint8_t *obs_desc;         /* total x 32, 16-byte aligned */
+    /* -- or indirect: observation o is row obs_idx[o] of kf_desc[obs_kf[o]].  kf_desc: a device table of n_kf device pointers to each keyframe's
+     * mDescriptors (mLdesc for lines), 16-byte aligned; the extractor's own output buffers are valid entries, nothing is flattened per call.  An
+     * obs_kf outside [0, n_kf) is skipped like an invalid observation. */
+    const int32_t *obs_kf, *obs_idx;
+    const uint8_t *const *kf_desc;
+    int32_t n_kf;
+    const uint8_t *obs_valid;        /* optional (NULL = all): 0 = the keyframe isBad(), the observation is skipped and its descriptor not read */
+    const int32_t *point_id;         /* optional (NULL = identity): the row of map_desc point i writes -- recompute only the touched points.  Entries
+                                      * must be DISTINCT (two points writing one row race); an id outside [0, map_rows) writes no row */
+} plf_map_obs_view;
+
+/* map_desc (map_rows x 32, 16-byte aligned, written IN PLACE: the very array the *_view.desc fields read): the chosen descriptor of every point with a
+ * valid observation; rows not named, and the row of a point without one, are untouched.  best_obs (n_points): position of the chosen observation
+ * within the point's own CSR range, -1 without a valid observation; best_median (n_points): its median distance, -1 likewise.  Filler between
+ * and beyond the CSR ranges is never read.  No upper limit on observations per point: up to 16 share a wave four points at a time, up to 256 take a
+ * wave, more take a workgroup (descriptors in LDS up to 4096, from global memory beyond).  PLF_E_BADARG before any device work: NULL arrays,
+ * n_points < 0, both or neither descriptor form, a misaligned map_desc / obs_desc. */
+int plf_map_distinctive_descriptors(const plf_map_obs_view *obs, uint8_t *map_desc, int32_t map_rows, int32_t *best_obs, int32_t *best_median,
+                                    int32_t device, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

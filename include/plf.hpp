@@ -350,6 +350,27 @@ struct Frame {
     }
 };
 
+// void MapPoint::ComputeDistinctiveDescriptors() include/MapPoint.h:75 (so@0x94460) for a batch of map points: device arrays in, the representative
+// descriptors written in place into the array the matchers' views read (plf_map_distinctive_descriptors; obs in CSR form, see plf_map_obs_view)
+struct MapPoint {
+    static void ComputeDistinctiveDescriptors(const plf_map_obs_view &mObservations_dev, uint8_t *mDescriptor_dev, int map_rows, int32_t *best_obs_dev,
+                                              int32_t *best_median_dev, int device = 0, void *stream = nullptr)
+    {
+        check(plf_map_distinctive_descriptors(&mObservations_dev, mDescriptor_dev, map_rows, best_obs_dev, best_median_dev, device, stream),
+              "MapPoint::ComputeDistinctiveDescriptors");
+    }
+};
+// void MapLine::ComputeDistinctiveDescriptors() include/MapLine.h:93 -- declared without a body in the reference: the MapPoint rule over the keyframes'
+// line descriptors with LSDmatcher::DescriptorDistance (PARITY UNPINNED); writes mLDescriptor
+struct MapLine {
+    static void ComputeDistinctiveDescriptors(const plf_map_obs_view &mObservations_dev, uint8_t *mLDescriptor_dev, int map_rows, int32_t *best_obs_dev,
+                                              int32_t *best_median_dev, int device = 0, void *stream = nullptr)
+    {
+        check(plf_map_distinctive_descriptors(&mObservations_dev, mLDescriptor_dev, map_rows, best_obs_dev, best_median_dev, device, stream),
+              "MapLine::ComputeDistinctiveDescriptors");
+    }
+};
+
 // ------------------------------------------------------------------ batches of independent host frames on all GPUs of the node
 // The caller loop of the reference (Examples/RGB-D/rgbd_tum.cc:84-128 -> System::TrackRGBD -> Tracking::GrabImageRGBD -> RGB-D Frame::Frame,
 // include/Frame.h:60) for N frames at once: plf_batch_* shards the frames over the GPUs in contiguous blocks (no collective), stages them through
@@ -514,6 +535,7 @@ protected:
 #if defined(PLF_WITH_OPENCV) && defined(__has_include)
 #if __has_include(<opencv2/core.hpp>)
 #include <cstring>
+#include <unordered_map>
 #include <utility>
 #include <opencv2/core.hpp>
 #include <opencv2/features2d.hpp>
@@ -840,6 +862,70 @@ public:
         return plf::ORBVocabulary::score(ia, va, ib, vb);
     }
 };
+
+// MapPoint::ComputeDistinctiveDescriptors / MapLine::ComputeDistinctiveDescriptors for a LIST of points of the reference's own types (what LocalMapping
+// runs after Fuse and after CreateNewMapPoints / CreateNewMapLines).  Walks GetObservations() (the std::map's order), KeyFrame::isBad() and the keyframes'
+// descriptor matrices, builds the CSR and calls plf_map_distinctive_descriptors in its indirect form.  EVERY CALL uploads the whole descriptor matrix of
+// every keyframe the listed points are observed from (once per keyframe and call): that is the price of starting from host cv::Mat members, and it is
+// only worth paying for a long list.  A caller whose keyframe descriptors already live on the device uses the C entry point and uploads nothing.
+// mDescriptor / mLDescriptor are protected in the reference: the forwarder inside MapPoint.cc / MapLine.cc assigns desc.row(i).
+struct DistinctiveDescriptors {
+    cv::Mat desc;                               // points x 32 CV_8U: row i = the new mDescriptor of point i (meaningful where best_obs[i] >= 0)
+    std::vector<int32_t> best_obs, best_median; // position in the point's GetObservations() order (bad keyframes counted), -1 = leave mDescriptor alone
+};
+namespace detail {
+template <class PointT, class DescOf> DistinctiveDescriptors distinctive(const std::vector<PointT *> &points, DescOf descOf, int device)
+{
+    DistinctiveDescriptors out;
+    const int P = (int)points.size();
+    out.best_obs.assign(P, -1); out.best_median.assign(P, -1);
+    out.desc.create(P, 32, CV_8U);
+    if (P == 0) return out;
+    memset(out.desc.data, 0, (size_t)P * 32);
+    std::vector<int32_t> start(P + 1, 0), kf, idx;
+    std::vector<uint8_t> valid;
+    std::unordered_map<const void *, int> seen; // keyframe -> its index in order of first appearance
+    std::vector<std::vector<uint8_t>> rows;
+    for (int i = 0; i < P; i++) {
+        if (points[i]) {
+            const auto observations = points[i]->GetObservations();
+            for (const auto &ob : observations) {
+                auto *pKF = ob.first;
+                const auto at = seen.emplace((const void *)pKF, (int)seen.size());
+                if (at.second) rows.push_back(rows32(descOf(pKF)));
+                kf.push_back(at.first->second); idx.push_back((int32_t)ob.second); valid.push_back(!pKF->isBad());
+            }
+        }
+        start[i + 1] = (int32_t)kf.size();
+    }
+    if (kf.empty()) return out;
+    std::vector<plf::DeviceArray<uint8_t>> dkf(seen.size());
+    std::vector<const uint8_t *> table(seen.size());
+    for (size_t k = 0; k < seen.size(); k++) {
+        dkf[k].reset(rows[k].size() + 32, device);
+        if (!rows[k].empty()) dkf[k].upload(rows[k].data(), rows[k].size());
+        table[k] = dkf[k].get();
+    }
+    plf::DeviceArray<int32_t> dstart(start, device), dk(kf, device), di(idx, device), dbo(P, device), dbm(P, device);
+    plf::DeviceArray<uint8_t> dv(valid, device), dmap((size_t)P * 32, device);
+    plf::DeviceArray<const uint8_t *> dtab(table, device);
+    dmap.fill(0);
+    plf_map_obs_view v = {P, dstart.get(), nullptr, dk.get(), di.get(), dtab.get(), (int32_t)seen.size(), dv.get(), nullptr};
+    plf::check(plf_map_distinctive_descriptors(&v, dmap.get(), P, dbo.get(), dbm.get(), device, nullptr), "ComputeDistinctiveDescriptors");
+    const std::vector<uint8_t> d = dmap.download();          // a NULL-stream download waits for the device first
+    memcpy(out.desc.data, d.data(), d.size());
+    out.best_obs = dbo.download(); out.best_median = dbm.download();
+    return out;
+}
+}  // namespace detail
+template <class MapPointT> DistinctiveDescriptors ComputeDistinctiveDescriptors(const std::vector<MapPointT *> &vpMapPoints, int device = 0)
+{
+    return detail::distinctive(vpMapPoints, [](auto *pKF) -> const cv::Mat & { return pKF->mDescriptors; }, device);
+}
+template <class MapLineT> DistinctiveDescriptors ComputeDistinctiveLineDescriptors(const std::vector<MapLineT *> &vpMapLines, int device = 0)
+{
+    return detail::distinctive(vpMapLines, [](auto *pKF) -> const cv::Mat & { return pKF->mLineDescriptors; }, device);
+}
 }  // namespace ORB_SLAM2_PLF
 #endif
 #endif

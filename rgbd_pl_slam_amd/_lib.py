@@ -173,3 +173,15 @@ def bow_prototypes(l):
     l.plf_bow_transform.argtypes = [P, P, I, I, I, I, P, P, P, P, P, P, P, P]
     l.plf_bow_score.argtypes = [P, P, P, I, P, P, P, I, P, I, P]
     return l
+
+
+# ---- map (include/plf.h, "Map")
+class MapObsView(C.Structure):
+    _fields_ = [("n_points", C.c_int32), ("obs_start", C.c_void_p), ("obs_desc", C.c_void_p), ("obs_kf", C.c_void_p), ("obs_idx", C.c_void_p),
+                ("kf_desc", C.c_void_p), ("n_kf", C.c_int32), ("obs_valid", C.c_void_p), ("point_id", C.c_void_p)]
+
+
+def map_prototypes(l):
+    P, I = C.c_void_p, C.c_int32
+    l.plf_map_distinctive_descriptors.argtypes = [C.POINTER(MapObsView), P, I, P, P, I, P]
+    return l
