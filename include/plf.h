@@ -704,6 +704,7 @@ int plf_vocab_create(const plf_vocab_desc *desc, int32_t device, plf_vocab **out
 int plf_vocab_load_text(const char *path, int32_t device, plf_vocab **out);   /* = plf_vocab_parse_text + plf_vocab_create */
 void plf_vocab_destroy(plf_vocab *v);
 int plf_vocab_info(const plf_vocab *v, plf_vocab_info_t *out);
+int plf_vocab_device(const plf_vocab *v);   /* the device the tree lives on; PLF_E_BADARG for NULL */
 
 /* void TemplatedVocabulary::transform(const std::vector<TDescriptor>&, BowVector&, FeatureVector&, int levelsup)  TemplatedVocabulary.h:1151-1218
  * for n_frames independent frames.  Frame f reads desc + f * capacity * 32 and n_desc[f] (the layout plf_orb_extract_batch writes; both in in_mem)
@@ -726,6 +727,84 @@ int plf_bow_transform(plf_vocab *v, const uint8_t *desc, int32_t n, int32_t leve
  * PLF_E_BADARG for a vocabulary whose scoring type is CHI_SQUARE, KL or BHATTACHARYYA. */
 int plf_bow_score(plf_vocab *v, const uint32_t *q_word_id, const double *q_val, int32_t q_n, const uint32_t *db_word_id, const double *db_val,
                   const int32_t *db_start, int32_t M, double *out, int32_t mem, void *stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * Keyframe database -- replaces KeyFrameDatabase (include/KeyFrameDatabase.h:48-58): add so@0x102fe0, erase so@0x102c60, clear so@0x102ed0,
+ * DetectLoopCandidates so@0x103120, DetectRelocalizationCandidates so@0x103980.  The step between plf_bow_transform_batch (which writes the
+ * vectors it stores and queries with) and the SearchByBoW matchers (whose plf_bow_view can point at the vectors it keeps).  The class has no
+ * source in the reference; the rule below is the binary's.
+ *
+ * Relocalisation, query F:
+ *  1. for every word of F->mBowVec ascending, every keyframe of mvInvertedFile[word] in list order (so@0x103a28-0x103ab7): a keyframe met for the
+ *     first time in this query (mnRelocQuery != F->mnId, so@0x103a5b) gets mnRelocWords = 0 and joins lKFsSharingWords; every meeting adds 1.
+ *  2. maxCommonWords = max mnRelocWords; minCommonWords = (int)(maxCommonWords * 0.8f), float multiply then truncation (so@0x103b17-0x103b28,
+ *     constant so@0x1265b0).
+ *  3. in list order, mnRelocWords > minCommonWords (so@0x103b3c): si = (float)score(F->mBowVec, pKFi->mBowVec) (double rounded once, so@0x103b66),
+ *     stored in the keyframe as mRelocScore (so@0x103b6a), appended to lScoreAndMatch.
+ *  4. per entry, the first 10 of GetBestCovisibilityKeyFrames (so@0x103c1c): accScore = bestScore = si; a neighbour counts iff its mnRelocQuery
+ *     is this query (so@0x103c6c) -- it shares a word, nothing else is asked; accScore += mRelocScore (so@0x103c77), and a strictly greater
+ *     mRelocScore makes it the group's keyframe (so@0x103c7d-0x103c97).  bestAccScore = running max from 0 (so@0x103ce1).
+ *  5. minScoreToRetain = 0.75f * bestAccScore (so@0x103d18); in order, accScore > minScoreToRetain contributes the group's keyframe unless it
+ *     is already in the output (so@0x103dc5, set at so@0x103e46).
+ * A neighbour of step 4 that shares a word but failed step 3 contributes the mRelocScore an EARLIER query stored: one float of persistent
+ * state per keyframe, and queries are order dependent.  The KeyFrame constructor (so@0x9d650) initialises mnRelocQuery / mnRelocWords
+ * (so@0x9d6f5, 0x9d6fd) but not mRelocScore at offset 0x64: before the first store the reference reads an indeterminate value.
+ * DEVIATION: this database defines it as 0.0f at add.
+ * Loop, query pKF with minScore: the same skeleton over mnLoopQuery / mnLoopWords / mLoopScore, except that (a) a keyframe of
+ * pKF->GetConnectedKeyFrames() (so@0x10316d) never joins the list and is not stamped (so@0x103255-0x10325f, 0x103750); (b) mLoopScore = si is
+ * stored, then only si >= minScore joins lScoreAndMatch (so@0x103374-0x103386); (c) a neighbour counts iff it is stamped with this query AND
+ * mnLoopWords > minCommonWords (so@0x10347c, 0x103482) -- its score is then this query's own, so loop queries carry no state.
+ * The stamps compare against ids that start at 0, like the stamps themselves: a query with id 0 would find every never-met keyframe
+ * "already met".  Not reproduced -- a query here shares a word with exactly the keyframes its own walk met (the reference never queries id 0).
+ * Order: lists are in add order and erase keeps it, so the first-meeting order of step 1 is ascending (smallest shared word id, add sequence
+ * number); slots are reused freely, the sequence number never is.
+ *
+ * The inverted file is a CSR by word, entries of a word in add order, REBUILT LAZILY: add / erase only mark it stale, the next detect (or
+ * plf_kfdb_info) rebuilds it on its stream (histogram, scan, scatter, per-word ordering) after uploading one rank per slot, for which it
+ * waits.  Detect calls process their queries in chunks of max(1, 2^22 / max_keyframes), so the dense per-chunk scratch (common words, score,
+ * first word, pair list: 16 bytes per query x slot; sort keys: 8 bytes per query x max_keyframes rounded up to a power of two) stays below
+ * 128 MB whatever Q is.  Query and keyframe vectors, covisibility, exclusion lists and all outputs are DEVICE memory; `slots` are HOST
+ * memory, because they are checked before any device work.  Asynchronous on `stream` (NULL = the database's own stream).
+ * ---------------------------------------------------------------------------------------------- */
+typedef struct plf_kfdb plf_kfdb;
+typedef struct { int32_t max_keyframes, capacity, n_keyframes, n_entries, n_best; } plf_kfdb_info_t;
+typedef struct { int32_t n_sharing, max_common_words, n_scored; float best_acc_score; } plf_kfdb_stats;   /* per query; all 0 for an empty result of step 1 */
+
+/* Bound to the vocabulary's device, word count and scoring type; PLF_E_BADARG for CHI_SQUARE / KL / BHATTACHARYYA (as plf_bow_score),
+ * max_keyframes < 1, capacity outside 1 .. PLF_BOW_MAX_CAPACITY.  Slots are 0 .. max_keyframes - 1; a vector holds up to `capacity` words. */
+int plf_kfdb_create(const plf_vocab *vocab, int32_t max_keyframes, int32_t capacity, plf_kfdb **out);
+void plf_kfdb_destroy(plf_kfdb *db);
+int plf_kfdb_info(plf_kfdb *db, plf_kfdb_info_t *out);   /* rebuilds a stale inverted file and waits: n_entries is its size */
+int plf_kfdb_set_n_best(plf_kfdb *db, int32_t n_best);   /* how many entries of a covisibility row a detect call reads; 10 at creation */
+
+/* void KeyFrameDatabase::add(KeyFrame*) for n keyframes, added in index order.  Keyframe f reads word_id / word_val at f * capacity and
+ * n_words[f] -- the layout plf_bow_transform_batch writes, device memory -- and is stored in slots[f] (host memory) with mRelocScore = 0.0f.
+ * PLF_E_BADARG before any device work: capacity > the database's, a slot outside the table, occupied, or named twice. */
+int plf_kfdb_add_batch(plf_kfdb *db, const uint32_t *word_id, const double *word_val, const int32_t *n_words, int32_t n, int32_t capacity,
+                       const int32_t *slots, void *stream);
+/* void KeyFrameDatabase::erase(KeyFrame*) / clear().  A slot that holds no keyframe is ignored, as the reference ignores an absent keyframe. */
+int plf_kfdb_erase_batch(plf_kfdb *db, const int32_t *slots, int32_t n);
+int plf_kfdb_clear(plf_kfdb *db);
+/* The resident vectors: slot s at word_id / word_val + s * capacity, n_words[s] (valid for live slots, once the add that wrote them has run). */
+int plf_kfdb_vectors(plf_kfdb *db, const uint32_t **word_id, const double **word_val, const int32_t **n_words);
+
+/* std::vector<KeyFrame*> DetectRelocalizationCandidates(Frame*) for Q query frames (vectors at q * capacity, q_n_words[q]); identical to Q
+ * single-query calls in index order, the persistent scores included.  covis_start / covis_slot: CSR over slots (max_keyframes + 1 starts) of
+ * each keyframe's mvpOrderedConnectedKeyFrames, of which the first n_best entries are read; an entry that is -1, outside the table or a
+ * slot without a keyframe is skipped (both NULL: no neighbours).  cand[q * max_cand + i]: slots in the reference's output order, -1 from the count on; n_cand[q] the
+ * true count (entries beyond max_cand are not written); stats: optional, Q entries.
+ * PRECONDITION (device data, not checked): every vector, stored or queried, holds distinct ascending word ids below the vocabulary's word
+ * count -- what plf_bow_transform_batch writes.  A word id beyond the vocabulary is ignored by the inverted file but not by the score; a
+ * repeated word id in a stored vector leaves an entry of the inverted file undefined. */
+int plf_kfdb_detect_reloc(plf_kfdb *db, const uint32_t *q_word_id, const double *q_word_val, const int32_t *q_n_words, int32_t Q, int32_t capacity,
+                          const int32_t *covis_start, const int32_t *covis_slot, int32_t max_cand, int32_t *cand, int32_t *n_cand, plf_kfdb_stats *stats,
+                          void *stream);
+/* std::vector<KeyFrame*> DetectLoopCandidates(KeyFrame*, float minScore).  excl_start / excl_slot: CSR over the queries (Q + 1 starts) of each
+ * query's GetConnectedKeyFrames(), any order (both NULL: none); a caller that has already added the query keyframe lists its slot there.
+ * min_score: Q floats.  Stateless. */
+int plf_kfdb_detect_loop(plf_kfdb *db, const uint32_t *q_word_id, const double *q_word_val, const int32_t *q_n_words, int32_t Q, int32_t capacity,
+                         const int32_t *covis_start, const int32_t *covis_slot, const int32_t *excl_start, const int32_t *excl_slot,
+                         const float *min_score, int32_t max_cand, int32_t *cand, int32_t *n_cand, plf_kfdb_stats *stats, void *stream);
 
 /* ------------------------------------------------------------------------------------------------
  * Map -- void MapPoint::ComputeDistinctiveDescriptors() include/MapPoint.h:75 (so@0x94460) and void MapLine::ComputeDistinctiveDescriptors()

@@ -523,6 +523,91 @@ protected:
     int device_;
 };
 
+// ORB_SLAM2::KeyFrameDatabase (include/KeyFrameDatabase.h:48-58) over slots: add / erase / clear, DetectLoopCandidates, DetectRelocalizationCandidates
+// on the GPU (plf_kfdb_*, include/plf.h "Keyframe database").  This form takes one query in HOST vectors and waits for its result; a pipeline that
+// keeps its vectors on the device and queries in batches uses add_device / the C entry points with handle().
+class KeyFrameDatabase {
+public:
+    KeyFrameDatabase(const ORBVocabulary &voc, int max_keyframes, int capacity) : S_(max_keyframes), C_(capacity)
+    {
+        check(plf_kfdb_create(voc.handle(), max_keyframes, capacity, &db_), "plf_kfdb_create");
+        device_ = plf_vocab_device(voc.handle());
+    }
+    ~KeyFrameDatabase() { plf_kfdb_destroy(db_); }
+    KeyFrameDatabase(const KeyFrameDatabase &) = delete;
+    KeyFrameDatabase &operator=(const KeyFrameDatabase &) = delete;
+    plf_kfdb *handle() const { return db_; }
+    plf_kfdb_info_t info() const { plf_kfdb_info_t i{}; check(plf_kfdb_info(db_, &i), "plf_kfdb_info"); return i; }
+    // void add(KeyFrame *pKF): the keyframe's mBowVec as flat ascending vectors, stored in `slot`
+    void add(int slot, const std::vector<uint32_t> &word_id, const std::vector<double> &word_val)
+    {
+        const int32_t n = (int32_t)word_id.size(), s = slot;
+        if (word_val.size() != word_id.size() || n > C_) throw Error(PLF_E_BADARG, "KeyFrameDatabase::add");
+        DeviceArray<uint32_t> di((size_t)C_, device_); DeviceArray<double> dv((size_t)C_, device_); DeviceArray<int32_t> dn(1, device_);
+        if (n > 0) { di.upload(word_id.data(), (size_t)n); dv.upload(word_val.data(), (size_t)n); }
+        dn.upload(&n, 1);
+        add_device(di.get(), dv.get(), dn.get(), 1, C_, &s, nullptr);
+        wait();                                          // the staging arrays go out of scope
+    }
+    // n keyframes straight from plf_bow_transform_batch's device output; only enqueues
+    void add_device(const uint32_t *word_id, const double *word_val, const int32_t *n_words, int n, int capacity, const int32_t *slots, void *stream)
+    {
+        check(plf_kfdb_add_batch(db_, word_id, word_val, n_words, n, capacity, slots, stream), "plf_kfdb_add_batch");
+    }
+    void erase(int slot) { const int32_t s = slot; check(plf_kfdb_erase_batch(db_, &s, 1), "plf_kfdb_erase_batch"); }
+    void clear() { check(plf_kfdb_clear(db_), "plf_kfdb_clear"); }
+    // covis_start / covis_slot: CSR over the slots (max_keyframes + 1 starts) of mvpOrderedConnectedKeyFrames, -1 = a keyframe outside the database;
+    // both empty = no neighbours.  Returns the candidate slots in the reference's order.
+    std::vector<int32_t> DetectRelocalizationCandidates(const std::vector<uint32_t> &word_id, const std::vector<double> &word_val,
+                                                        const std::vector<int32_t> &covis_start, const std::vector<int32_t> &covis_slot,
+                                                        plf_kfdb_stats *stats = nullptr)
+    {
+        return detect(false, word_id, word_val, covis_start, covis_slot, std::vector<int32_t>(), 0.0f, stats);
+    }
+    // connected: the slots of pKF->GetConnectedKeyFrames() (and pKF's own, if it was added), any order
+    std::vector<int32_t> DetectLoopCandidates(const std::vector<uint32_t> &word_id, const std::vector<double> &word_val, float minScore,
+                                              const std::vector<int32_t> &connected, const std::vector<int32_t> &covis_start,
+                                              const std::vector<int32_t> &covis_slot, plf_kfdb_stats *stats = nullptr)
+    {
+        return detect(true, word_id, word_val, covis_start, covis_slot, connected, minScore, stats);
+    }
+private:
+    void wait() { DeviceArray<int32_t> d(1, device_); (void)d.download(); }   // a NULL-stream download waits for the device first
+    std::vector<int32_t> detect(bool loop, const std::vector<uint32_t> &word_id, const std::vector<double> &word_val, const std::vector<int32_t> &covis_start,
+                                const std::vector<int32_t> &covis_slot, const std::vector<int32_t> &connected, float minScore, plf_kfdb_stats *stats)
+    {
+        const int32_t n = (int32_t)word_id.size();
+        if (word_val.size() != word_id.size() || (!covis_start.empty() && covis_start.size() != (size_t)S_ + 1)) throw Error(PLF_E_BADARG, "KeyFrameDatabase::Detect");
+        const int cap = n > 0 ? n : 1;
+        DeviceArray<uint32_t> di((size_t)cap, device_); DeviceArray<double> dv((size_t)cap, device_); DeviceArray<int32_t> dn(1, device_);
+        if (n > 0) { di.upload(word_id.data(), (size_t)n); dv.upload(word_val.data(), (size_t)n); }
+        dn.upload(&n, 1);
+        DeviceArray<int32_t> dcs(covis_start.size() + 1, device_), dci(covis_slot.size() + 1, device_), dcand((size_t)S_, device_), dnc(1, device_), dst(4, device_);
+        if (!covis_start.empty()) dcs.upload(covis_start.data(), covis_start.size());
+        if (!covis_slot.empty()) dci.upload(covis_slot.data(), covis_slot.size());
+        const int32_t *cs = covis_start.empty() ? nullptr : dcs.get(), *ci = covis_start.empty() ? nullptr : dci.get();
+        if (loop) {
+            const int32_t es[2] = {0, (int32_t)connected.size()};
+            DeviceArray<int32_t> des(2, device_), dei(connected.size() + 1, device_);
+            DeviceArray<float> dms(1, device_);
+            des.upload(es, 2); dms.upload(&minScore, 1);
+            if (!connected.empty()) dei.upload(connected.data(), connected.size());
+            check(plf_kfdb_detect_loop(db_, di.get(), dv.get(), dn.get(), 1, cap, cs, ci, des.get(), dei.get(), dms.get(), S_, dcand.get(), dnc.get(),
+                                       (plf_kfdb_stats *)dst.get(), nullptr), "plf_kfdb_detect_loop");
+            wait();
+        } else
+            check(plf_kfdb_detect_reloc(db_, di.get(), dv.get(), dn.get(), 1, cap, cs, ci, S_, dcand.get(), dnc.get(), (plf_kfdb_stats *)dst.get(), nullptr),
+                  "plf_kfdb_detect_reloc");
+        const std::vector<int32_t> nc = dnc.download();  // a NULL-stream download waits for the device first
+        std::vector<int32_t> out = dcand.download();
+        out.resize((size_t)nc[0]);
+        if (stats) { const std::vector<int32_t> st = dst.download(); memcpy(stats, st.data(), sizeof(*stats)); }
+        return out;
+    }
+    plf_kfdb *db_ = nullptr;
+    int S_, C_, device_ = 0;
+};
+
 }  // namespace plf
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -861,6 +946,81 @@ public:
         for (const auto &e : b) { ib.push_back(e.first); vb.push_back(e.second); }
         return plf::ORBVocabulary::score(ia, va, ib, vb);
     }
+};
+
+// include/KeyFrameDatabase.h:48-58 with the reference's signatures over its own KeyFrame / Frame classes (templates, so that this header needs none of
+// the reference's).  Keeps the pointer <-> slot table, stages mBowVec at add and at every query, and reads GetBestCovisibilityKeyFrames(10) of every
+// stored keyframe and pKF->GetConnectedKeyFrames() from the objects at query time (a keyframe outside the database becomes -1).
+// The price of starting from host objects, as with the map adapter below: add() finds a free slot by a linear scan over max_keyframes, and EVERY QUERY
+// rebuilds and uploads the covisibility CSR of all stored keyframes (one GetBestCovisibilityKeyFrames(10) per stored keyframe), stages the query vector,
+// allocates its device arrays and waits for the result.  It exists for signature parity; a caller that keeps its vectors and its covisibility CSR on
+// the device uses plf::KeyFrameDatabase::add_device / the C entry points and uploads nothing per query.
+template <class KeyFrameT, class FrameT> class KeyFrameDatabase {
+public:
+    explicit KeyFrameDatabase(const plf::ORBVocabulary &voc, int max_keyframes = 4096, int capacity = 2048)
+        : db_(voc, max_keyframes, capacity), kf_((size_t)max_keyframes, nullptr) {}
+    void add(KeyFrameT *pKF)
+    {
+        if (slot_.count(pKF)) return;
+        int s = 0;
+        while (s < (int)kf_.size() && kf_[s]) s++;
+        if (s == (int)kf_.size()) throw plf::Error(PLF_E_CAPACITY, "KeyFrameDatabase::add");
+        std::vector<uint32_t> id; std::vector<double> val;
+        flat(pKF->mBowVec, id, val);
+        db_.add(s, id, val);
+        kf_[s] = pKF; slot_[pKF] = s;
+    }
+    void erase(KeyFrameT *pKF)
+    {
+        const auto it = slot_.find(pKF);
+        if (it == slot_.end()) return;
+        db_.erase(it->second);
+        kf_[it->second] = nullptr; slot_.erase(it);
+    }
+    void clear() { db_.clear(); slot_.clear(); std::fill(kf_.begin(), kf_.end(), nullptr); }
+    std::vector<KeyFrameT *> DetectLoopCandidates(KeyFrameT *pKF, float minScore)
+    {
+        std::vector<uint32_t> id; std::vector<double> val;
+        flat(pKF->mBowVec, id, val);
+        std::vector<int32_t> conn, cs, ci;
+        for (KeyFrameT *c : pKF->GetConnectedKeyFrames()) { const auto it = slot_.find(c); if (it != slot_.end()) conn.push_back(it->second); }
+        const auto self = slot_.find(pKF);
+        if (self != slot_.end()) conn.push_back(self->second);   // the reference's walk meets pKF itself only through mnLoopQuery == mnId: never a candidate
+        covis(cs, ci);
+        return pointers(db_.DetectLoopCandidates(id, val, minScore, conn, cs, ci));
+    }
+    std::vector<KeyFrameT *> DetectRelocalizationCandidates(FrameT *F)
+    {
+        std::vector<uint32_t> id; std::vector<double> val;
+        flat(F->mBowVec, id, val);
+        std::vector<int32_t> cs, ci;
+        covis(cs, ci);
+        return pointers(db_.DetectRelocalizationCandidates(id, val, cs, ci));
+    }
+    plf::KeyFrameDatabase &device() { return db_; }
+private:
+    template <class BowVectorT> static void flat(const BowVectorT &v, std::vector<uint32_t> &id, std::vector<double> &val)
+    {
+        for (const auto &e : v) { id.push_back(e.first); val.push_back(e.second); }
+    }
+    void covis(std::vector<int32_t> &cs, std::vector<int32_t> &ci)
+    {
+        cs.assign(kf_.size() + 1, 0);
+        for (size_t s = 0; s < kf_.size(); s++) {
+            if (kf_[s])
+                for (KeyFrameT *n : kf_[s]->GetBestCovisibilityKeyFrames(10)) { const auto it = slot_.find(n); ci.push_back(it == slot_.end() ? -1 : it->second); }
+            cs[s + 1] = (int32_t)ci.size();
+        }
+    }
+    std::vector<KeyFrameT *> pointers(const std::vector<int32_t> &slots) const
+    {
+        std::vector<KeyFrameT *> out;
+        for (int32_t s : slots) out.push_back(kf_[s]);
+        return out;
+    }
+    plf::KeyFrameDatabase db_;
+    std::vector<KeyFrameT *> kf_;
+    std::unordered_map<KeyFrameT *, int> slot_;
 };
 
 // MapPoint::ComputeDistinctiveDescriptors / MapLine::ComputeDistinctiveDescriptors for a LIST of points of the reference's own types (what LocalMapping

@@ -7,5 +7,6 @@ from .lines import LineSegment  # noqa: F401
 from .matcher import Matcher, DescriptorDistance  # noqa: F401
 from . import frame  # noqa: F401
 from .bow import Vocabulary  # noqa: F401
+from .kfdb import KeyFrameDatabase  # noqa: F401
 from . import mappoints  # noqa: F401
 from .mappoints import distinctive_descriptors, MapPoint, MapLine  # noqa: F401

@@ -175,6 +175,31 @@ def bow_prototypes(l):
     return l
 
 
+# ---- keyframe database (include/plf.h, "Keyframe database")
+class KfdbInfo(C.Structure):
+    _fields_ = [("max_keyframes", C.c_int32), ("capacity", C.c_int32), ("n_keyframes", C.c_int32), ("n_entries", C.c_int32), ("n_best", C.c_int32)]
+
+
+KFDB_STATS_DTYPE = np.dtype([("n_sharing", "<i4"), ("max_common_words", "<i4"), ("n_scored", "<i4"), ("best_acc_score", "<f4")])
+
+
+def kfdb_prototypes(l):
+    P, I = C.c_void_p, C.c_int32
+    l.plf_vocab_device.argtypes = [P]
+    l.plf_kfdb_create.argtypes = [P, I, I, C.POINTER(P)]
+    l.plf_kfdb_destroy.argtypes = [P]
+    l.plf_kfdb_destroy.restype = None
+    l.plf_kfdb_info.argtypes = [P, C.POINTER(KfdbInfo)]
+    l.plf_kfdb_set_n_best.argtypes = [P, I]
+    l.plf_kfdb_add_batch.argtypes = [P, P, P, P, I, I, P, P]
+    l.plf_kfdb_erase_batch.argtypes = [P, P, I]
+    l.plf_kfdb_clear.argtypes = [P]
+    l.plf_kfdb_vectors.argtypes = [P, C.POINTER(P), C.POINTER(P), C.POINTER(P)]
+    l.plf_kfdb_detect_reloc.argtypes = [P, P, P, P, I, I, P, P, I, P, P, P, P]
+    l.plf_kfdb_detect_loop.argtypes = [P, P, P, P, I, I, P, P, P, P, P, I, P, P, P, P]
+    return l
+
+
 # ---- map (include/plf.h, "Map")
 class MapObsView(C.Structure):
     _fields_ = [("n_points", C.c_int32), ("obs_start", C.c_void_p), ("obs_desc", C.c_void_p), ("obs_kf", C.c_void_p), ("obs_idx", C.c_void_p),

@@ -182,6 +182,8 @@ extern "C" int plf_vocab_info(const plf_vocab *v, plf_vocab_info_t *out)
     return PLF_OK;
 }
 
+extern "C" int plf_vocab_device(const plf_vocab *v) { return v ? v->device : PLF_E_BADARG; }
+
 // ---- transform
 struct BowTemp {   // device buffers of one call with host memory on either side
     void *p[9] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};

@@ -3,6 +3,7 @@
 // ScoringObject.cpp:23-120 and :271-311, FORB.cpp:82-102.  Everything a double passes through is written as the reference writes it
 // (sequential adds, ascending word id; the Makefile's -ffp-contract=off keeps mul and add apart), so the outputs are bit-equal.
 #include "plf_common.h"
+#include "bow_score.h"
 
 // min over the 16 lanes of a DPP row; every lane of the row ends up with the row's minimum (the steps of plf_wave_sum)
 __device__ __forceinline__ uint32_t bow_row_min(uint32_t v)
@@ -195,44 +196,14 @@ __global__ void __launch_bounds__(BOW_T) k_bow_frame(const int32_t *__restrict__
     if (t == 0) { node_start[sbase + nn] = m; n_nodes[f] = nn; }
 }
 
-// ---- scoring: one wave per stored vector.  The lanes walk the shorter of the two vectors 64 entries at a time and look each word up in the
-// longer one (binary search); the terms of the common words are then added one by one in ascending word id, as the reference's merge loop
-// meets them (ScoringObject.cpp:34-59, :84-109, :283-308).
+// ---- scoring: one wave per stored vector; the merge itself is bow_score_wave (bow_score.h), shared with the keyframe database
 __global__ void __launch_bounds__(256) k_bow_score(int scoring, const uint32_t *__restrict__ q_id, const double *__restrict__ q_val, int q_n,
                                                    const uint32_t *__restrict__ db_id, const double *__restrict__ db_val,
                                                    const int32_t *__restrict__ db_start, int M, double *__restrict__ out)
 {
     const int j = (blockIdx.x * 256 + threadIdx.x) >> 6;   // wave-uniform
-    const int lane = plf_lane();
     if (j >= M) return;
     const int s = db_start[j], dn = max(0, db_start[j + 1] - s);
-    const bool q_short = q_n <= dn;
-    const uint32_t *a_id = q_short ? q_id : db_id + s;  const int an = q_short ? q_n : dn;       // walked
-    const uint32_t *b_id = q_short ? db_id + s : q_id;  const int bn = q_short ? dn : q_n;       // searched
-    const double *a_val = q_short ? q_val : db_val + s, *b_val = q_short ? db_val + s : q_val;
-    double score = 0.0;
-    for (int p0 = 0; p0 < an; p0 += 64) {
-        const int p = p0 + lane;
-        double term = 0.0;
-        bool hit = false;
-        if (p < an) {
-            const uint32_t w = a_id[p];
-            int lo = 0, hi = bn;
-            while (lo < hi) { const int mid = (lo + hi) >> 1; if (b_id[mid] < w) lo = mid + 1; else hi = mid; }
-            if (lo < bn && b_id[lo] == w) {
-                hit = true;
-                const double vi = q_short ? a_val[p] : b_val[lo], wi = q_short ? b_val[lo] : a_val[p];   // v1 = the query, v2 = the stored vector
-                term = scoring == PLF_BOW_L1_NORM ? fabs(vi - wi) - fabs(vi) - fabs(wi) : vi * wi;
-            }
-        }
-        unsigned long long mask = __ballot(hit);
-        while (mask) {
-            const int src = __ffsll((long long)mask) - 1;
-            score += __shfl(term, src, 64);
-            mask &= mask - 1;
-        }
-    }
-    if (scoring == PLF_BOW_L1_NORM) score = -score / 2.0;                               // ScoringObject.cpp:65
-    else if (scoring == PLF_BOW_L2_NORM) score = score >= 1 ? 1.0 : 1.0 - sqrt(1.0 - score);   // :114-117
-    if (lane == 0) out[j] = score;
+    const double score = bow_score_wave(scoring, q_id, q_val, q_n, db_id + s, db_val + s, dn, nullptr);
+    if (plf_lane() == 0) out[j] = score;
 }
