@@ -842,6 +842,84 @@ typedef struct {
 int plf_map_distinctive_descriptors(const plf_map_obs_view *obs, uint8_t *map_desc, int32_t map_rows, int32_t *best_obs, int32_t *best_median,
                                     int32_t device, void *stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * Covisibility graph -- void KeyFrame::UpdateConnections() include/KeyFrame.h (so@0x9fb60) and the count that opens
+ * void Tracking::UpdateLocalKeyFrames() (so@0x4d5a0), over the observation CSR plf_map_obs_view already carries: the rows
+ * (mvpOrderedConnectedKeyFrames, GetConnectedKeyFrames()) that plf_kfdb_detect_reloc / plf_kfdb_detect_loop read as covis_* / excl_*.
+ * Integer work only: every output is exact and two identical calls write identical bits.
+ *
+ * PLF_COVIS_CONNECTIONS, row = one keyframe's mvpMapPoints, from the binary:
+ *  1. per entry in order: null skipped (so@0x9fc92), MapPoint::isBad() skipped (so@0x9fc9a); for every observation whose keyframe's mnId is not
+ *     the row's own (so@0x9fcd0; here: slot != row_self) KFcounter[kf]++ (so@0x9fd3d).  No isBad() on the observer; a point listed twice
+ *     counts twice.
+ *  2. KFcounter empty: return, the lists stay (so@0x9fe73).  Here n_conn = n_ord = 0, max_kf = -1 and nothing else of the row is written.
+ *  3. in std::map<KeyFrame*, int> order = ascending key: a strictly greater count replaces (nmax, pKFmax) (so@0x9feae-0x9feb8: the first
+ *     maximum in key order wins); count > 14 (cmp $0xe, so@0x9febc) joins vPairs (and calls AddConnection, so@0x9ff0e); vPairs empty: the
+ *     single pair (nmax, pKFmax).
+ *  4. std::sort of (weight, KeyFrame*) ascending (so@0x9ff45), then push_front: DESCENDING by weight, equal weights DESCENDING by key.
+ *  5. mConnectedKeyFrameWeights = KFcounter, every weight (so@0xa01bd): conn_* is that map in key order, GetConnectedKeyFrames() (so@0x9c7c0) its keys.
+ *  6. under mbFirstConnection, mpParent = the front of the ordered list: ord_kf[r * stride].
+ * KEY (deviation): the reference's key is the keyframe's address, which no restatement can know.  kf_key gives one 64-bit value per slot, all
+ * distinct; a caller that wants the reference's own order of equal weights and of `first maximum` passes the pointers.  NULL = the slot index.
+ * `th` is 15 in the reference.  KeyFrame::UpdateBestCovisibles() (so@0x9f290), which AddConnection runs on the OTHER keyframe, orders its
+ * whole weight map without a threshold: the same call with th = 1 gives that list.  AddConnection itself -- the side effect on other
+ * keyframes -- stays with the caller; or the caller recomputes every row, which is what a whole-graph call (one row per keyframe) is for.
+ *
+ * PLF_COVIS_VOTES, row = one frame's mvpMapPoints: the same count with no row_self, every keyframe counted, bad ones included
+ * (so@0x4d68a, 0x4d69b); in key order a keyframe that isBad() (kf_bad, so@0x4d8d7) is skipped, the others are conn_* in key order
+ * (mvpLocalKeyFrames before its expansion) and the first strict maximum among them is max_kf / max_w (pKFmax, from max = 0).  No threshold,
+ * no sort: ord_kf / ord_w are not written and ord_* may be NULL (all three or none; when given, n_ord[r] = 0 is written for every row).  A count that is not empty but holds only bad keyframes has a result: n_conn = 0,
+ * max_kf = -1, max_w = 0.  The expansion by neighbours, children and parent is pointer-graph logic and stays with the caller.
+ *
+ * GetBestCovisibilityKeyFrames(N) (so@0x9cdb0) is the first min(N, n_ord) entries of a row of ord_kf.  GetCovisiblesByWeight(w) (so@0x9cff0):
+ * upper_bound with a > b (so@0x9d088-0x9d0bc) = the prefix before the first weight < w.  DIFFERS FROM UPSTREAM ORB-SLAM2: when no weight is
+ * below w upstream returns the empty list; this fork adds `&& back() < w` (so@0x9d160-0x9d166), which cannot hold there, so the binary
+ * returns the WHOLE list.  plf_covis_by_weight follows the binary.  An empty ordered list gives the empty list (so@0x9d05d).
+ *
+ * Layout: row r writes conn_* / ord_* at r * stride.  n_conn[r], n_ord[r] are the TRUE counts; entries at `stride` and beyond are not written.
+ * In a row with a result, *_kf from the count up to stride is -1, so ord_kf with covis_start[s] = s * stride is a valid covis_* argument of
+ * plf_kfdb_detect_*, which skips -1.  A row with an empty count writes its counts and max_kf = -1, nothing else (max_w neither): its old lists stay,
+ * as in the reference -- so ord_kf / conn_kf must hold -1 (or an earlier result) before the FIRST call that is to feed plf_kfdb_detect_*, which reads
+ * whole rows and ignores n_ord; the Python mirror allocates them filled with -1.
+ * No upper limit on a row's length, on observations per point or on n_kf.  Filler between and beyond the CSR ranges is never read.
+ * Counting: a dense LDS counter per slot while n_kf <= dense_max_kf (0 = 16384; at most 30720), an open-addressing LDS table of table_slots
+ * entries beyond (0 = 4096; rounded up to a power of two, at most 8192; full at 7/8), and per-workgroup dense counters in global memory for a
+ * row that fills the table.  Lists of up to 4096 entries are sorted in LDS, longer ones in global memory.  All three paths give the same bits.
+ * COST OF kf_key: every call that passes it ranks the n_kf keys first by counting, for each, the smaller ones: n_kf^2 compares (10^8 at 10,000 slots, well
+ * under a millisecond; 10^10 at 100,000, tens of milliseconds; 10^12 at a million, seconds) whatever the number of rows.  A per-frame votes call or a
+ * single-keyframe UpdateConnections on a map beyond some 50,000 keyframes should pass NULL (slot order) or batch its rows into fewer calls.
+ * The CSR may be any observation relation: passing the map-line observations is possible, but the reference states no covisibility rule over
+ * lines -- PARITY UNPINNED for that use.
+ * Stateless; every array is DEVICE memory; asynchronous on `stream` (NULL = the null stream); scratch comes from the stream-ordered pool.
+ * PLF_E_BADARG before any device work: a NULL required array, negative sizes, stride < 1, th < 1, an unknown mode, row_self in votes mode,
+ * ord_* missing in connections mode (in votes mode: all three or none).  row_self may be NULL in connections mode: no row has a keyframe of its own.
+ * ---------------------------------------------------------------------------------------------- */
+#define PLF_COVIS_CONNECTIONS 0
+#define PLF_COVIS_VOTES 1
+typedef struct {
+    int32_t n_rows;
+    const int32_t *row_start;        /* n_rows + 1: CSR of point ids per row (a keyframe's or a frame's mvpMapPoints) */
+    const int32_t *row_point;        /* point ids; -1 or outside [0, n_points) = null entry, skipped */
+    const int32_t *row_self;         /* connections mode: the row's own keyframe slot; -1 = none; NULL in votes mode */
+    int32_t n_points;
+    const int32_t *obs_start;        /* n_points + 1: the same CSR plf_map_obs_view carries */
+    const int32_t *obs_kf;           /* observing keyframe slot; outside [0, n_kf) skipped */
+    const uint8_t *point_bad;        /* optional, n_points: 1 = MapPoint::isBad() */
+    int32_t n_kf;
+    const uint8_t *kf_bad;           /* optional, n_kf: votes mode only (ignored in connections mode) */
+    const int64_t *kf_key;           /* optional, n_kf, distinct: map order and tie order; NULL = slot */
+} plf_covis_view;
+typedef struct { int32_t mode, th, stride, dense_max_kf, table_slots; } plf_covis_params;   /* the last two: 0 = default */
+
+/* conn_kf / conn_w / n_conn: KFcounter in key order (votes mode: without the bad keyframes).  ord_kf / ord_w / n_ord: the ordered list.
+ * max_kf / max_w: (pKFmax, nmax).  conn_* and ord_* hold n_rows * stride entries, the others n_rows. */
+int plf_covis_count(const plf_covis_view *v, const plf_covis_params *p, int32_t *conn_kf, int32_t *conn_w, int32_t *n_conn, int32_t *ord_kf,
+                    int32_t *ord_w, int32_t *n_ord, int32_t *max_kf, int32_t *max_w, int32_t device, void *stream);
+/* n_out[r] = how many leading entries of row r of ord_kf GetCovisiblesByWeight(w) returns.  Reads min(n_ord[r], stride) weights: a row
+ * whose true count exceeds stride is judged by what was written. */
+int plf_covis_by_weight(const int32_t *ord_w, const int32_t *n_ord, int32_t n_rows, int32_t stride, int32_t w, int32_t *n_out, int32_t device,
+                        void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -620,6 +620,7 @@ private:
 #if defined(PLF_WITH_OPENCV) && defined(__has_include)
 #if __has_include(<opencv2/core.hpp>)
 #include <cstring>
+#include <set>
 #include <unordered_map>
 #include <utility>
 #include <opencv2/core.hpp>
@@ -1086,6 +1087,175 @@ template <class MapLineT> DistinctiveDescriptors ComputeDistinctiveLineDescripto
 {
     return detail::distinctive(vpMapLines, [](auto *pKF) -> const cv::Mat & { return pKF->mLineDescriptors; }, device);
 }
+// The covisibility graph over the reference's own KeyFrame / MapPoint / Frame classes: KeyFrame::UpdateConnections (so@0x9fb60) for a LIST of keyframes in
+// one device call, and the KeyFrame queries that read its result -- GetConnectedKeyFrames (so@0x9c7c0), GetVectorCovisibleKeyFrames,
+// GetBestCovisibilityKeyFrames (so@0x9cdb0), GetCovisiblesByWeight (so@0x9cff0) -- with the keyframe as first argument, because the lists live here and
+// not in the keyframe.  Meant for the lists of keyframes a SLAM thread touches at a time, tens to a few thousand.  kf_key is the keyframe's ADDRESS, so ties resolve exactly as the reference's std::map<KeyFrame*, int> does.  What stays with the
+// caller: AddConnection on the OTHER keyframes (or list every keyframe, which recomputes every row), mbFirstConnection / mpParent / AddChild (Parent() names
+// the front of the ordered list).  EVERY CALL uploads the observation CSR of the points the listed keyframes hold: the price of starting from host
+// pointer members; a caller whose CSR is resident uses plf_covis_count and uploads nothing.
+template <class KeyFrameT, class MapPointT> class CovisibilityGraph {
+public:
+    struct Row {
+        std::vector<KeyFrameT *> connected;        // mConnectedKeyFrameWeights in key (address) order ...
+        std::vector<int> connectedWeights;         // ... and its weights
+        std::vector<KeyFrameT *> ordered;          // mvpOrderedConnectedKeyFrames
+        std::vector<int> orderedWeights;           // mvOrderedWeights
+    };
+    struct Votes {
+        std::vector<KeyFrameT *> vpLocalKeyFrames; // in keyframeCounter order, bad keyframes left out: mvpLocalKeyFrames before its expansion
+        std::vector<int> votes;
+        KeyFrameT *pKFmax = nullptr;
+        int max = 0;
+    };
+    explicit CovisibilityGraph(int device = 0, int first_stride = 256) : device_(device), first_stride_(std::max(first_stride, 1)) {}
+
+    // pKF->UpdateConnections() for every keyframe of the list.  A keyframe whose KFcounter is empty keeps its lists, as in the reference.
+    void UpdateConnections(const std::vector<KeyFrameT *> &vpKFs, int th = 15)
+    {
+        Gather g;
+        for (KeyFrameT *pKF : vpKFs) {
+            g.slot(pKF);
+            g.row(pKF->GetMapPointMatches());
+            g.self.push_back(g.slot(pKF));
+        }
+        if (vpKFs.empty()) return;
+        const int R = (int)vpKFs.size(), S = (int)g.kfs.size();
+        Device d(g, device_);
+        plf::DeviceArray<int32_t> self(g.self, device_), cn(R, device_), on(R, device_), mk(R, device_), mw(R, device_), ck, cw, ok, ow;
+        plf_covis_view v = d.view(R, S);
+        v.row_self = self.get();
+        // the outputs are R x stride: a first pass with a stride that holds an ordinary neighbourhood, and -- the counts are the true ones -- a second
+        // pass at the longest list only if some row did not fit.  (R x S would be 1.6 GB for a whole graph of 10,000 keyframes.)
+        int stride = std::max(1, std::min(S, first_stride_));
+        std::vector<int32_t> hcn, hon;
+        for (;;) {
+            ck.reset((size_t)R * stride, device_); cw.reset((size_t)R * stride, device_); ok.reset((size_t)R * stride, device_); ow.reset((size_t)R * stride, device_);
+            const plf_covis_params p = {PLF_COVIS_CONNECTIONS, th, stride, 0, 0};
+            plf::check(plf_covis_count(&v, &p, ck.get(), cw.get(), cn.get(), ok.get(), ow.get(), on.get(), mk.get(), mw.get(), device_, nullptr),
+                       "KeyFrame::UpdateConnections");
+            hcn = cn.download(); hon = on.download();
+            const int longest = *std::max_element(hcn.begin(), hcn.end());      // n_ord <= n_conn
+            if (longest <= stride) break;
+            stride = longest;
+        }
+        const std::vector<int32_t> hck = ck.download(), hcw = cw.download(), hok = ok.download(), how = ow.download();
+        for (int r = 0; r < R; r++) {
+            if (hcn[r] == 0) continue;
+            Row &row = rows_[vpKFs[r]];
+            row = Row();
+            for (int i = 0; i < hcn[r]; i++) { row.connected.push_back(g.kfs[hck[(size_t)r * stride + i]]); row.connectedWeights.push_back(hcw[(size_t)r * stride + i]); }
+            for (int i = 0; i < hon[r]; i++) { row.ordered.push_back(g.kfs[hok[(size_t)r * stride + i]]); row.orderedWeights.push_back(how[(size_t)r * stride + i]); }
+        }
+    }
+    void UpdateConnections(KeyFrameT *pKF) { UpdateConnections(std::vector<KeyFrameT *>(1, pKF)); }
+
+    std::set<KeyFrameT *> GetConnectedKeyFrames(KeyFrameT *pKF) const
+    {
+        const Row *r = find(pKF);
+        return r ? std::set<KeyFrameT *>(r->connected.begin(), r->connected.end()) : std::set<KeyFrameT *>();
+    }
+    std::vector<KeyFrameT *> GetVectorCovisibleKeyFrames(KeyFrameT *pKF) const { const Row *r = find(pKF); return r ? r->ordered : std::vector<KeyFrameT *>(); }
+    std::vector<KeyFrameT *> GetBestCovisibilityKeyFrames(KeyFrameT *pKF, const int &N) const
+    {
+        const Row *r = find(pKF);
+        if (!r) return std::vector<KeyFrameT *>();
+        return std::vector<KeyFrameT *>(r->ordered.begin(), r->ordered.begin() + std::min<size_t>(r->ordered.size(), (size_t)std::max(N, 0)));
+    }
+    // the lists are host vectors here, so this is the binary's own search (plf_covis_by_weight is the same rule over device rows): the prefix before the
+    // first weight below w; when no weight is below w, the whole list (the fork's `&& back() < w` cannot hold there; upstream returns the empty list)
+    std::vector<KeyFrameT *> GetCovisiblesByWeight(KeyFrameT *pKF, const int &w) const
+    {
+        const Row *r = find(pKF);
+        if (!r || r->ordered.empty()) return std::vector<KeyFrameT *>();
+        const auto it = std::upper_bound(r->orderedWeights.begin(), r->orderedWeights.end(), w, [](int a, int b) { return a > b; });
+        if (it == r->orderedWeights.end() && r->orderedWeights.back() < w) return std::vector<KeyFrameT *>();
+        return std::vector<KeyFrameT *>(r->ordered.begin(), r->ordered.begin() + (it - r->orderedWeights.begin()));
+    }
+    int GetWeight(KeyFrameT *pKF, KeyFrameT *pOther) const
+    {
+        const Row *r = find(pKF);
+        if (r) for (size_t i = 0; i < r->connected.size(); i++) if (r->connected[i] == pOther) return r->connectedWeights[i];
+        return 0;
+    }
+    KeyFrameT *Parent(KeyFrameT *pKF) const { const Row *r = find(pKF); return r && !r->ordered.empty() ? r->ordered.front() : nullptr; }   // what mbFirstConnection assigns
+    const Row *find(KeyFrameT *pKF) const { const auto it = rows_.find(pKF); return it == rows_.end() ? nullptr : &it->second; }
+
+    // the head of Tracking::UpdateLocalKeyFrames (so@0x4d5a0) for one frame: the votes of F.mvpMapPoints; an entry whose point isBad() is set to NULL, as there
+    template <class FrameT> Votes LocalKeyFrameVotes(FrameT &F) const
+    {
+        Votes out;
+        Gather g;
+        for (auto &pMP : F.mvpMapPoints) if (pMP && pMP->isBad()) pMP = nullptr;
+        g.row(F.mvpMapPoints);
+        const int S = (int)g.kfs.size(), stride = std::max(S, 1);
+        if (S == 0) return out;
+        Device d(g, device_);
+        std::vector<uint8_t> bad(S);
+        for (int s = 0; s < S; s++) bad[s] = g.kfs[s]->isBad();
+        plf::DeviceArray<uint8_t> dbad(bad, device_);
+        plf::DeviceArray<int32_t> ck(stride, device_), cw(stride, device_), cn(1, device_), mk(1, device_), mw(1, device_);
+        plf_covis_view v = d.view(1, S);
+        v.kf_bad = dbad.get();
+        const plf_covis_params p = {PLF_COVIS_VOTES, 1, stride, 0, 0};
+        plf::check(plf_covis_count(&v, &p, ck.get(), cw.get(), cn.get(), nullptr, nullptr, nullptr, mk.get(), mw.get(), device_, nullptr), "Tracking::UpdateLocalKeyFrames");
+        const std::vector<int32_t> hck = ck.download(), hcw = cw.download();
+        const int n = cn.download()[0], kmax = mk.download()[0];
+        for (int i = 0; i < n; i++) { out.vpLocalKeyFrames.push_back(g.kfs[hck[i]]); out.votes.push_back(hcw[i]); }
+        if (kmax >= 0) { out.pKFmax = g.kfs[kmax]; out.max = mw.download()[0]; }
+        return out;
+    }
+
+private:
+    // slots for the keyframes and ids for the points in order of first appearance; the two CSRs as host vectors
+    struct Gather {
+        std::vector<KeyFrameT *> kfs;
+        std::unordered_map<KeyFrameT *, int> kf_slot;
+        std::unordered_map<MapPointT *, int> point_id;
+        std::vector<int32_t> row_start{0}, row_point, self, obs_start{0}, obs_kf;
+        std::vector<uint8_t> point_bad;
+        int slot(KeyFrameT *pKF) { const auto at = kf_slot.emplace(pKF, (int)kfs.size()); if (at.second) kfs.push_back(pKF); return at.first->second; }
+        void row(const std::vector<MapPointT *> &points)
+        {
+            for (MapPointT *pMP : points) {
+                if (!pMP) { row_point.push_back(-1); continue; }
+                const auto at = point_id.emplace(pMP, (int)point_bad.size());
+                if (at.second) {
+                    point_bad.push_back(pMP->isBad());
+                    const auto observations = pMP->GetObservations();
+                    for (const auto &ob : observations) obs_kf.push_back(slot(ob.first));
+                    obs_start.push_back((int32_t)obs_kf.size());
+                }
+                row_point.push_back(at.first->second);
+            }
+            row_start.push_back((int32_t)row_point.size());
+        }
+    };
+    struct Device {
+        plf::DeviceArray<int32_t> row_start, row_point, obs_start, obs_kf;
+        plf::DeviceArray<uint8_t> point_bad;
+        plf::DeviceArray<int64_t> key;
+        int n_points;
+        Device(Gather &g, int device) : n_points((int)g.point_bad.size())
+        {
+            g.row_point.push_back(-1); g.obs_kf.push_back(-1); g.point_bad.push_back(0);      // never an empty allocation; beyond the CSR ranges, never read
+            std::vector<int64_t> k(g.kfs.size() + 1, 0);
+            for (size_t s = 0; s < g.kfs.size(); s++) k[s] = (int64_t)(intptr_t)g.kfs[s];
+            row_start.reset(g.row_start.size(), device); row_start.upload(g.row_start.data(), g.row_start.size());
+            row_point.reset(g.row_point.size(), device); row_point.upload(g.row_point.data(), g.row_point.size());
+            obs_start.reset(g.obs_start.size(), device); obs_start.upload(g.obs_start.data(), g.obs_start.size());
+            obs_kf.reset(g.obs_kf.size(), device); obs_kf.upload(g.obs_kf.data(), g.obs_kf.size());
+            point_bad.reset(g.point_bad.size(), device); point_bad.upload(g.point_bad.data(), g.point_bad.size());
+            key.reset(k.size(), device); key.upload(k.data(), k.size());
+        }
+        plf_covis_view view(int n_rows, int n_kf) const
+        {
+            return plf_covis_view{n_rows, row_start.get(), row_point.get(), nullptr, n_points, obs_start.get(), obs_kf.get(), point_bad.get(), n_kf, nullptr, key.get()};
+        }
+    };
+    int device_, first_stride_;
+    std::unordered_map<KeyFrameT *, Row> rows_;
+};
 }  // namespace ORB_SLAM2_PLF
 #endif
 #endif

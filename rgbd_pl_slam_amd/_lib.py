@@ -210,3 +210,24 @@ def map_prototypes(l):
     P, I = C.c_void_p, C.c_int32
     l.plf_map_distinctive_descriptors.argtypes = [C.POINTER(MapObsView), P, I, P, P, I, P]
     return l
+
+
+# ---- covisibility graph (include/plf.h, "Covisibility graph")
+COVIS_CONNECTIONS, COVIS_VOTES = 0, 1
+
+
+class CovisView(C.Structure):
+    _fields_ = [("n_rows", C.c_int32), ("row_start", C.c_void_p), ("row_point", C.c_void_p), ("row_self", C.c_void_p), ("n_points", C.c_int32),
+                ("obs_start", C.c_void_p), ("obs_kf", C.c_void_p), ("point_bad", C.c_void_p), ("n_kf", C.c_int32), ("kf_bad", C.c_void_p),
+                ("kf_key", C.c_void_p)]
+
+
+class CovisParams(C.Structure):
+    _fields_ = [("mode", C.c_int32), ("th", C.c_int32), ("stride", C.c_int32), ("dense_max_kf", C.c_int32), ("table_slots", C.c_int32)]
+
+
+def covis_prototypes(l):
+    P, I = C.c_void_p, C.c_int32
+    l.plf_covis_count.argtypes = [C.POINTER(CovisView), C.POINTER(CovisParams), P, P, P, P, P, P, P, P, I, P]
+    l.plf_covis_by_weight.argtypes = [P, P, I, I, I, P, I, P]
+    return l
