@@ -843,6 +843,68 @@ int plf_map_distinctive_descriptors(const plf_map_obs_view *obs, uint8_t *map_de
                                     int32_t device, void *stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Map geometry -- void MapPoint::UpdateNormalAndDepth() include/MapPoint.h (so@0x924e0) and void MapLine::UpdateAverageDir()
+ * include/MapLine.h:97: the statement that follows every ComputeDistinctiveDescriptors() in LocalMapping, loop closing and the bundle
+ * adjustments.  It writes mNormalVector, mfMinDistance and mfMaxDistance -- the `normal`, `min_distance`, `max_distance` arrays that
+ * plf_frustum_points / plf_frustum_lines read (GetNormal so@0x917b0, Get{Min,Max}DistanceInvariance so@0x8fa40 / 0x8fad0 apply the 0.8 / 1.2
+ * there).  The rule, from the binary:
+ *  1. mbBad set: return, nothing written (so@0x9265d).
+ *  2. observations = mObservations, pRefKF = mpRefKF, Pos = mWorldPos.clone(); observations empty: return, nothing written (so@0x92879).
+ *  3. normal = zeros(3,1,CV_32F) (so@0x92a90); for every observation in std::map order: Owi = pKF->GetCameraCenter() (so@0x92da7, KeyFrame
+ *     so@0x97900), normali = mWorldPos - Owi (so@0x92db7), normal = normal + normali / cv::norm(normali) (so@0x93098, 0x930ab, 0x930c2), n++
+ *     (so@0x934ac).  No isBad() test on the observing keyframe.
+ *  4. PC = Pos - pRefKF->GetCameraCenter() (so@0x93619, 0x93631), dist = (float)cv::norm(PC) (so@0x939b7, vcvtsd2ss so@0x939cb).
+ *  5. level = pRefKF->mvKeysUn[observations[pRefKF]].octave (so@0x93a4f .. 0x93a7e).  observations[...] is operator[] on the copy: the tree
+ *     search of so@0x939fc .. 0x93a1d falls through to _M_emplace_hint_unique (so@0x93a45) for a reference keyframe that does not observe the
+ *     point, which inserts index 0.
+ *  6. mfMaxDistance = dist * mvScaleFactors[level] (so@0x93ace, vmulss).
+ *  7. mfMinDistance = mfMaxDistance / mvScaleFactors[mnScaleLevels - 1] (so@0x93af6, vdivss).
+ *  8. mNormalVector = normal / n (so@0x93b08 vcvtsi2sd, so@0x93b0e).
+ * The OpenCV 3.3 routines the binary reaches through its PLT are not in the snapshot; they are restated [UPSTREAM]:
+ *  - a - b on CV_32F: one float subtraction per element.
+ *  - cv::norm(NORM_L2) of three floats: s = 0.0; s += (double)x * (double)x for x, y, z in that order; sqrt(s) in double.
+ *  - normal + normali / d folds to cv::scaleAdd(normali, 1.0 / d, normal): alpha = (float)(1.0 / d), a double division rounded once to float;
+ *    normal[k] = normali[k] * alpha + normal[k], a float multiply and then a float add, not fused.  Neither normali[k] / d nor a double sum.
+ *  - normal / n is convertTo with alpha = 1.0 / (double)n: normal[k] * (float)(1.0 / n) + 0.0f; the added zero turns a -0.0f product into +0.0f.
+ * The sum of step 3 is one dependent chain of float additions per component in the order of the CSR; the device adds it in that order in every
+ * schedule (the per-observation terms are what runs in parallel), so the result does not depend on the observation count's size class.
+ * mWorldPos == Owi gives d = 0, alpha = inf, 0 * inf = NaN: NaN propagates, as in the reference.
+ * MapLine::UpdateAverageDir has no body anywhere in the reference: it is taken as steps 1-8 at the segment's midpoint, the very expression
+ * plf_frustum_lines gates at, with the level given by the caller (the line extractor runs one octave) -- PARITY UNPINNED.
+ * Stateless; every pointer is DEVICE memory; asynchronous on `stream` (NULL = the null stream).
+ * ---------------------------------------------------------------------------------------------- */
+typedef struct {
+    int32_t n_points;
+    const int32_t *obs_start, *obs_kf;  /* the CSR plf_map_obs_view carries (n_points + 1; total); inside a point: the iteration order of mObservations
+                                         * (the float sum depends on it).  An obs_kf outside [0, n_kf) is skipped and not counted */
+    const int32_t *obs_idx;             /* total; needed for the indirect level form only */
+    const float   *kf_ow;               /* n_kf x 3: KeyFrame::GetCameraCenter() per slot */
+    int32_t n_kf;
+    const int32_t *ref_kf;              /* n_points: slot of mpRefKF; outside [0, n_kf): the point is left alone */
+    /* the level of step 5, in exactly one of two forms -- packed: */
+    const int32_t *ref_level;           /* n_points */
+    /* -- or indirect: the octave of kf_keys[ref_kf][idx], idx = obs_idx of the (first) observation whose obs_kf == ref_kf, 0 if there is none.
+     * idx is not checked against the keyframe's size, which the call does not have. */
+    const plf_keypoint *const *kf_keys; /* device table of n_kf device pointers to each keyframe's mvKeysUn (plf_frame_view.keys_un) */
+    const float   *scale_factors; int32_t nlevels;   /* mvScaleFactors (device), mnScaleLevels; not read when min / max_distance are NULL.  A level
+                                                      * outside [0, nlevels) is clamped to it (the reference reads out of bounds) */
+    const uint8_t *point_bad;           /* optional, n_points: 1 = isBad(), point untouched */
+    const int32_t *point_id;            /* optional (NULL = identity), DISTINCT: the row of world_pos / normal / min / max this point reads and writes;
+                                         * outside [0, map_rows): the point is left alone */
+    int32_t pos_floats;                 /* 3 = map points, 6 = map lines (start xyz, end xyz; midpoint rule; packed level form only) */
+} plf_map_geom_view;
+
+/* normal (map_rows x 3), min_distance, max_distance (map_rows) are written IN PLACE: the very arrays the frustum calls read.  Rows not named are
+ * untouched, and so are the rows of a point that is bad, has an empty range, a ref_kf or point_id out of range, or no observation left after the
+ * out-of-range ones are skipped.  n_obs_used (n_points): n of step 3, -1 for an untouched point.  min_distance and max_distance may both be NULL
+ * (UpdateAverageDir proper: direction only).  No upper limit on observations per point: up to 16 share a wave four points at a time, up to 256
+ * take a wave, more take a workgroup, 2048 terms in LDS at a time.  PLF_E_BADARG before any device work: a NULL required array, a negative
+ * size, both or neither level form, pos_floats not 3 or 6, the indirect form with pos_floats == 6 or without obs_idx, exactly one of
+ * min / max NULL, distances asked for without scale_factors or with nlevels < 1. */
+int plf_map_update_normal_depth(const plf_map_geom_view *v, const float *world_pos, float *normal, float *min_distance, float *max_distance,
+                                int32_t map_rows, int32_t *n_obs_used, int32_t device, void *stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Covisibility graph -- void KeyFrame::UpdateConnections() include/KeyFrame.h (so@0x9fb60) and the count that opens
  * void Tracking::UpdateLocalKeyFrames() (so@0x4d5a0), over the observation CSR plf_map_obs_view already carries: the rows
  * (mvpOrderedConnectedKeyFrames, GetConnectedKeyFrames()) that plf_kfdb_detect_reloc / plf_kfdb_detect_loop read as covis_* / excl_*.

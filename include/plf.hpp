@@ -359,6 +359,15 @@ struct MapPoint {
         check(plf_map_distinctive_descriptors(&mObservations_dev, mDescriptor_dev, map_rows, best_obs_dev, best_median_dev, device, stream),
               "MapPoint::ComputeDistinctiveDescriptors");
     }
+    // void MapPoint::UpdateNormalAndDepth() (so@0x924e0), the statement after every ComputeDistinctiveDescriptors(): mNormalVector, mfMinDistance and
+    // mfMaxDistance written in place into the arrays plf_frustum_points reads (plf_map_update_normal_depth; see plf_map_geom_view)
+    static void UpdateNormalAndDepth(const plf_map_geom_view &mObservations_dev, const float *mWorldPos_dev, float *mNormalVector_dev, float *mfMinDistance_dev,
+                                     float *mfMaxDistance_dev, int map_rows, int32_t *n_obs_used_dev, int device = 0, void *stream = nullptr)
+    {
+        check(plf_map_update_normal_depth(&mObservations_dev, mWorldPos_dev, mNormalVector_dev, mfMinDistance_dev, mfMaxDistance_dev, map_rows, n_obs_used_dev,
+                                          device, stream),
+              "MapPoint::UpdateNormalAndDepth");
+    }
 };
 // void MapLine::ComputeDistinctiveDescriptors() include/MapLine.h:93 -- declared without a body in the reference: the MapPoint rule over the keyframes'
 // line descriptors with LSDmatcher::DescriptorDistance (PARITY UNPINNED); writes mLDescriptor
@@ -368,6 +377,15 @@ struct MapLine {
     {
         check(plf_map_distinctive_descriptors(&mObservations_dev, mLDescriptor_dev, map_rows, best_obs_dev, best_median_dev, device, stream),
               "MapLine::ComputeDistinctiveDescriptors");
+    }
+    // void MapLine::UpdateAverageDir() include/MapLine.h:97 -- declared without a body in the reference: the MapPoint rule at the segment's midpoint
+    // (PARITY UNPINNED).  The view has pos_floats = 6 and the packed level form; the distances may both be NULL (direction only).
+    static void UpdateAverageDir(const plf_map_geom_view &mObservations_dev, const float *mWorldPos_dev, float *mNormalVector_dev, float *mfMinDistance_dev,
+                                 float *mfMaxDistance_dev, int map_rows, int32_t *n_obs_used_dev, int device = 0, void *stream = nullptr)
+    {
+        check(plf_map_update_normal_depth(&mObservations_dev, mWorldPos_dev, mNormalVector_dev, mfMinDistance_dev, mfMaxDistance_dev, map_rows, n_obs_used_dev,
+                                          device, stream),
+              "MapLine::UpdateAverageDir");
     }
 };
 
@@ -1086,6 +1104,65 @@ template <class MapPointT> DistinctiveDescriptors ComputeDistinctiveDescriptors(
 template <class MapLineT> DistinctiveDescriptors ComputeDistinctiveLineDescriptors(const std::vector<MapLineT *> &vpMapLines, int device = 0)
 {
     return detail::distinctive(vpMapLines, [](auto *pKF) -> const cv::Mat & { return pKF->mLineDescriptors; }, device);
+}
+// MapPoint::UpdateNormalAndDepth for a LIST of points of the reference's own types (the statement after ComputeDistinctiveDescriptors() in LocalMapping,
+// loop closing and after the bundle adjustments).  Reads isBad(), GetObservations() (the std::map's order), GetReferenceKeyFrame(), GetWorldPos(),
+// pKF->GetCameraCenter(), and of the reference keyframe mvKeysUn, mvScaleFactors and mnScaleLevels (the scale table of the first reference keyframe met
+// serves the call: every keyframe of a map carries the same one).  The level is resolved on the host, as operator[] does it (index 0 for a reference
+// keyframe that does not observe the point), and goes to the device in the packed form.  Uploads once per call; for ONE point the adapter is slower
+// than the loop it replaces.  mNormalVector / mfMinDistance / mfMaxDistance are protected in the reference: the forwarder inside MapPoint.cc assigns
+// them.  A null entry of the list is treated like a bad point.
+struct NormalAndDepth {
+    std::vector<float> normal;                  // points x 3: the new mNormalVector of point i (meaningful where n[i] > 0)
+    std::vector<float> minDistance, maxDistance;
+    std::vector<int32_t> n;                     // observations counted, -1 = leave the three members alone (bad point, no observation)
+};
+template <class MapPointT> NormalAndDepth UpdateNormalAndDepth(const std::vector<MapPointT *> &vpMapPoints, int device = 0)
+{
+    NormalAndDepth out;
+    const int P = (int)vpMapPoints.size();
+    out.normal.assign((size_t)P * 3, 0.0f); out.minDistance.assign(P, 0.0f); out.maxDistance.assign(P, 0.0f); out.n.assign(P, -1);
+    if (P == 0) return out;
+    std::vector<int32_t> start(P + 1, 0), kf, ref(P, -1), level(P, 0);
+    std::vector<uint8_t> bad(P, 1);
+    std::vector<float> pos((size_t)P * 3, 0.0f), ow, scale;
+    std::unordered_map<const void *, int> seen; // keyframe -> its slot in order of first appearance
+    auto slot_of = [&](auto *pKF) {
+        const auto at = seen.emplace((const void *)pKF, (int)seen.size());
+        if (at.second) { const cv::Mat Ow = pKF->GetCameraCenter(); for (int k = 0; k < 3; k++) ow.push_back(Ow.template at<float>(k)); }
+        return at.first->second;
+    };
+    for (int i = 0; i < P; i++) {
+        MapPointT *pMP = vpMapPoints[i];
+        if (pMP && !pMP->isBad()) {
+            bad[i] = 0;
+            const auto observations = pMP->GetObservations();
+            auto *pRefKF = pMP->GetReferenceKeyFrame();
+            const cv::Mat Pos = pMP->GetWorldPos();
+            for (int k = 0; k < 3; k++) pos[(size_t)i * 3 + k] = Pos.template at<float>(k);
+            for (const auto &ob : observations) kf.push_back(slot_of(ob.first));
+            if (pRefKF && !observations.empty()) {
+                ref[i] = slot_of(pRefKF);
+                const auto it = observations.find(pRefKF);
+                const size_t idx = it == observations.end() ? 0 : it->second;
+                level[i] = idx < pRefKF->mvKeysUn.size() ? pRefKF->mvKeysUn[idx].octave : 0;
+                if (scale.empty()) scale.assign(pRefKF->mvScaleFactors.begin(), pRefKF->mvScaleFactors.begin() + pRefKF->mnScaleLevels);
+            }
+        }
+        start[i + 1] = (int32_t)kf.size();
+    }
+    if (kf.empty() || scale.empty()) return out;
+    plf::DeviceArray<int32_t> dstart(start, device), dk(kf, device), dref(ref, device), dlevel(level, device), dn(P, device);
+    plf::DeviceArray<uint8_t> dbad(bad, device);
+    plf::DeviceArray<float> dpos(pos, device), dow(ow, device), dscale(scale, device), dnormal(out.normal, device), dmin(out.minDistance, device),
+        dmax(out.maxDistance, device);
+    plf_map_geom_view v = {};
+    v.n_points = P; v.obs_start = dstart.get(); v.obs_kf = dk.get(); v.kf_ow = dow.get(); v.n_kf = (int32_t)seen.size(); v.ref_kf = dref.get();
+    v.ref_level = dlevel.get(); v.scale_factors = dscale.get(); v.nlevels = (int32_t)scale.size(); v.point_bad = dbad.get(); v.pos_floats = 3;
+    plf::check(plf_map_update_normal_depth(&v, dpos.get(), dnormal.get(), dmin.get(), dmax.get(), P, dn.get(), device, nullptr), "UpdateNormalAndDepth");
+    out.normal = dnormal.download();                       // a NULL-stream download waits for the device first
+    out.minDistance = dmin.download(); out.maxDistance = dmax.download(); out.n = dn.download();
+    return out;
 }
 // The covisibility graph over the reference's own KeyFrame / MapPoint / Frame classes: KeyFrame::UpdateConnections (so@0x9fb60) for a LIST of keyframes in
 // one device call, and the KeyFrame queries that read its result -- GetConnectedKeyFrames (so@0x9c7c0), GetVectorCovisibleKeyFrames,

@@ -9,6 +9,6 @@ from . import frame  # noqa: F401
 from .bow import Vocabulary  # noqa: F401
 from .kfdb import KeyFrameDatabase  # noqa: F401
 from . import mappoints  # noqa: F401
-from .mappoints import distinctive_descriptors, MapPoint, MapLine  # noqa: F401
+from .mappoints import distinctive_descriptors, update_normal_and_depth, kf_keys_table, MapPoint, MapLine  # noqa: F401
 from . import covisibility  # noqa: F401
 from .covisibility import update_connections, local_keyframe_votes, Covisibility  # noqa: F401

@@ -212,6 +212,19 @@ def map_prototypes(l):
     return l
 
 
+# ---- map geometry (include/plf.h, "Map geometry")
+class MapGeomView(C.Structure):
+    _fields_ = [("n_points", C.c_int32), ("obs_start", C.c_void_p), ("obs_kf", C.c_void_p), ("obs_idx", C.c_void_p), ("kf_ow", C.c_void_p),
+                ("n_kf", C.c_int32), ("ref_kf", C.c_void_p), ("ref_level", C.c_void_p), ("kf_keys", C.c_void_p), ("scale_factors", C.c_void_p),
+                ("nlevels", C.c_int32), ("point_bad", C.c_void_p), ("point_id", C.c_void_p), ("pos_floats", C.c_int32)]
+
+
+def mapgeom_prototypes(l):
+    P, I = C.c_void_p, C.c_int32
+    l.plf_map_update_normal_depth.argtypes = [C.POINTER(MapGeomView), P, P, P, P, I, P, I, P]
+    return l
+
+
 # ---- covisibility graph (include/plf.h, "Covisibility graph")
 COVIS_CONNECTIONS, COVIS_VOTES = 0, 1
 

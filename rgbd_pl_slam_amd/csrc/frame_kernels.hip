@@ -230,7 +230,7 @@ __global__ void __launch_bounds__(256) k_frustum_lines(const float *__restrict__
     if (!frustum_project(P, cam, bounds, s0, s1, s2, u1, v1, r1)) return;
     if (!frustum_project(P, cam, bounds, e0, e1, e2, u2, v2, r2)) return;
     const float maxDistance = 1.2f * max_dist[i], minDistance = 0.8f * min_dist[i];
-    const float PO0 = 0.5f * (s0 + e0) - P.Ow[0], PO1 = 0.5f * (s1 + e1) - P.Ow[1], PO2 = 0.5f * (s2 + e2) - P.Ow[2];
+    const float PO0 = plf_seg_mid(s0, e0) - P.Ow[0], PO1 = plf_seg_mid(s1, e1) - P.Ow[1], PO2 = plf_seg_mid(s2, e2) - P.Ow[2];
     double s = 0;
     s += (double)PO0 * (double)PO0; s += (double)PO1 * (double)PO1; s += (double)PO2 * (double)PO2;
     const float dist = (float)sqrt(s);

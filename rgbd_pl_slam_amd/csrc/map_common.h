@@ -19,3 +19,17 @@ struct MapArgs {
 };
 
 static inline size_t map_block_lds(int waves, int cap) { return (size_t)cap * 33 + (size_t)waves * (8 + MAP_HIST * 4 + 4); }
+
+// ---- MapPoint::UpdateNormalAndDepth / MapLine::UpdateAverageDir (mapgeom_kernels.hip, mapgeom_host.hip).  The size classes are those above
+// (MAP_SMALL_MAX, MAP_WAVE_MAX); the workgroup schedule stages the terms of MAPGEOM_CHUNK observations at a time, so it has no upper limit.
+#define MAPGEOM_CHUNK 2048   // terms (x, y, z, counted) per LDS round of the workgroup schedule: 32 KB
+
+struct MapGeomArgs {
+    plf_map_geom_view v;
+    const float *world_pos;
+    float *normal, *min_distance, *max_distance;
+    int64_t map_rows;
+    int32_t *n_obs_used;
+    int32_t *list[3];        // point indices per size class, n_points entries each
+    int32_t *count;          // entries of the three lists
+};

@@ -25,6 +25,10 @@ static inline size_t plf_align_up(size_t v, size_t a) { return (v + a - 1) / a *
 // ---- wave-level helpers (64 lanes)
 __device__ __forceinline__ int plf_lane() { return threadIdx.x & 63; }
 
+// one coordinate of a map line's midpoint: the point at which Frame::isInFrustum(MapLine*) gates distance and viewing angle (frame_kernels.hip) and at
+// which MapLine::UpdateAverageDir takes normal and depth (mapgeom_kernels.hip) -- one expression, so that both see the same bits
+__device__ __forceinline__ float plf_seg_mid(float s, float e) { return 0.5f * (s + e); }
+
 // sum over the 64 lanes (all of them active), result wave-uniform: four DPP steps leave every lane of a row of 16 with its row's sum, four v_readlane add the
 // rows on the scalar unit.  (The butterfly over __shfl_xor was six ds_bpermute round trips with their address arithmetic and waits.)
 __device__ __forceinline__ int plf_wave_sum(int v)

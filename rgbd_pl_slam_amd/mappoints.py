@@ -1,5 +1,6 @@
-"""MapPoint::ComputeDistinctiveDescriptors / MapLine::ComputeDistinctiveDescriptors on the GPU: a thin mirror of plf_map_distinctive_descriptors
-(include/plf.h, "Map"); the compute is HIP (csrc/map_kernels.hip).  All arrays are device tensors (torch, cuda) or raw device addresses."""
+"""MapPoint::ComputeDistinctiveDescriptors / MapLine::ComputeDistinctiveDescriptors and MapPoint::UpdateNormalAndDepth / MapLine::UpdateAverageDir
+on the GPU: thin mirrors of plf_map_distinctive_descriptors and plf_map_update_normal_depth (include/plf.h, "Map" and "Map geometry"); the
+compute is HIP (csrc/map_kernels.hip, csrc/mapgeom_kernels.hip).  All arrays are device tensors (torch, cuda) or raw device addresses."""
 import ctypes as C
 
 from . import _lib as L
@@ -70,10 +71,76 @@ def distinctive_descriptors(obs_start, map_desc, obs_desc=None, obs_kf=None, obs
     return best_obs, best_median
 
 
+def kf_keys_table(buffers, device="cuda"):
+    """device table of key point buffer addresses (each keyframe's mvKeysUn: the extractor's keys_un output, 28-byte plf_keypoint records) for the
+    indirect level form of update_normal_and_depth: one entry per keyframe slot (tensors or raw addresses).  Keep it and the buffers alive while
+    calls that read it are in flight."""
+    return kf_table(buffers, device)
+
+
+def update_normal_and_depth(obs_start, obs_kf, kf_ow, ref_kf, world_pos, normal, min_distance=None, max_distance=None, ref_level=None, obs_idx=None,
+                            kf_keys=None, scale_factors=None, point_bad=None, point_id=None, n_obs_used=None, device=0, stream=None, n_points=None,
+                            map_rows=None, n_kf=None, nlevels=None, pos_floats=None):
+    """obs_start (n_points + 1,), obs_kf (total,) int32: the observation CSR, inside a point in the iteration order of mObservations (the float sum
+    depends on it).  kf_ow (n_kf, 3) float32: the camera centres.  ref_kf (n_points,) int32: slot of mpRefKF.  The level of the reference key, in
+    exactly one form: packed `ref_level` (n_points,) int32, or indirect `obs_idx` (total,) int32 with `kf_keys` = kf_keys_table(...).
+    scale_factors (nlevels,) float32: mvScaleFactors.  point_bad (n_points,) uint8, point_id (n_points,) int32, distinct: optional.
+    world_pos (rows, 3) float32 for map points, (rows, 6) for map lines (the rule runs at the midpoint; packed level form only).
+    normal (rows, 3), min_distance, max_distance (rows,) float32 are updated IN PLACE; min / max may both be None (direction only).
+    Returns n_obs_used, an int32 device tensor: observations counted per point, -1 for a point left alone (bad, empty, ref_kf or row out of range).
+    Every array is a contiguous torch tensor on the GPU of the dtype named above (checked), or an int device address (taken as it is); with
+    addresses, `n_points`, `map_rows`, `n_kf`, `nlevels` and `pos_floats` give what a tensor would have carried.
+    Only enqueues, on `stream` (a raw HIP stream) or the null stream."""
+    import torch
+    lib = L.mapgeom_prototypes(L.lib())
+
+    def size(given, a, what, dim=0, minus=0):
+        if given is not None:
+            return given
+        if a is None:
+            return 0
+        if isinstance(a, int):
+            raise ValueError("%s is an address: give its size" % what)
+        return int(a.shape[dim]) - minus
+
+    n_points = size(n_points, obs_start, "obs_start", minus=1)
+    map_rows = size(map_rows, normal, "normal")
+    n_kf = size(n_kf, kf_ow, "kf_ow")
+    nlevels = size(nlevels, scale_factors, "scale_factors")
+    if pos_floats is None:
+        if isinstance(world_pos, int) or world_pos.dim() != 2:
+            raise ValueError("world_pos is not a (rows, 3) or (rows, 6) tensor: give pos_floats")
+        pos_floats = int(world_pos.shape[1])
+    v = L.MapGeomView()
+    v.n_points = n_points
+    v.obs_start = _arg(obs_start, "obs_start", torch.int32, n_points + 1)
+    v.obs_kf = _arg(obs_kf, "obs_kf", torch.int32)
+    v.obs_idx = _arg(obs_idx, "obs_idx", torch.int32)
+    v.kf_ow = _arg(kf_ow, "kf_ow", torch.float32, n_kf)
+    v.n_kf = n_kf
+    v.ref_kf = _arg(ref_kf, "ref_kf", torch.int32, n_points)
+    v.ref_level = _arg(ref_level, "ref_level", torch.int32, n_points)
+    v.kf_keys = _arg(kf_keys, "kf_keys", torch.int64, n_kf)
+    v.scale_factors = _arg(scale_factors, "scale_factors", torch.float32)
+    v.nlevels = nlevels
+    v.point_bad = _arg(point_bad, "point_bad", torch.uint8, n_points)
+    v.point_id = _arg(point_id, "point_id", torch.int32, n_points)
+    v.pos_floats = pos_floats
+    if n_obs_used is None:
+        n_obs_used = torch.empty(max(n_points, 0), dtype=torch.int32, device="cuda:%d" % device if isinstance(normal, int) or normal is None else normal.device)
+    L.check(lib.plf_map_update_normal_depth(C.byref(v), _arg(world_pos, "world_pos", torch.float32, map_rows), _arg(normal, "normal", torch.float32, map_rows),
+                                            _arg(min_distance, "min_distance", torch.float32, map_rows), _arg(max_distance, "max_distance", torch.float32, map_rows),
+                                            map_rows, _arg(n_obs_used, "n_obs_used", torch.int32, n_points), device, C.c_void_p(stream) if stream else None),
+            "plf_map_update_normal_depth")
+    return n_obs_used
+
+
 class MapPoint:
     ComputeDistinctiveDescriptors = staticmethod(distinctive_descriptors)
+    UpdateNormalAndDepth = staticmethod(update_normal_and_depth)
 
 
 class MapLine:
-    """the same rule over mLdesc (the reference has no body for the line routine: parity unpinned)"""
+    """the same rules over mLdesc and the segment's midpoint (the reference has no body for the line routines: parity unpinned)"""
     ComputeDistinctiveDescriptors = staticmethod(distinctive_descriptors)
+    UpdateAverageDir = staticmethod(update_normal_and_depth)
