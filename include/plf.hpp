@@ -703,6 +703,17 @@ inline std::vector<uint8_t> rows32(const cv::Mat &m)   // n x 32 CV_8U, rows pos
     for (int r = 0; r < m.rows; r++) memcpy(&out[(size_t)r * 32], m.data + (size_t)r * m.step, 32);
     return out;
 }
+// keyframe pointer -> slot in order of first appearance; first(pKF) runs once, when the keyframe is met for the first time
+struct KeyFrameSlots {
+    std::unordered_map<const void *, int> slot;
+    size_t size() const { return slot.size(); }
+    template <class KeyFrameT, class First> int operator()(KeyFrameT *pKF, First first)
+    {
+        const auto at = slot.emplace((const void *)pKF, (int)slot.size());
+        if (at.second) first(pKF);
+        return at.first->second;
+    }
+};
 inline void pose34(const cv::Mat &Tcw, float *R, float *t)   // 4x4 CV_32F
 {
     for (int r = 0; r < 3; r++) { for (int c = 0; c < 3; c++) R[r * 3 + c] = Tcw.at<float>(r, c); t[r] = Tcw.at<float>(r, 3); }
@@ -1063,16 +1074,14 @@ template <class PointT, class DescOf> DistinctiveDescriptors distinctive(const s
     memset(out.desc.data, 0, (size_t)P * 32);
     std::vector<int32_t> start(P + 1, 0), kf, idx;
     std::vector<uint8_t> valid;
-    std::unordered_map<const void *, int> seen; // keyframe -> its index in order of first appearance
+    KeyFrameSlots seen;
     std::vector<std::vector<uint8_t>> rows;
     for (int i = 0; i < P; i++) {
         if (points[i]) {
             const auto observations = points[i]->GetObservations();
             for (const auto &ob : observations) {
                 auto *pKF = ob.first;
-                const auto at = seen.emplace((const void *)pKF, (int)seen.size());
-                if (at.second) rows.push_back(rows32(descOf(pKF)));
-                kf.push_back(at.first->second); idx.push_back((int32_t)ob.second); valid.push_back(!pKF->isBad());
+                kf.push_back(seen(pKF, [&](auto *first) { rows.push_back(rows32(descOf(first))); })); idx.push_back((int32_t)ob.second); valid.push_back(!pKF->isBad());
             }
         }
         start[i + 1] = (int32_t)kf.size();
@@ -1126,11 +1135,9 @@ template <class MapPointT> NormalAndDepth UpdateNormalAndDepth(const std::vector
     std::vector<int32_t> start(P + 1, 0), kf, ref(P, -1), level(P, 0);
     std::vector<uint8_t> bad(P, 1);
     std::vector<float> pos((size_t)P * 3, 0.0f), ow, scale;
-    std::unordered_map<const void *, int> seen; // keyframe -> its slot in order of first appearance
+    detail::KeyFrameSlots seen;
     auto slot_of = [&](auto *pKF) {
-        const auto at = seen.emplace((const void *)pKF, (int)seen.size());
-        if (at.second) { const cv::Mat Ow = pKF->GetCameraCenter(); for (int k = 0; k < 3; k++) ow.push_back(Ow.template at<float>(k)); }
-        return at.first->second;
+        return seen(pKF, [&](auto *first) { const cv::Mat Ow = first->GetCameraCenter(); for (int k = 0; k < 3; k++) ow.push_back(Ow.template at<float>(k)); });
     };
     for (int i = 0; i < P; i++) {
         MapPointT *pMP = vpMapPoints[i];
@@ -1287,11 +1294,11 @@ private:
     // slots for the keyframes and ids for the points in order of first appearance; the two CSRs as host vectors
     struct Gather {
         std::vector<KeyFrameT *> kfs;
-        std::unordered_map<KeyFrameT *, int> kf_slot;
+        detail::KeyFrameSlots kf_slot;
         std::unordered_map<MapPointT *, int> point_id;
         std::vector<int32_t> row_start{0}, row_point, self, obs_start{0}, obs_kf;
         std::vector<uint8_t> point_bad;
-        int slot(KeyFrameT *pKF) { const auto at = kf_slot.emplace(pKF, (int)kfs.size()); if (at.second) kfs.push_back(pKF); return at.first->second; }
+        int slot(KeyFrameT *pKF) { return kf_slot(pKF, [&](KeyFrameT *first) { kfs.push_back(first); }); }
         void row(const std::vector<MapPointT *> &points)
         {
             for (MapPointT *pMP : points) {
@@ -1309,21 +1316,20 @@ private:
         }
     };
     struct Device {
+        int n_points;
         plf::DeviceArray<int32_t> row_start, row_point, obs_start, obs_kf;
         plf::DeviceArray<uint8_t> point_bad;
         plf::DeviceArray<int64_t> key;
-        int n_points;
-        Device(Gather &g, int device) : n_points((int)g.point_bad.size())
+        // one element of padding each: never an empty allocation; beyond the CSR ranges, never read
+        Device(Gather &g, int device)
+            : n_points((int)g.point_bad.size()), row_start(g.row_start, device), row_point(padded(g.row_point, -1), device), obs_start(g.obs_start, device),
+              obs_kf(padded(g.obs_kf, -1), device), point_bad(padded(g.point_bad, 0), device), key(keys(g.kfs), device) {}
+        template <class T> static const std::vector<T> &padded(std::vector<T> &v, int pad) { v.push_back((T)pad); return v; }
+        static std::vector<int64_t> keys(const std::vector<KeyFrameT *> &kfs)
         {
-            g.row_point.push_back(-1); g.obs_kf.push_back(-1); g.point_bad.push_back(0);      // never an empty allocation; beyond the CSR ranges, never read
-            std::vector<int64_t> k(g.kfs.size() + 1, 0);
-            for (size_t s = 0; s < g.kfs.size(); s++) k[s] = (int64_t)(intptr_t)g.kfs[s];
-            row_start.reset(g.row_start.size(), device); row_start.upload(g.row_start.data(), g.row_start.size());
-            row_point.reset(g.row_point.size(), device); row_point.upload(g.row_point.data(), g.row_point.size());
-            obs_start.reset(g.obs_start.size(), device); obs_start.upload(g.obs_start.data(), g.obs_start.size());
-            obs_kf.reset(g.obs_kf.size(), device); obs_kf.upload(g.obs_kf.data(), g.obs_kf.size());
-            point_bad.reset(g.point_bad.size(), device); point_bad.upload(g.point_bad.data(), g.point_bad.size());
-            key.reset(k.size(), device); key.upload(k.data(), k.size());
+            std::vector<int64_t> k(kfs.size() + 1, 0);
+            for (size_t s = 0; s < kfs.size(); s++) k[s] = (int64_t)(intptr_t)kfs[s];
+            return k;
         }
         plf_covis_view view(int n_rows, int n_kf) const
         {

@@ -124,9 +124,7 @@ extern "C" int plf_vocab_create(const plf_vocab_desc *d, int32_t device, plf_voc
         else if (nchild[i] < 1 || nchild[i] > 32) return PLF_E_BADARG;
         if (nchild[i] > max_children) max_children = nchild[i];
     }
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) { (void)hipGetLastError(); return PLF_E_HIP; }
-    if (device < 0 || device >= ndev) return PLF_E_BADARG;
+    PLF_TRY(plf_select_device(device));
     // repack in child order: the children of a node become one contiguous block of slots, in ascending NodeId (the order :1416 appends them)
     std::vector<int> first(n, 0), slot_of(n, 0);
     int next = 1;
@@ -149,7 +147,6 @@ extern "C" int plf_vocab_create(const plf_vocab_desc *d, int32_t device, plf_voc
     v->info = plf_vocab_info_t{d->k, d->L, d->scoring, d->weighting, n, n_words, min_leaf};
     v->max_children = max_children;
 #define BOW_TRY(expr) do { if ((expr) != hipSuccess) { (void)hipGetLastError(); plf_vocab_destroy(v); return PLF_E_HIP; } } while (0)
-    BOW_TRY(hipSetDevice(device));
     BOW_TRY(hipStreamCreateWithFlags(&v->stream, hipStreamNonBlocking));
     BOW_TRY(hipMalloc((void **)&v->d_info, (size_t)n * sizeof(int4)));
     BOW_TRY(hipMalloc((void **)&v->d_desc, (size_t)n * 32));

@@ -8,20 +8,11 @@ __global__ void k_covis_rows(CovisArgs);
 __global__ void k_covis_rank(const int64_t *, int, int32_t *, int32_t *);
 __global__ void k_covis_by_weight(const int32_t *, const int32_t *, int, int, int, int32_t *);
 
-#define COVIS_MAX_DEVICES 64
 #define COVIS_MAX_GRID 1024
 #define COVIS_SCRATCH_BYTES ((size_t)256 << 20)   // bound of the per-workgroup scratch: fewer workgroups rather than more memory
-static bool g_covis_ready[COVIS_MAX_DEVICES];     // per device: LDS attribute of k_covis_rows set (idempotent, so a race only repeats it)
+static PlfLdsOnce g_covis_lds = {(const void *)k_covis_rows, (int)covis_lds_bytes(1, COVIS_DENSE_LIMIT, 0, COVIS_SORT_CAP)};
 
-static int covis_device(int32_t device)
-{
-    if (device < 0 || device >= COVIS_MAX_DEVICES) return PLF_E_BADARG;
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) { (void)hipGetLastError(); return PLF_E_HIP; }
-    if (device >= ndev) return PLF_E_BADARG;
-    PLF_HIP_TRY(hipSetDevice(device));
-    return PLF_OK;
-}
+static int covis_device(int32_t device) { return device < 0 || device >= PLF_MAX_DEVICES ? PLF_E_BADARG : plf_select_device(device); }
 
 extern "C" int plf_covis_count(const plf_covis_view *v, const plf_covis_params *p, int32_t *conn_kf, int32_t *conn_w, int32_t *n_conn, int32_t *ord_kf,
                                int32_t *ord_w, int32_t *n_ord, int32_t *max_kf, int32_t *max_w, int32_t device, void *stream)
@@ -33,7 +24,7 @@ extern "C" int plf_covis_count(const plf_covis_view *v, const plf_covis_params *
     if (p->mode == PLF_COVIS_VOTES && v->row_self) return PLF_E_BADARG;
     if (p->mode == PLF_COVIS_CONNECTIONS && (!ord_kf || !ord_w || !n_ord)) return PLF_E_BADARG;
     if (p->mode == PLF_COVIS_VOTES && (ord_kf || ord_w || n_ord) && !(ord_kf && ord_w && n_ord)) return PLF_E_BADARG;   // all three or none
-    { const int st = covis_device(device); if (st != PLF_OK) return st; }
+    PLF_TRY(covis_device(device));
     if (v->n_rows == 0) return PLF_OK;
 
     CovisArgs a;
@@ -56,21 +47,11 @@ extern "C" int plf_covis_count(const plf_covis_view *v, const plf_covis_params *
     if (cnt_bytes + list_bytes) grid = std::min(grid, std::max<size_t>(1, COVIS_SCRATCH_BYTES / (cnt_bytes + list_bytes)));
     const size_t bytes = rank_bytes + grid * (cnt_bytes + list_bytes);
 
-    if (!g_covis_ready[device]) {
-        PLF_HIP_TRY(hipFuncSetAttribute((const void *)k_covis_rows, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                        (int)covis_lds_bytes(1, COVIS_DENSE_LIMIT, 0, COVIS_SORT_CAP)));
-        g_covis_ready[device] = true;
-    }
+    PLF_TRY(plf_lds_once(g_covis_lds, device));
     hipStream_t s = (hipStream_t)stream;
-    char *scratch = nullptr;
-    bool pooled = true;
-    if (bytes) {
-        if (hipMallocAsync((void **)&scratch, bytes, s) != hipSuccess) {    // no stream-ordered allocator: a plain allocation, and the call waits for its work
-            (void)hipGetLastError();
-            pooled = false;
-            if (hipMalloc((void **)&scratch, bytes) != hipSuccess) { (void)hipGetLastError(); return PLF_E_NOMEM; }
-        }
-    }
+    PlfScratch mem = {nullptr, true};
+    if (bytes) PLF_TRY(plf_scratch_acquire(mem, bytes, s));
+    char *scratch = (char *)mem.p;
     int32_t *rank = v->kf_key ? (int32_t *)scratch : nullptr;
     a.rank = rank; a.inv = rank ? rank + n_kf : nullptr;
     a.g_cnt = cnt_bytes ? (int32_t *)(scratch + rank_bytes) : nullptr;
@@ -82,18 +63,14 @@ extern "C" int plf_covis_count(const plf_covis_view *v, const plf_covis_params *
         hipLaunchKernelGGL(k_covis_rows, dim3((unsigned)grid), dim3(COVIS_T), covis_lds_bytes(a.dense, v->n_kf, slots, a.list_cap), s, a);
         if (hipGetLastError() != hipSuccess) st = PLF_E_HIP;
     }
-    if (scratch) {
-        if (pooled) { if (hipFreeAsync(scratch, s) != hipSuccess) { (void)hipGetLastError(); st = PLF_E_HIP; } }
-        else { if (hipStreamSynchronize(s) != hipSuccess) { (void)hipGetLastError(); st = PLF_E_HIP; } (void)hipFree(scratch); }
-    }
-    return st;
+    return scratch ? plf_scratch_release(mem, s, st) : st;
 }
 
 extern "C" int plf_covis_by_weight(const int32_t *ord_w, const int32_t *n_ord, int32_t n_rows, int32_t stride, int32_t w, int32_t *n_out, int32_t device,
                                    void *stream)
 {
     if (!ord_w || !n_ord || !n_out || n_rows < 0 || stride < 1) return PLF_E_BADARG;
-    { const int st = covis_device(device); if (st != PLF_OK) return st; }
+    PLF_TRY(covis_device(device));
     if (n_rows == 0) return PLF_OK;
     hipLaunchKernelGGL(k_covis_by_weight, dim3((unsigned)((n_rows + COVIS_T - 1) / COVIS_T)), dim3(COVIS_T), 0, (hipStream_t)stream, ord_w, n_ord, n_rows, stride, w,
                        n_out);

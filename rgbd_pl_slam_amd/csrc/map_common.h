@@ -1,4 +1,4 @@
-// map_common.h -- shared by map_kernels.hip and map_host.hip (include/plf.h, "Map")
+// map_common.h -- shared by map_kernels.hip / map_host.hip (include/plf.h, "Map") and mapgeom_kernels.hip / mapgeom_host.hip ("Map geometry")
 #pragma once
 #include "plf_common.h"
 
@@ -8,13 +8,35 @@
 #define MAP_NAIVE_CAP 1024   // of the naive schedule's single wave (32 KB, so several fit a CU)
 #define MAP_HIST 320         // histogram bins per wave: 257 distances, rounded up to five per lane
 
+// the three lists of point indices a binning pre-pass fills, one per size class with room for every point, and their counters: (3 * n + 4) ints of scratch
+struct MapBins { int32_t *list[3]; int32_t *count; };
+static inline size_t map_bins_bytes(size_t n) { return (3 * n + 4) * sizeof(int32_t); }
+static inline MapBins map_bins_at(void *scratch, size_t n) { int32_t *s = (int32_t *)scratch; return MapBins{{s, s + n, s + 2 * n}, s + 3 * n}; }
+// every kernel walks its list with a grid-stride loop: the grids are sized for the machine, not for counts the host does not have
+static inline dim3 map_grid(size_t n, size_t per_block, size_t cap = 2048) { const size_t g = (n + per_block - 1) / per_block; return dim3((unsigned)(g < cap ? g : cap)); }
+#ifdef __HIPCC__
+// one step of a pre-pass, run by every lane of a wave: the lane's point p joins the list of its class cls (0 .. 2, any other value: no list), with one
+// atomic per wave and class.  The rule that gives a point its class is the caller's.
+__device__ __forceinline__ void map_bins_append(const MapBins &b, int cls, int p)
+{
+#pragma unroll
+    for (int c = 0; c < 3; c++) {
+        const unsigned long long mask = __ballot(cls == c);
+        if (!mask) continue;
+        int base = 0;
+        if (plf_lane() == 0) base = atomicAdd(&b.count[c], __popcll(mask));
+        base = __builtin_amdgcn_readfirstlane(base);
+        if (cls == c) b.list[c][base + plf_lanes_below(mask)] = p;
+    }
+}
+#endif
+
 struct MapArgs {
     plf_map_obs_view v;
     uint8_t *map_desc;
     int64_t map_rows;
     int32_t *best_obs, *best_median;
-    int32_t *list[3];        // point indices per size class, n_points entries each
-    int32_t *count;          // entries of the three lists
+    MapBins bins;
     int naive;               // one wave per point whatever its count (k_map_wave up to 256, k_map_block with one wave beyond): the A/B baseline of tools/bench_distinct.py
 };
 
@@ -30,6 +52,5 @@ struct MapGeomArgs {
     float *normal, *min_distance, *max_distance;
     int64_t map_rows;
     int32_t *n_obs_used;
-    int32_t *list[3];        // point indices per size class, n_points entries each
-    int32_t *count;          // entries of the three lists
+    MapBins bins;
 };

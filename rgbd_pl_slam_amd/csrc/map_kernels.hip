@@ -17,10 +17,6 @@ __device__ __forceinline__ uint32_t map_row_min(uint32_t v)   // min over a DPP 
     v = min(v, (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x140, 0xF, 0xF, false));   // row_mirror
     return v;
 }
-__device__ __forceinline__ int map_lanes_below(unsigned long long mask)   // set bits of mask below this lane
-{
-    return (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(mask >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mask, 0u));
-}
 // observation o (a position of the CSR) takes part: its keyframe is not isBad() (so@0x94706); the indirect form also drops a keyframe index outside the table
 __device__ __forceinline__ bool map_valid(const plf_map_obs_view &v, int64_t o)
 {
@@ -62,15 +58,7 @@ __global__ void __launch_bounds__(256) k_map_bin(MapArgs a)
             cls = n <= 0 ? 3 : n <= MAP_SMALL_MAX && !a.naive ? 0 : n <= MAP_WAVE_MAX ? 1 : 2;
             if (cls == 3) map_store_none(a, (int)p);
         }
-#pragma unroll
-        for (int c = 0; c < 3; c++) {
-            const unsigned long long mask = __ballot(cls == c);
-            if (!mask) continue;
-            int base = 0;
-            if (lane == 0) base = atomicAdd(&a.count[c], __popcll(mask));
-            base = __builtin_amdgcn_readfirstlane(base);
-            if (cls == c) a.list[c][base + map_lanes_below(mask)] = (int)p;
-        }
+        map_bins_append(a.bins, cls, (int)p);
     }
 }
 
@@ -80,13 +68,13 @@ __global__ void __launch_bounds__(256) k_map_small(MapArgs a)
 {
     __shared__ uint4 s_d[256 * 2];
     const int t = threadIdx.x, g = t >> 4, i = t & 15;
-    const int cnt = a.count[0];
+    const int cnt = a.bins.count[0];
     for (int q0 = blockIdx.x * 16; q0 < cnt; q0 += gridDim.x * 16) {   // workgroup-uniform
         const int q = q0 + g;
         const bool act = q < cnt;
         int pt = 0, n = 0;
         int64_t s = 0;
-        if (act) { pt = a.list[0][q]; s = a.v.obs_start[pt]; n = a.v.obs_start[pt + 1] - (int)s; }
+        if (act) { pt = a.bins.list[0][q]; s = a.v.obs_start[pt]; n = a.v.obs_start[pt + 1] - (int)s; }
         const bool ok = act && i < n && map_valid(a.v, s + i);
         uint4 x0 = make_uint4(0, 0, 0, 0), x1 = x0;
         if (ok) { const uint4 *p = map_desc_of(a.v, s + i); x0 = p[0]; x1 = p[1]; }
@@ -125,9 +113,9 @@ __global__ void __launch_bounds__(256) k_map_wave(MapArgs a)
 {
     __shared__ uint16_t s_pos[4][MAP_WAVE_MAX];
     const int lane = plf_lane(), w = threadIdx.x >> 6;
-    const int cnt = a.count[1];
+    const int cnt = a.bins.count[1];
     for (int q = blockIdx.x * 4 + w; q < cnt; q += gridDim.x * 4) {   // wave-uniform
-        const int pt = a.list[1][q];
+        const int pt = a.bins.list[1][q];
         const int64_t s = a.v.obs_start[pt];
         const int n = min(a.v.obs_start[pt + 1] - (int)s, MAP_WAVE_MAX);
         int N = 0;
@@ -136,7 +124,7 @@ __global__ void __launch_bounds__(256) k_map_wave(MapArgs a)
             const int p = c * 64 + lane;
             const bool ok = p < n && map_valid(a.v, s + p);
             const unsigned long long mask = __ballot(ok);
-            if (ok) s_pos[w][N + map_lanes_below(mask)] = (uint16_t)p;
+            if (ok) s_pos[w][N + plf_lanes_below(mask)] = (uint16_t)p;
             N += __popcll(mask);
         }
         __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");
@@ -202,9 +190,9 @@ __global__ void __launch_bounds__(1024) k_map_block(MapArgs a, int cap)
     int *s_hist = (int *)(s_wbest + W), *s_wsum = s_hist + W * MAP_HIST;
     uint8_t *s_valid = (uint8_t *)(s_wsum + W);
     int *hist = s_hist + w * MAP_HIST;
-    const int cnt = a.count[2];
+    const int cnt = a.bins.count[2];
     for (int q = blockIdx.x; q < cnt; q += gridDim.x) {   // workgroup-uniform
-        const int pt = a.list[2][q];
+        const int pt = a.bins.list[2][q];
         const int64_t s = a.v.obs_start[pt];
         const int n = a.v.obs_start[pt + 1] - (int)s;
         const bool in_lds = n <= cap;

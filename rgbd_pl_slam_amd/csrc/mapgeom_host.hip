@@ -1,7 +1,6 @@
 // mapgeom_host.hip -- host side of the map geometry section of include/plf.h: argument checks and the launches of mapgeom_kernels.hip.  No handle:
 // the only state of a call is its scratch (three point lists and their counters), taken from the device's stream-ordered memory pool so that a
 // call on a caller's stream only enqueues.
-#include <algorithm>
 #include "plf_common.h"
 #include "map_common.h"
 
@@ -23,35 +22,22 @@ extern "C" int plf_map_update_normal_depth(const plf_map_geom_view *v, const flo
     if (max_distance && (!v->scale_factors || v->nlevels < 1)) return PLF_E_BADARG;
     if (device < 0) return PLF_E_BADARG;
     if (v->n_points == 0) return PLF_OK;
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) { (void)hipGetLastError(); return PLF_E_HIP; }
-    if (device >= ndev) return PLF_E_BADARG;
-    PLF_HIP_TRY(hipSetDevice(device));
+    PLF_TRY(plf_select_device(device));
     hipStream_t s = (hipStream_t)stream;
-    const size_t n = (size_t)v->n_points, bytes = (3 * n + 4) * sizeof(int32_t);
-    int32_t *scratch = nullptr;
-    bool pooled = true;
-    if (hipMallocAsync((void **)&scratch, bytes, s) != hipSuccess) {    // no stream-ordered allocator: a plain allocation, and the call waits for its work
-        (void)hipGetLastError();
-        pooled = false;
-        if (hipMalloc((void **)&scratch, bytes) != hipSuccess) { (void)hipGetLastError(); return PLF_E_NOMEM; }
-    }
+    const size_t n = (size_t)v->n_points;
+    PlfScratch scratch;
+    PLF_TRY(plf_scratch_acquire(scratch, map_bins_bytes(n), s));
     MapGeomArgs a;
     a.v = *v; a.world_pos = world_pos; a.normal = normal; a.min_distance = min_distance; a.max_distance = max_distance; a.map_rows = map_rows;
-    a.n_obs_used = n_obs_used;
-    a.list[0] = scratch; a.list[1] = scratch + n; a.list[2] = scratch + 2 * n; a.count = scratch + 3 * n;
+    a.n_obs_used = n_obs_used; a.bins = map_bins_at(scratch.p, n);
     int st = PLF_OK;
-    if (hipMemsetAsync(a.count, 0, 4 * sizeof(int32_t), s) != hipSuccess) st = PLF_E_HIP;
+    if (hipMemsetAsync(a.bins.count, 0, 4 * sizeof(int32_t), s) != hipSuccess) st = PLF_E_HIP;
     if (st == PLF_OK) {
-        // every kernel walks its list with a grid-stride loop: the grids are sized for the machine, not for counts the host does not have
-        const unsigned cap = 2048;
-        hipLaunchKernelGGL(k_mapgeom_bin, dim3((unsigned)std::min<size_t>((n + 255) / 256, cap)), dim3(256), 0, s, a);
-        hipLaunchKernelGGL(k_mapgeom_small, dim3((unsigned)std::min<size_t>((n + 15) / 16, cap)), dim3(256), 0, s, a);
-        hipLaunchKernelGGL(k_mapgeom_wave, dim3((unsigned)std::min<size_t>((n + 3) / 4, cap)), dim3(256), 0, s, a);
-        hipLaunchKernelGGL(k_mapgeom_block, dim3((unsigned)std::min<size_t>(n, 512)), dim3(1024), 0, s, a);
+        hipLaunchKernelGGL(k_mapgeom_bin, map_grid(n, 256), dim3(256), 0, s, a);
+        hipLaunchKernelGGL(k_mapgeom_small, map_grid(n, 16), dim3(256), 0, s, a);
+        hipLaunchKernelGGL(k_mapgeom_wave, map_grid(n, 4), dim3(256), 0, s, a);
+        hipLaunchKernelGGL(k_mapgeom_block, map_grid(n, 1, 512), dim3(1024), 0, s, a);
         if (hipGetLastError() != hipSuccess) st = PLF_E_HIP;
     }
-    if (pooled) { if (hipFreeAsync(scratch, s) != hipSuccess) { (void)hipGetLastError(); st = PLF_E_HIP; } }
-    else { if (hipStreamSynchronize(s) != hipSuccess) { (void)hipGetLastError(); st = PLF_E_HIP; } (void)hipFree(scratch); }
-    return st;
+    return plf_scratch_release(scratch, s, st);
 }

@@ -11,10 +11,6 @@
 #include "plf_common.h"
 #include "map_common.h"
 
-__device__ __forceinline__ int geom_lanes_below(unsigned long long mask)
-{
-    return (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(mask >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mask, 0u));
-}
 __device__ __forceinline__ float geom_readlane(float v, int l) { return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), l)); }
 __device__ __forceinline__ int64_t geom_row(const MapGeomArgs &a, int pt) { return a.v.point_id ? a.v.point_id[pt] : pt; }
 // mWorldPos of a row; for a map line the midpoint of its segment
@@ -84,15 +80,7 @@ __global__ void __launch_bounds__(256) k_mapgeom_bin(MapGeomArgs a)
             cls = skip ? 3 : n <= MAP_SMALL_MAX ? 0 : n <= MAP_WAVE_MAX ? 1 : 2;
             if (cls == 3) a.n_obs_used[p] = -1;
         }
-#pragma unroll
-        for (int c = 0; c < 3; c++) {
-            const unsigned long long mask = __ballot(cls == c);
-            if (!mask) continue;
-            int base = 0;
-            if (lane == 0) base = atomicAdd(&a.count[c], __popcll(mask));
-            base = __builtin_amdgcn_readfirstlane(base);
-            if (cls == c) a.list[c][base + geom_lanes_below(mask)] = (int)p;
-        }
+        map_bins_append(a.bins, cls, (int)p);
     }
 }
 
@@ -102,7 +90,7 @@ __global__ void __launch_bounds__(256) k_mapgeom_small(MapGeomArgs a)
 {
     __shared__ float4 s_t[256];
     const int t = threadIdx.x, g = t >> 4, i = t & 15;
-    const int cnt = a.count[0];
+    const int cnt = a.bins.count[0];
     for (int q0 = blockIdx.x * 16; q0 < cnt; q0 += gridDim.x * 16) {   // workgroup-uniform
         const int q = q0 + g;
         const bool act = q < cnt;
@@ -110,7 +98,7 @@ __global__ void __launch_bounds__(256) k_mapgeom_small(MapGeomArgs a)
         int64_t s = 0, row = 0;
         float p0 = 0.0f, p1 = 0.0f, p2 = 0.0f;
         if (act) {
-            pt = a.list[0][q]; s = a.v.obs_start[pt]; n = a.v.obs_start[pt + 1] - (int)s; row = geom_row(a, pt); ref = a.v.ref_kf[pt];
+            pt = a.bins.list[0][q]; s = a.v.obs_start[pt]; n = a.v.obs_start[pt + 1] - (int)s; row = geom_row(a, pt); ref = a.v.ref_kf[pt];
             geom_pos(a, row, p0, p1, p2);
         }
         float t0 = 0.0f, t1 = 0.0f, t2 = 0.0f;
@@ -135,9 +123,9 @@ __global__ void __launch_bounds__(256) k_mapgeom_small(MapGeomArgs a)
 __global__ void __launch_bounds__(256) k_mapgeom_wave(MapGeomArgs a)
 {
     const int lane = plf_lane(), w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const int cnt = a.count[1];
+    const int cnt = a.bins.count[1];
     for (int q = blockIdx.x * 4 + w; q < cnt; q += gridDim.x * 4) {   // wave-uniform
-        const int pt = a.list[1][q];
+        const int pt = a.bins.list[1][q];
         const int64_t s = a.v.obs_start[pt], row = geom_row(a, pt);
         const int n = a.v.obs_start[pt + 1] - (int)s, ref = a.v.ref_kf[pt];
         float p0, p1, p2;
@@ -169,9 +157,9 @@ __global__ void __launch_bounds__(1024) k_mapgeom_block(MapGeomArgs a)
     __shared__ float4 s_t[MAPGEOM_CHUNK];      // x, y, z, w != 0: the observation counts
     __shared__ int s_ref;
     const int lane = plf_lane(), w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const int cnt = a.count[2];
+    const int cnt = a.bins.count[2];
     for (int q = blockIdx.x; q < cnt; q += gridDim.x) {   // workgroup-uniform
-        const int pt = a.list[2][q];
+        const int pt = a.bins.list[2][q];
         const int64_t s = a.v.obs_start[pt], row = geom_row(a, pt);
         const int n = a.v.obs_start[pt + 1] - (int)s, ref = a.v.ref_kf[pt];
         float p0, p1, p2;

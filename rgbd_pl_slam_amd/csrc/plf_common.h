@@ -19,11 +19,18 @@
         }                                                                                             \
     } while (0)
 
+#define PLF_TRY(expr) do { const int _st = (expr); if (_st != PLF_OK) return _st; } while (0)   // a PLF_* status that is not PLF_OK ends the call
+
 static inline size_t plf_align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
 
 #ifdef __HIPCC__
 // ---- wave-level helpers (64 lanes)
 __device__ __forceinline__ int plf_lane() { return threadIdx.x & 63; }
+// set bits of a __ballot mask below this lane
+__device__ __forceinline__ int plf_lanes_below(unsigned long long mask)
+{
+    return (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(mask >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mask, 0u));
+}
 
 // one coordinate of a map line's midpoint: the point at which Frame::isInFrustum(MapLine*) gates distance and viewing angle (frame_kernels.hip) and at
 // which MapLine::UpdateAverageDir takes normal and depth (mapgeom_kernels.hip) -- one expression, so that both see the same bits
@@ -113,3 +120,44 @@ static inline void plf_order_end(PlfStreamOrder &o, hipStream_t s)
 }
 static inline void plf_order_free(PlfStreamOrder &o) { if (o.ev) (void)hipEventDestroy(o.ev); o.ev = nullptr; o.set = false; }
 struct PlfOrderGuard { PlfStreamOrder &o; hipStream_t s; ~PlfOrderGuard() { plf_order_end(o, s); } };
+
+// ---- host plumbing of the calls without a handle (map_host.hip, mapgeom_host.hip, covis_host.hip; the first also bow_host.hip)
+#define PLF_MAX_DEVICES 64
+// makes `device` current: PLF_E_HIP without a device to count, PLF_E_BADARG for one the machine does not have.  What a caller refuses before it gets
+// here (a negative device, one beyond PLF_MAX_DEVICES) and what it returns without looking at the device is the caller's, and differs between them.
+static inline int plf_select_device(int32_t device)
+{
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) { (void)hipGetLastError(); return PLF_E_HIP; }
+    if (device < 0 || device >= ndev) return PLF_E_BADARG;
+    PLF_HIP_TRY(hipSetDevice(device));
+    return PLF_OK;
+}
+
+// the scratch of one call on stream s, from the device's stream-ordered pool; without such an allocator a plain allocation, and the release waits for the
+// call's work.  Release after the launches are checked: it returns the call's status `st`, or PLF_E_HIP where the release itself failed.
+struct PlfScratch { void *p; bool pooled; };
+static inline int plf_scratch_acquire(PlfScratch &m, size_t bytes, hipStream_t s)
+{
+    m.p = nullptr; m.pooled = true;
+    if (hipMallocAsync(&m.p, bytes, s) == hipSuccess) return PLF_OK;
+    (void)hipGetLastError();
+    m.pooled = false;
+    if (hipMalloc(&m.p, bytes) == hipSuccess) return PLF_OK;
+    (void)hipGetLastError();
+    return PLF_E_NOMEM;
+}
+static inline int plf_scratch_release(PlfScratch &m, hipStream_t s, int st)
+{
+    if (m.pooled) { if (hipFreeAsync(m.p, s) != hipSuccess) { (void)hipGetLastError(); st = PLF_E_HIP; } }
+    else { if (hipStreamSynchronize(s) != hipSuccess) { (void)hipGetLastError(); st = PLF_E_HIP; } (void)hipFree(m.p); }
+    return st;
+}
+
+// the dynamic-LDS limit of one kernel, raised once per device (idempotent, so a race only repeats it); device < PLF_MAX_DEVICES
+struct PlfLdsOnce { const void *fn; int bytes; bool ready[PLF_MAX_DEVICES]; };
+static inline int plf_lds_once(PlfLdsOnce &o, int device)
+{
+    if (!o.ready[device]) { PLF_HIP_TRY(hipFuncSetAttribute(o.fn, hipFuncAttributeMaxDynamicSharedMemorySize, o.bytes)); o.ready[device] = true; }
+    return PLF_OK;
+}

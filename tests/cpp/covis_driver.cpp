@@ -1,5 +1,5 @@
 // covis_driver.cpp -- ORB_SLAM2_PLF::CovisibilityGraph, the adapter of include/plf.hpp under PLF_WITH_OPENCV, over the mock KeyFrame / MapPoint / Frame of
-// tests/mock/ORB_SLAM2/mock_covis.h; compiled and run by tests/test_gpu_covis_cpp.py.
+// tests/mock/ORB_SLAM2/mock_covis.h; compiled and run by tests/test_gpu_cpp_drivers.py.
 // argv[1]: a directory with scenario.txt; writes out.txt, one line per query.  scenario.txt, one command per line:
 //   pool N | kf ID POS BAD (keyframe ID lives at pool[POS]: addresses ascend with POS, and the address is the map key) | point PID BAD N KFID* |
 //   row KFID N PID* (-1 = null) | frame N PID* | update TH | connected KFID | best KFID N | byweight KFID W | weight KFID KFID | votes FRAME

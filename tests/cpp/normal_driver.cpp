@@ -1,5 +1,5 @@
 // normal_driver.cpp -- ORB_SLAM2_PLF::UpdateNormalAndDepth, the adapter of include/plf.hpp under PLF_WITH_OPENCV, over the mock KeyFrame / MapPoint of
-// tests/mock/ORB_SLAM2/mock_normal.h; compiled by tests/test_normal_ref.py and run by tests/test_gpu_normal_cpp.py.
+// tests/mock/ORB_SLAM2/mock_normal.h; compiled by tests/test_normal_ref.py and run by tests/test_gpu_cpp_drivers.py.
 // argv[1]: a directory with scenario.txt; writes out.txt, one line per point.  scenario.txt (floats as hex bit patterns), one command per line:
 //   pool N | scale N F* | kf POS X Y Z N OCTAVE* (the keyframe lives at pool[POS]: addresses ascend with POS, and the address is the map key) |
 //   point X Y Z BAD REF N (POS IDX)* | run

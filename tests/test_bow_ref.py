@@ -9,6 +9,7 @@ import pytest
 
 import bowref
 from conftest import gpu_available
+from cppbuild import build_driver
 
 GOLD = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 
@@ -149,11 +150,7 @@ def test_cpp_vocabulary_mirror_compiles_and_never_falls_back(tmp_path):
     """plf::ORBVocabulary with the reference's transform signature over tests/mock/ (cv::Mat, DBoW2::BowVector / FeatureVector): built here; without a GPU
     loading a good file must throw plf::Error(PLF_E_HIP), a missing file just returns false (tests/test_gpu_bow.py runs the driver on the GPU)"""
     import subprocess
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    lib = os.path.join(root, "rgbd_pl_slam_amd", "libplf_hip.so")
-    exe = tmp_path / "bow_driver"
-    subprocess.check_call(["g++", "-std=c++17", "-Wall", "-Werror", "-DPLF_WITH_OPENCV", "-I", os.path.join(root, "include"), "-I", os.path.join(root, "tests", "mock"),
-                           os.path.join(root, "tests", "cpp", "bow_driver.cpp"), "-o", str(exe), lib, "-Wl,-rpath," + os.path.dirname(lib), "-Wl,-rpath,/opt/rocm/lib"])
+    exe = build_driver("bow_driver", tmp_path, "-Wall", "-Werror")
     voc = bowref.make_vocab(1, 3, 2)
     bowref.save_text(voc, str(tmp_path / "voc.txt"))
     bowref.make_descriptors(voc, 1, 10).tofile(str(tmp_path / "desc1.u8")); bowref.make_descriptors(voc, 2, 10).tofile(str(tmp_path / "desc2.u8"))

@@ -7,6 +7,7 @@ import os
 import numpy as np
 
 import covisref
+from cppbuild import build_driver
 
 GOLD = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 
@@ -141,13 +142,7 @@ def test_symbols_are_exported_and_reject_bad_arguments_without_a_device():
 
 
 def build_covis_driver(tmp_path, flags=("-Werror",)):
-    import subprocess
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    lib = os.path.join(root, "rgbd_pl_slam_amd", "libplf_hip.so")
-    exe = tmp_path / "covis_driver"
-    subprocess.check_call(["g++", "-std=c++17", "-Wall", *flags, "-DPLF_WITH_OPENCV", "-I", os.path.join(root, "include"), "-I", os.path.join(root, "tests", "mock"),
-                           os.path.join(root, "tests", "cpp", "covis_driver.cpp"), "-o", str(exe), lib, "-Wl,-rpath," + os.path.dirname(lib), "-Wl,-rpath,/opt/rocm/lib"])
-    return exe
+    return build_driver("covis_driver", tmp_path, "-Wall", *flags)
 
 
 def driver_scenario(fx, path):
@@ -187,7 +182,7 @@ def driver_scenario(fx, path):
 
 def test_cpp_covisibility_mirror_compiles_and_never_falls_back(tmp_path):
     """ORB_SLAM2_PLF::CovisibilityGraph over tests/mock/ORB_SLAM2/mock_covis.h: built here with -Werror; without a GPU the driver must stop with
-    plf::Error(PLF_E_HIP) at its first device allocation (tests/test_gpu_covis_cpp.py runs it on the GPU against the fixture)"""
+    plf::Error(PLF_E_HIP) at its first device allocation (tests/test_gpu_cpp_drivers.py runs it on the GPU against the fixture)"""
     import subprocess
     from conftest import gpu_available
     exe = build_covis_driver(tmp_path)

@@ -11,6 +11,7 @@ import pytest
 import bowref
 import orc
 from conftest import gpu_available
+from cppbuild import build_driver
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -265,10 +266,7 @@ def test_extract_transform_search_by_bow_end_to_end():
 def test_cpp_mirror(tmp_path):
     """plf::ORBVocabulary through its reference-signature overload (std::vector<cv::Mat>, DBoW2::BowVector, DBoW2::FeatureVector, levelsup): tests/cpp/bow_driver.cpp
     built against tests/mock/ and run"""
-    lib = os.path.join(ROOT, "rgbd_pl_slam_amd", "libplf_hip.so")
-    exe = tmp_path / "bow_driver"
-    subprocess.check_call(["g++", "-std=c++17", "-O1", "-g", "-Wall", "-DPLF_WITH_OPENCV", "-I", os.path.join(ROOT, "include"), "-I", os.path.join(ROOT, "tests", "mock"),
-                           os.path.join(ROOT, "tests", "cpp", "bow_driver.cpp"), "-o", str(exe), lib, "-Wl,-rpath," + os.path.dirname(lib), "-Wl,-rpath,/opt/rocm/lib"])
+    exe = build_driver("bow_driver", tmp_path, "-O1", "-g", "-Wall")
     ref = bowref.make_vocab(91, 10, 5, bowref.TF_IDF, bowref.L1_NORM, zero_share=0.05, dup_share=0.1, full=30)
     bowref.save_text(ref, str(tmp_path / "voc.txt"), trailing_blank_lines=1)
     d1 = bowref.make_descriptors(ref, 1, 900); d2 = np.concatenate([d1[:400], bowref.make_descriptors(ref, 2, 300)])

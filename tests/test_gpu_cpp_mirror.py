@@ -11,9 +11,9 @@ import pytest
 import matchgen
 import orc
 from conftest import gpu_available
+from cppbuild import build_driver
 
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 def test_full_path_through_the_cpp_adapters(tmp_path):
@@ -21,11 +21,7 @@ def test_full_path_through_the_cpp_adapters(tmp_path):
         pytest.fail("no GPU visible: the -m gpu tests need a real MI355X")
     from rgbd_pl_slam_amd._lib import KP_DTYPE, KL_DTYPE
     from rgbd_pl_slam_amd.synth import synth_frame
-    lib = os.path.join(ROOT, "rgbd_pl_slam_amd", "libplf_hip.so")
-    exe = tmp_path / "mirror_driver"
-    subprocess.check_call(["g++", "-std=c++17", "-O1", "-g", "-rdynamic", "-DPLF_WITH_OPENCV", "-I", os.path.join(ROOT, "include"), "-I", os.path.join(ROOT, "tests", "mock"),
-                           os.path.join(ROOT, "tests", "cpp", "mirror_driver.cpp"), "-o", str(exe), lib, "-Wl,-rpath," + os.path.dirname(lib),
-                           "-Wl,-rpath,/opt/rocm/lib"])
+    exe = build_driver("mirror_driver", tmp_path, "-O1", "-g", "-rdynamic")
     w, h, nfeat, nlines = 640, 480, 1000, 100
     img = synth_frame(77, w, h)
     ro = orc.orb_extract(img, nfeatures=nfeat); rl = orc.line_extract(img, nlines)

@@ -9,6 +9,7 @@ import pytest
 import mapref
 import orc
 from conftest import gpu_available
+from cppbuild import build_driver
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -266,10 +267,7 @@ def test_line_side_mirror_names():
 
 
 def test_cpp_driver(tmp_path):
-    lib = os.path.join(ROOT, "rgbd_pl_slam_amd", "libplf_hip.so")
-    exe = tmp_path / "mappoint_driver"
-    subprocess.check_call(["g++", "-std=c++17", "-O1", "-g", "-Wall", "-DPLF_WITH_OPENCV", "-I", os.path.join(ROOT, "include"), "-I", os.path.join(ROOT, "tests", "mock"),
-                           os.path.join(ROOT, "tests", "cpp", "mappoint_driver.cpp"), "-o", str(exe), lib, "-Wl,-rpath," + os.path.dirname(lib), "-Wl,-rpath,/opt/rocm/lib"])
+    exe = build_driver("mappoint_driver", tmp_path, "-O1", "-g", "-Wall")
     rng = np.random.default_rng(31)
     counts = np.concatenate([rng.integers(0, 12, 60), [16, 17, 40, 64]])
     start, desc, _ = mapref.make_points(32, counts)

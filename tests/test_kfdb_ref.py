@@ -8,6 +8,7 @@ import numpy as np
 
 import bowref
 import kfdbref
+from cppbuild import build_driver
 from kfdbref import random_bows
 
 GOLD = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
@@ -135,12 +136,7 @@ def test_symbols_are_exported_and_reject_bad_arguments_without_a_device():
 
 
 def build_kfdb_driver(tmp_path, flags=("-Werror",)):
-    import subprocess
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    lib = os.path.join(root, "rgbd_pl_slam_amd", "libplf_hip.so")
-    exe = tmp_path / "kfdb_driver"
-    subprocess.check_call(["g++", "-std=c++17", "-Wall", *flags, "-DPLF_WITH_OPENCV", "-I", os.path.join(root, "include"), "-I", os.path.join(root, "tests", "mock"),
-                           os.path.join(root, "tests", "cpp", "kfdb_driver.cpp"), "-o", str(exe), lib, "-Wl,-rpath," + os.path.dirname(lib), "-Wl,-rpath,/opt/rocm/lib"])
+    exe = build_driver("kfdb_driver", tmp_path, "-Wall", *flags)
     voc = bowref.make_vocab(2, 10, 2)
     bowref.save_text(voc, str(tmp_path / "voc.txt"))
     return exe, voc

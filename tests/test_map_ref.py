@@ -8,6 +8,7 @@ import numpy as np
 
 import mapref
 from conftest import gpu_available
+from cppbuild import build_driver
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 GOLD = os.path.join(ROOT, "tests", "golden")
@@ -119,10 +120,7 @@ def test_misuse_is_refused_before_any_device_work():
 
 def test_cpp_adapter_compiles_against_the_mocks_and_never_falls_back(tmp_path):
     """plf::MapPoint / plf::MapLine and the ORB_SLAM2_PLF adapter over tests/mock/ORB_SLAM2/mock_map.h, driven by tests/cpp/mappoint_driver.cpp"""
-    lib = os.path.join(ROOT, "rgbd_pl_slam_amd", "libplf_hip.so")
-    exe = tmp_path / "mappoint_driver"
-    subprocess.check_call(["g++", "-std=c++17", "-Wall", "-Werror", "-DPLF_WITH_OPENCV", "-I", os.path.join(ROOT, "include"), "-I", os.path.join(ROOT, "tests", "mock"),
-                           os.path.join(ROOT, "tests", "cpp", "mappoint_driver.cpp"), "-o", str(exe), lib, "-Wl,-rpath," + os.path.dirname(lib), "-Wl,-rpath,/opt/rocm/lib"])
+    exe = build_driver("mappoint_driver", tmp_path, "-Wall", "-Werror")
     start, desc, _ = mapref.make_points(5, [3, 0, 20, 1])
     mapref.write_driver_input(tmp_path, start, desc, n_kf=32, seed=5)
     run = subprocess.run([str(exe), str(tmp_path)], text=True, capture_output=True)

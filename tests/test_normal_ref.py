@@ -10,6 +10,7 @@ import numpy as np
 
 import normref as R
 from conftest import gpu_available
+from cppbuild import build_driver
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 FIXTURE = os.path.join(ROOT, "tests", "golden", "normal_depth_tiny.json")
@@ -17,11 +18,7 @@ F = np.float32
 
 
 def build_normal_driver(tmp_path, flags=("-Werror",)):
-    lib = os.path.join(ROOT, "rgbd_pl_slam_amd", "libplf_hip.so")
-    exe = tmp_path / "normal_driver"
-    subprocess.check_call(["g++", "-std=c++17", "-Wall", *flags, "-DPLF_WITH_OPENCV", "-I", os.path.join(ROOT, "include"), "-I", os.path.join(ROOT, "tests", "mock"),
-                           os.path.join(ROOT, "tests", "cpp", "normal_driver.cpp"), "-o", str(exe), lib, "-Wl,-rpath," + os.path.dirname(lib), "-Wl,-rpath,/opt/rocm/lib"])
-    return exe
+    return build_driver("normal_driver", tmp_path, "-Wall", *flags)
 
 
 def driver_scenario(fx, path):

@@ -7,8 +7,6 @@ The per-kernel split comes from a kernel trace taken in a run of its own (tracin
     python tools/bench_bow.py --kernel-stats DIR
 A measurement needs the GPU: without one this tool fails, it does not fall back."""
 import argparse
-import glob
-import csv
 import json
 import os
 import sys
@@ -16,19 +14,10 @@ import sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
+sys.path.insert(0, os.path.join(ROOT, "tools"))
+import benchlib  # noqa: E402
 OUT = os.path.join(ROOT, "profiles", "bow_transform.json")
 EXTRACT_MS_SAME_BATCH = 163.0   # BENCH_r06.json: ORB + LSD extraction step of 8192 frames
-
-
-def kernel_split(d):
-    rows = {}
-    for path in glob.glob(os.path.join(d, "**", "*kernel_stats.csv"), recursive=True):
-        for r in csv.DictReader(open(path)):
-            name = r["Name"].split("(")[0]
-            if name.startswith("k_bow_"):
-                c, t = rows.get(name, (0, 0))
-                rows[name] = (c + int(r["Calls"]), t + int(r["TotalDurationNs"]))
-    return {k: {"calls": c, "avg_ms": t / c / 1e6} for k, (c, t) in rows.items() if c}
 
 
 def main():
@@ -42,18 +31,14 @@ def main():
     ap.add_argument("--kernel-stats", default=None, help="directory of a rocprofv3 --kernel-trace --stats run of this tool: merge the per-kernel split")
     a = ap.parse_args()
     if a.kernel_stats:
-        res = json.load(open(OUT))
-        split = kernel_split(a.kernel_stats)
-        if not split:
-            sys.exit("no k_bow_* rows under " + a.kernel_stats)
-        res["per_kernel_ms"] = {k: round(v["avg_ms"], 4) for k, v in split.items()}
-        d = res["per_kernel_ms"].get("k_bow_descend16") or res["per_kernel_ms"].get("k_bow_descend32")
-        if d:
-            res["descent_algorithmic_GBps"] = round(res["descent_algorithmic_bytes"] / (d * 1e-3) / 1e9, 1)
-            res["note"] = ("descent_algorithmic_GBps counts the L x k x 32 B of child descriptors each feature compares against; they are served from cache "
-                           "(the 35 MB node table is read by every frame), so the rate may exceed the HBM peak and is not an HBM roofline fraction")
-        json.dump(res, open(OUT, "w"), indent=1)
-        print(json.dumps(res))
+        def put(res, split):
+            res["per_kernel_ms"] = {k: v["avg_ms"] for k, v in split.items()}
+            d = res["per_kernel_ms"].get("k_bow_descend16") or res["per_kernel_ms"].get("k_bow_descend32")
+            if d:
+                res["descent_algorithmic_GBps"] = round(res["descent_algorithmic_bytes"] / (d * 1e-3) / 1e9, 1)
+                res["note"] = ("descent_algorithmic_GBps counts the L x k x 32 B of child descriptors each feature compares against; they are served from cache "
+                               "(the 35 MB node table is read by every frame), so the rate may exceed the HBM peak and is not an HBM roofline fraction")
+        print(json.dumps(benchlib.merge_kernel_stats(OUT, a.kernel_stats, "k_bow_", put)[0]))
         return
     import numpy as np
     import torch
@@ -70,16 +55,7 @@ def main():
     nd = torch.full((F,), n, dtype=torch.int32, device="cuda")
     torch.cuda.synchronize()
     st = torch.cuda.Stream()          # the events and the transform share this stream
-    for _ in range(a.warmup):
-        out = V.transform(desc, nd, a.levelsup, stream=st.cuda_stream)
-    torch.cuda.synchronize()
-    ms = []
-    for _ in range(a.calls):
-        e0 = torch.cuda.Event(enable_timing=True); e1 = torch.cuda.Event(enable_timing=True)
-        e0.record(st); out = V.transform(desc, nd, a.levelsup, stream=st.cuda_stream); e1.record(st)
-        e1.synchronize()
-        ms.append(e0.elapsed_time(e1))
-    torch.cuda.synchronize()
+    ms, out = benchlib.event_times(lambda: V.transform(desc, nd, a.levelsup, stream=st.cuda_stream), st, a.warmup, a.calls)
     # a spot check that what was timed is the transform: frame 5 against the restatement
     bow, _ = bowref.transform(ref, base[5], a.levelsup)
     nw = int(out["n_words"][5])

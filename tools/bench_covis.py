@@ -12,8 +12,6 @@ The per-kernel split comes from a kernel trace taken in a run of its own:
     python tools/bench_covis.py --kernel-stats DIR
 A measurement needs the GPU: without one this tool fails, it does not fall back."""
 import argparse
-import csv
-import glob
 import json
 import os
 import subprocess
@@ -23,6 +21,7 @@ import tempfile
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tools"))
+import benchlib  # noqa: E402
 OUT = os.path.join(ROOT, "profiles", "covis.json")
 N_KF, N_POINTS, N_FRAMES, FRAME_POINTS = 10000, 500000, 8192, 300
 
@@ -48,21 +47,9 @@ def make_map(rng):
     return start.astype(np.int32), obs_kf, row_start.astype(np.int32), row_point
 
 
-def kernel_split(d):
-    rows = {}
-    for path in glob.glob(os.path.join(d, "**", "*kernel_stats.csv"), recursive=True):
-        for r in csv.DictReader(open(path)):
-            name = r["Name"].split("(")[0]
-            if name.startswith("k_covis_"):
-                c, t = rows.get(name, (0, 0))
-                rows[name] = (c + int(r["Calls"]), t + int(r["TotalDurationNs"]))
-    return {k: {"calls": c, "avg_ms": round(t / c / 1e6, 4)} for k, (c, t) in rows.items() if c}
-
-
 def cpu_loop_ms(arrays, mode, th, reps):
     with tempfile.TemporaryDirectory() as d:
-        exe = os.path.join(d, "covis_cpu")
-        subprocess.check_call(["g++", "-O3", "-march=native", "-std=c++17", os.path.join(ROOT, "tools", "covis_cpu.cpp"), "-o", exe])
+        exe = benchlib.build_cpp("covis_cpu.cpp", d, "-O3", "-march=native")
         paths = []
         for i, a in enumerate(arrays):
             paths.append(os.path.join(d, "a%d.i32" % i)); a.tofile(paths[-1])
@@ -80,13 +67,7 @@ def main():
     ap.add_argument("--kernel-stats", default=None, help="directory of a rocprofv3 --kernel-trace --stats run of this tool: merge the per-kernel split")
     a = ap.parse_args()
     if a.kernel_stats:
-        res = json.load(open(OUT))
-        split = kernel_split(a.kernel_stats)
-        if not split:
-            sys.exit("no k_covis_* rows under " + a.kernel_stats)
-        res["per_kernel_ms_traced_both_shapes"] = split
-        json.dump(res, open(OUT, "w"), indent=1)
-        print(json.dumps(split))
+        print(json.dumps(benchlib.merge_kernel_stats(OUT, a.kernel_stats, "k_covis_", lambda res, split: res.update(per_kernel_ms_traced_both_shapes=split))[1]))
         return
     import numpy as np
     import torch
@@ -114,22 +95,17 @@ def main():
                       cpu=((frame_start, frame_point.reshape(-1), row_self, obs_start, obs_kf), 1, 1)),
     }
     for name, s in shapes.items():
-        out = None
-        for _ in range(a.warmup):
-            out = s["run"](out)
-        torch.cuda.synchronize()
-        ms = []
-        for _ in range(a.calls):
-            e0 = torch.cuda.Event(enable_timing=True); e1 = torch.cuda.Event(enable_timing=True)
-            e0.record(st); s["run"](out); e1.record(st)
-            e1.synchronize()
-            ms.append(e0.elapsed_time(e1))
-        torch.cuda.synchronize()
+        box = [None]                                                # the output arrays of the first call serve the later ones
+
+        def run():
+            box[0] = s["run"](box[0])
+            return box[0]
+        ms_gpu, out = benchlib.median_ms(run, st, a.warmup, a.calls)
         n_conn, max_kf, max_w = out.n_conn.cpu().numpy().astype(np.int64), out.max_kf.cpu().numpy().astype(np.int64), out.max_w.cpu().numpy().astype(np.int64)
         live = n_conn > 0
         check = int(n_conn.sum() + (max_kf[live] + 1).sum() + max_w[live].sum())
         row = {"rows": s["rows"], "increments": s["increments"], "stride": s["stride"], "max_n_conn": int(n_conn.max()),
-               "ms_gpu": {"median": round(float(np.median(ms)), 4), "min": round(min(ms), 4), "max": round(max(ms), 4)}}
+               "ms_gpu": ms_gpu}
         if name == "graph":
             n_ord = out.n_ord.cpu().numpy().astype(np.int64)
             check += int(n_ord.sum() + (out.ord_kf[:, 0].cpu().numpy().astype(np.int64)[live] + 1).sum())

@@ -16,8 +16,6 @@ The per-kernel split comes from a kernel trace taken in a run of its own, of the
     python tools/bench_distinct.py --kernel-stats DIR --only global
 A measurement needs the GPU: without one this tool fails, it does not fall back."""
 import argparse
-import csv
-import glob
 import json
 import os
 import subprocess
@@ -27,6 +25,8 @@ import tempfile
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
+sys.path.insert(0, os.path.join(ROOT, "tools"))
+import benchlib  # noqa: E402
 OUT = os.path.join(ROOT, "profiles", "distinct_descriptors.json")
 SHAPES = ("local", "global", "worst", "small", "medium", "large")
 
@@ -48,21 +48,9 @@ def counts_of(shape, rng):
     return c
 
 
-def kernel_split(d):
-    rows = {}
-    for path in glob.glob(os.path.join(d, "**", "*kernel_stats.csv"), recursive=True):
-        for r in csv.DictReader(open(path)):
-            name = r["Name"].split("(")[0]
-            if name.startswith("k_map_"):
-                c, t = rows.get(name, (0, 0))
-                rows[name] = (c + int(r["Calls"]), t + int(r["TotalDurationNs"]))
-    return {k: {"calls": c, "avg_ms": round(t / c / 1e6, 4)} for k, (c, t) in rows.items() if c}
-
-
 def cpu_loop_ms(start, desc, reps):
     with tempfile.TemporaryDirectory() as d:
-        exe = os.path.join(d, "distinct_cpu")
-        subprocess.check_call(["g++", "-O3", "-march=native", "-std=c++17", os.path.join(ROOT, "tools", "distinct_cpu.cpp"), "-o", exe])
+        exe = benchlib.build_cpp("distinct_cpu.cpp", d, "-O3", "-march=native")
         start.tofile(os.path.join(d, "s.i32")); desc.tofile(os.path.join(d, "d.u8"))
         out = subprocess.check_output([exe, os.path.join(d, "s.i32"), os.path.join(d, "d.u8"), str(reps)], text=True).split()
     return float(out[1]), int(out[3])
@@ -79,13 +67,9 @@ def main():
     ap.add_argument("--kernel-stats", default=None, help="directory of a rocprofv3 --kernel-trace --stats run of this tool with --only SHAPE: merge the per-kernel split")
     a = ap.parse_args()
     if a.kernel_stats:
-        res = json.load(open(OUT))
-        split = kernel_split(a.kernel_stats)
-        if not split or not a.only:
-            sys.exit("no k_map_* rows under " + a.kernel_stats + " (or --only missing)")
-        res["shapes"][a.only]["per_kernel_ms_traced"] = split
-        json.dump(res, open(OUT, "w"), indent=1)
-        print(json.dumps(split))
+        if not a.only:
+            sys.exit("--kernel-stats needs --only SHAPE")
+        print(json.dumps(benchlib.merge_kernel_stats(OUT, a.kernel_stats, "k_map_", lambda res, split: res["shapes"][a.only].update(per_kernel_ms_traced=split))[1]))
         return
     import numpy as np
     import torch
@@ -106,18 +90,8 @@ def main():
         results = {}
         for mode in (("auto", "naive") if a.mode == "both" else (a.mode,)):
             os.environ["PLF_MAP_NAIVE"] = "1" if mode == "naive" else "0"
-            for _ in range(a.warmup):
-                bo, bm = distinctive_descriptors(ds, md, obs_desc=dd, stream=st.cuda_stream)
-            torch.cuda.synchronize()
-            ms = []
-            for _ in range(a.calls):
-                e0 = torch.cuda.Event(enable_timing=True); e1 = torch.cuda.Event(enable_timing=True)
-                e0.record(st); bo, bm = distinctive_descriptors(ds, md, obs_desc=dd, stream=st.cuda_stream); e1.record(st)
-                e1.synchronize()
-                ms.append(e0.elapsed_time(e1))
-            torch.cuda.synchronize()
+            row["ms_" + mode], (bo, bm) = benchlib.median_ms(lambda: distinctive_descriptors(ds, md, obs_desc=dd, stream=st.cuda_stream), st, a.warmup, a.calls)
             results[mode] = (bo.cpu().numpy(), bm.cpu().numpy())
-            row["ms_" + mode] = {"median": round(float(np.median(ms)), 4), "min": round(min(ms), 4), "max": round(max(ms), 4)}
         os.environ["PLF_MAP_NAIVE"] = "0"
         got = results.get("auto") or results["naive"]
         # a spot check that what was timed is the rule: the first 300 points against the restatement

@@ -11,8 +11,6 @@ The per-kernel split comes from a kernel trace taken in a run of its own:
     python tools/bench_kfdb.py --kernel-stats DIR
 A measurement needs the GPU: without one this tool fails, it does not fall back."""
 import argparse
-import csv
-import glob
 import json
 import os
 import subprocess
@@ -23,19 +21,10 @@ import time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
+sys.path.insert(0, os.path.join(ROOT, "tools"))
+import benchlib  # noqa: E402
 OUT = os.path.join(ROOT, "profiles", "kfdb.json")
 NEIGHBOUR_STAGES_MS = {"plf_bow_transform_batch, 8192 frames (README)": 2.37}
-
-
-def kernel_split(d):
-    rows = {}
-    for path in glob.glob(os.path.join(d, "**", "*kernel_stats.csv"), recursive=True):
-        for r in csv.DictReader(open(path)):
-            name = r["Name"].split("(")[0]
-            if name.startswith("k_kfdb_"):
-                c, t = rows.get(name, (0, 0))
-                rows[name] = (c + int(r["Calls"]), t + int(r["TotalDurationNs"]))
-    return {k: {"calls": c, "avg_ms": t / c / 1e6} for k, (c, t) in rows.items() if c}
 
 
 def main():
@@ -50,13 +39,8 @@ def main():
     ap.add_argument("--kernel-stats", default=None)
     a = ap.parse_args()
     if a.kernel_stats:
-        res = json.load(open(OUT))
-        split = kernel_split(a.kernel_stats)
-        if not split:
-            sys.exit("no k_kfdb_* rows under " + a.kernel_stats)
-        res["per_kernel_avg_ms"] = {k: round(v["avg_ms"], 4) for k, v in split.items()}
-        json.dump(res, open(OUT, "w"), indent=1)
-        print(json.dumps(res))
+        put = lambda res, split: res.update(per_kernel_avg_ms={k: v["avg_ms"] for k, v in split.items()})
+        print(json.dumps(benchlib.merge_kernel_stats(OUT, a.kernel_stats, "k_kfdb_", put)[0]))
         return
     import numpy as np
     import torch
@@ -104,20 +88,11 @@ def main():
            "mean_sharing_keyframes": float(g_stats[:, 0].mean()), "mean_scored_keyframes": float(g_stats[:, 2].mean()), "mean_candidates": float(g_n.mean())}
     for QQ in (1, Q):
         sub = {k: v[:QQ].contiguous() for k, v in qs.items()}
-        for _ in range(a.warmup):
-            db.detect_relocalization_candidates(sub, (covis_start, covis_slot), MAXC, stream=st.cuda_stream)
-        torch.cuda.synchronize()
-        ms = []
-        for _ in range(a.calls):
-            e0 = torch.cuda.Event(enable_timing=True); e1 = torch.cuda.Event(enable_timing=True)
-            e0.record(st); db.detect_relocalization_candidates(sub, (covis_start, covis_slot), MAXC, stream=st.cuda_stream); e1.record(st)
-            e1.synchronize()
-            ms.append(e0.elapsed_time(e1))
-        res["gpu_ms_Q%d" % QQ] = {"median": round(float(np.median(ms)), 4), "min": round(min(ms), 4), "max": round(max(ms), 4)}
+        res["gpu_ms_Q%d" % QQ] = benchlib.median_ms(lambda: db.detect_relocalization_candidates(sub, (covis_start, covis_slot), MAXC, stream=st.cuda_stream),
+                                                    st, a.warmup, a.calls)[0]
     if not a.no_cpu:
         with tempfile.TemporaryDirectory() as td:
-            exe = os.path.join(td, "kfdb_cpu")
-            subprocess.check_call(["g++", "-O3", "-march=native", "-std=c++17", os.path.join(ROOT, "tools", "kfdb_cpu.cpp"), "-o", exe])
+            exe = benchlib.build_cpp("kfdb_cpu.cpp", td, "-O3", "-march=native")
             open(os.path.join(td, "meta.txt"), "w").write("%d %d %d %d %d %d %d\n" % (S, n, Q, n, ref.n_words, 10, MAXC))
             for name, t in (("kf_n.i32", kf["n_words"]), ("kf_id.u32", kf["word_id"]), ("kf_val.f64", kf["word_val"]), ("q_n.i32", qs["n_words"]),
                             ("q_id.u32", qs["word_id"]), ("q_val.f64", qs["word_val"]), ("covis_start.i32", covis_start), ("covis_slot.i32", covis_slot)):

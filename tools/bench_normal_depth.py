@@ -11,31 +11,19 @@ The per-kernel split comes from a kernel trace taken in a run of its own:
     python tools/bench_normal_depth.py --kernel-stats DIR --only global
 A measurement needs the GPU: without one this tool fails, it does not fall back."""
 import argparse
-import csv
-import glob
 import json
 import os
 import pathlib
-import subprocess
 import sys
 import tempfile
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
+sys.path.insert(0, os.path.join(ROOT, "tools"))
+import benchlib  # noqa: E402
 OUT = os.path.join(ROOT, "profiles", "normal_depth.json")
 SHAPES = {"local": (5000, 600), "global": (500000, 10000)}
-
-
-def kernel_split(d):
-    rows = {}
-    for path in glob.glob(os.path.join(d, "**", "*kernel_stats.csv"), recursive=True):
-        for r in csv.DictReader(open(path)):
-            name = r["Name"].split("(")[0]
-            if name.startswith("k_mapgeom_"):
-                c, t = rows.get(name, (0, 0))
-                rows[name] = (c + int(r["Calls"]), t + int(r["TotalDurationNs"]))
-    return {k: {"calls": c, "avg_ms": round(t / c / 1e6, 4)} for k, (c, t) in rows.items() if c}
 
 
 def main():
@@ -48,13 +36,9 @@ def main():
     ap.add_argument("--kernel-stats", default=None, help="directory of a rocprofv3 --kernel-trace --stats run of this tool with --only SHAPE: merge the per-kernel split")
     a = ap.parse_args()
     if a.kernel_stats:
-        res = json.load(open(OUT))
-        split = kernel_split(a.kernel_stats)
-        if not split or not a.only:
-            sys.exit("no k_mapgeom_* rows under " + a.kernel_stats + " (or --only missing)")
-        res["shapes"][a.only]["per_kernel_ms_traced"] = split
-        json.dump(res, open(OUT, "w"), indent=1)
-        print(json.dumps(split))
+        if not a.only:
+            sys.exit("--kernel-stats needs --only SHAPE")
+        print(json.dumps(benchlib.merge_kernel_stats(OUT, a.kernel_stats, "k_mapgeom_", lambda res, split: res["shapes"][a.only].update(per_kernel_ms_traced=split))[1]))
         return
     import numpy as np
     import torch
@@ -80,18 +64,9 @@ def main():
             nv, mn, mx = fill[:, :3].contiguous(), fill[:, 3].contiguous(), fill[:, 4].contiguous()
             call = lambda: update_normal_and_depth(d["obs_start"], d["obs_kf"], d["kf_ow"], d["ref_kf"], d["world_pos"], nv, mn, mx, ref_level=d["level"],
                                                    scale_factors=dsf, stream=st.cuda_stream)
-            for _ in range(a.warmup):
-                used = call()
-            torch.cuda.synchronize()
-            ms = []
-            for _ in range(a.calls):
-                e0 = torch.cuda.Event(enable_timing=True); e1 = torch.cuda.Event(enable_timing=True)
-                e0.record(st); used = call(); e1.record(st)
-                e1.synchronize()
-                ms.append(e0.elapsed_time(e1))
-            torch.cuda.synchronize()
+            ms_device, used = benchlib.median_ms(call, st, a.warmup, a.calls)
             row = {"points": int(n), "observations": int(counts.sum()), "keyframes": n_kf, "mean_count": round(float(counts.mean()), 2), "max_count": int(counts.max()),
-                   "ms_device": {"median": round(float(np.median(ms)), 4), "min": round(min(ms), 4), "max": round(max(ms), 4)}}
+                   "ms_device": ms_device}
             if exe is not None:
                 c = run_cpu_loop(exe, tmp, m, sf, reps=3)
                 same = (np.array_equal(c[3], used.cpu().numpy()) and R.same_bits(c[0], nv.cpu().numpy()) and R.same_bits(c[1], mn.cpu().numpy())
