@@ -982,6 +982,120 @@ int plf_covis_count(const plf_covis_view *v, const plf_covis_params *p, int32_t 
 int plf_covis_by_weight(const int32_t *ord_w, const int32_t *n_ord, int32_t n_rows, int32_t stride, int32_t w, int32_t *n_out, int32_t device,
                         void *stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * Culling -- void LocalMapping::KeyFrameCulling() (so@0x643e0) and void LocalMapping::MapPointCulling() (so@0x593f0) of include/LocalMapping.h,
+ * over the same resident observation CSR and mvpMapPoints rows as the covisibility graph, plus the keyframes' own mvKeysUn / mvDepth.
+ * Integer work with one float gate and one double comparison: every output is exact and two identical calls write identical bits.
+ *
+ * KeyFrameCulling, from the binary:
+ *  1. the candidates are mpCurrentKeyFrame->GetVectorCovisibleKeyFrames(), taken once before the loop (so@0x64417).  Here: cand_row, the row
+ *     of each candidate in the reference's order -- e.g. the row indices behind one row of plf_covis_count's ord_kf.
+ *  2. a candidate with mnId == 0 is skipped (cmpq $0,(%r12), so@0x64469): cand_flags bit 0.
+ *  3. nMPs = nRedundantObservations = 0 (so@0x64499, 0x644a1); for i over GetMapPointMatches() (so@0x64478): a null entry is skipped
+ *     (so@0x644c6), a point that isBad() is skipped (so@0x644ce); when !mbMonocular (cmpb $0,(this), so@0x644db) d = mvDepth[i] and the entry
+ *     is skipped if d > mThDepth (vucomiss + ja, so@0x644ed-0x644f7) or 0 > d (so@0x644fd-0x64501): both tests are false for a NaN, and the
+ *     second for -0.0f, so neither is skipped; nMPs++ (so@0x64506); the entry goes on only if pMP->Observations() > 3 (cmp $3; jle,
+ *     so@0x64510; th_obs); scaleLevel = pKF->mvKeysUn[i].octave (stride 28, offset 0x14, so@0x6451a-0x6452f); over GetObservations() in
+ *     std::map order the candidate itself is skipped (so@0x64554), an observer whose mvKeysUn[idx].octave <= scaleLevel + 1 counts
+ *     (so@0x64573-0x6457d: cmp; jg), the loop leaves at the third count (cmp $2; jg, so@0x64582); three counts: nRedundantObservations++
+ *     (so@0x64638).
+ *  4. (double)nRedundantObservations > 0.9 * (double)nMPs (vcvtsi2sd, vmulsd with the double at so@0x1266b0, vucomisd + ja,
+ *     so@0x64600-0x64618): pKF->SetBadFlag() (so@0x64645).  `ratio` is that double.
+ * MapPoint::Observations() (so@0x8f7b0) returns nObs, which AddObservation (so@0x91e70) raises by 2 for an observation with
+ * mvuRight[idx] >= 0 and by 1 otherwise: obs_w.  KeyFrame::SetBadFlag() (so@0xa0770) returns at once for mnId == 0 (so@0xa07de) and for
+ * mbNotErase only sets mbToBeErased (so@0xa07e4-0xa07ed; cand_flags bit 1); otherwise it calls MapPoint::EraseObservation(this)
+ * (so@0x922b0) on every non-null entry of mvpMapPoints: nothing if the keyframe is not among the point's observations (so a point listed
+ * twice is erased once), else nObs -= 2 or 1 (so@0x923d7-0x923e5, 0x92481), and with nObs <= 2 (cmpl $2, so@0x92408) MapPoint::SetBadFlag()
+ * (so@0x92030): the point is bad, and null in every row, for every later candidate.  THE DECISION ON CANDIDATE j DEPENDS ON WHICH
+ * CANDIDATES BEFORE j WERE ERASED; PLF_CULL_SEQUENTIAL gives exactly the one-by-one loop.
+ * Here: a point's Observations() is the sum of obs_w over its observations whose obs_kf is inside [0, n_kf) and was not erased by this call;
+ * erasing a keyframe removes every observation that names its slot from the points of its row (the rows and the CSR agree, as
+ * AddObservation / AddMapPoint keep them: an observation (kf, idx) of point p means row(kf)[idx] == p), and a point of that row that is
+ * not bad, is observed by the keyframe and is left with <= 2 goes bad.  The count of step 3 needs three observers and the gate the whole
+ * sum, so where the walk stops does not change either; every size class below gives the bits of the serial loop.
+ * The PL fork's KeyFrameCulling may weigh map lines as well; no body for that exists anywhere in the reference: lines are OUT OF SCOPE.
+ *
+ * Modes.  PLF_CULL_SNAPSHOT: every candidate judged against the map as given, independently, in one pass (statistics, maintenance; any
+ * number of candidates, e.g. every keyframe); nothing is erased: kf_erased and point_went_bad are not written, status = {n_cand, 0}.
+ * PLF_CULL_SEQUENTIAL: the reference's loop.  The call enqueues max_culls + 1 pairs of (evaluate, commit) kernels up front and reads
+ * nothing back: evaluate judges every candidate from the first undecided one on under the current erased / bad state, one workgroup per
+ * candidate; commit is one workgroup that confirms the leading run of keeps and the first candidate to erase, applies its erasures and
+ * advances the decided count status[0].  A pair that finds every candidate decided ends at its first test of status[0].  COST OF A ROUND:
+ * two launches and one evaluation of every undecided row, so a call costs (erasures + 1) row evaluations of the list and 2 * (max_culls + 1)
+ * launches (a few microseconds each when they have nothing to do).  At most max_culls (0 = 8) erasures are applied per call; if the list
+ * needs more, status[0] < n_cand: the outputs before status[0] are final, those from it on hold the last evaluation, and the caller goes on
+ * with a second call for the rest of the list on the applied state: point_bad |= point_went_bad, kf_gone |= kf_erased (the mirrors do
+ * this loop).  The candidates are distinct rows.  A candidate whose own slot is already set in kf_gone is judged like any other (its own
+ * observations are skipped either way) and, if flagged, reported as erased again: a caller does not list erased keyframes.
+ *
+ * Size classes of the evaluate pass (by a point's CSR range length n): n <= 8 one lane per point; 9 .. 64 eight lanes per point;
+ * more than 64 a whole wave, 64 observations per step with ballot / popcount and the same early stop.  force_class (1, 2, 3) sends every
+ * point through the lane, group or wave schedule: all give the same bits.
+ * Stateless; every array is DEVICE memory; asynchronous on `stream`; scratch (n_kf + n_points bytes, sequential mode only) comes from the
+ * stream-ordered pool.  Out-of-range row_point / obs_kf are skipped as in plf_covis_count; a cand_row outside [0, n_rows) or a row_kf
+ * outside [0, n_kf) is decided as skipped (3).  Filler between and beyond the CSR ranges is never read.
+ * ---------------------------------------------------------------------------------------------- */
+#define PLF_CULL_SNAPSHOT 0
+#define PLF_CULL_SEQUENTIAL 1
+typedef struct {
+    int32_t n_rows;
+    const int32_t *row_start;        /* n_rows + 1: the keyframes' mvpMapPoints, dense: the position inside the row is the feature index */
+    const int32_t *row_point;        /* point ids; -1 or outside [0, n_points) = null */
+    const int32_t *row_kf;           /* n_rows: the slot of the row's keyframe */
+    int32_t n_points;
+    const int32_t *obs_start;        /* n_points + 1 */
+    const int32_t *obs_kf;           /* observing keyframe slot; outside [0, n_kf) skipped and not weighed */
+    const int32_t *obs_idx;          /* feature index in that keyframe; read in the indirect level form only (negative: 0) */
+    const uint8_t *obs_w;            /* optional: 2 for an observation with mvuRight[idx] >= 0, else 1; NULL = 1 everywhere */
+    const uint8_t *point_bad;        /* optional, n_points */
+    int32_t n_kf;
+    const uint8_t *kf_gone;          /* optional, n_kf: 1 = erased by an earlier call (its kf_erased): the slot's observations are skipped and not weighed */
+    /* the octaves, in exactly one of two forms -- packed: */
+    const int32_t *row_level;        /* parallel to row_point: mvKeysUn[i].octave of the row's keyframe */
+    const int32_t *obs_level;        /* parallel to obs_kf */
+    /* -- or indirect: kf_keys[row_kf[r]][i].octave and kf_keys[obs_kf][obs_idx].octave; indices are not checked against the keyframe's size */
+    const plf_keypoint *const *kf_keys;   /* device table of n_kf device pointers (plf_map_geom_view.kf_keys) */
+    /* the depths, in at most one of two forms; both may be NULL when monocular != 0 */
+    const float *row_depth;          /* parallel to row_point: mvDepth[i] */
+    const float *const *kf_depth;    /* device table of n_kf device pointers to each keyframe's mvDepth */
+    float th_depth;                  /* mThDepth */
+    int32_t monocular;               /* mbMonocular: != 0 means no depth gate */
+} plf_cull_view;
+typedef struct {
+    int32_t mode;
+    int32_t th_obs;                  /* 3 in the reference: Observations() > th_obs */
+    int32_t max_culls;               /* sequential mode: erasures applied per call at most; 0 = 8 */
+    int32_t force_class;             /* 0 = by observation count; 1, 2, 3 = every point by lane, lane group, wave */
+    double ratio;                    /* 0.9 in the reference */
+} plf_cull_params;
+
+/* cand_row, cand_flags (optional, NULL = 0; bit 0: mnId == 0, bit 1: mbNotErase): n_cand each.  n_mps, n_redundant, decision: n_cand each;
+ * decision 0 = keep, 1 = erased (snapshot: would be), 2 = redundant but mbNotErase (mbToBeErased; no erasure, no effect on later candidates),
+ * 3 = skipped (counts -1).  Entries at n_cand and beyond are not written.  kf_erased (n_kf, uint8): 1 written for every slot erased, the others
+ * untouched; point_went_bad (optional, n_points, uint8): likewise; point_nobs (optional, n_points): Observations() of every point after the
+ * erasures (one more pass over the CSR when given).  status (2): {candidates decided, erasures applied}.
+ * PLF_E_BADARG before any device work: a NULL required array, negative sizes, both or neither level form (packed needs both arrays, indirect
+ * needs obs_idx), depths missing while monocular == 0 or both depth forms, an unknown mode, th_obs < 0, max_culls < 0, force_class outside 0 .. 3. */
+int plf_keyframe_culling(const plf_cull_view *v, const plf_cull_params *p, const int32_t *cand_row, const uint8_t *cand_flags, int32_t n_cand,
+                         int32_t *n_mps, int32_t *n_redundant, int32_t *decision, uint8_t *kf_erased, uint8_t *point_went_bad, int32_t *point_nobs,
+                         int32_t *status, int32_t device, void *stream);
+
+/* MapPointCulling over mlpRecentAddedMapPoints, decisions independent per point; from the binary, in this order:
+ *  1. isBad() (so@0x59432): dropped from the list -> 1.
+ *  2. 0.25f > GetFoundRatio() (the float at so@0x12666c; vucomiss %xmm0,%xmm1 + ja, so@0x5944b-0x5944f): SetBadFlag and drop -> 2.
+ *     GetFoundRatio (so@0x8f8d0) is (float)mnFound / mnVisible, one float division.  visible == 0: found > 0 gives +inf and found == 0 gives
+ *     NaN; `ja` is not taken for either (unordered sets CF), so rule 2 does NOT fire and the point goes on to rule 3.
+ *  3. (int)cur - (int)mnFirstKFid >= 2 (32-bit sub, cmp $1; jle, so@0x59451-0x5945a) && Observations() <= cnThObs (cmp; jge, so@0x59464):
+ *     SetBadFlag and drop -> 2.  cnThObs = mbMonocular ? 2 : 3 (sbb / not / add $3, so@0x5941c-0x59422): cn_th_obs.
+ *  4. (int)cur - (int)mnFirstKFid >= 3 (cmp $2; jle, so@0x5946f): drop -> 1.
+ *  5. otherwise keep -> 0.
+ * found, visible (int32), first_kf_id (int64: mnFirstKFid is a long, narrowed as the binary does): n each.  Observations(): point_nobs (n), or,
+ * when it is NULL, the sum of obs_w (NULL = 1) over the in-range obs_kf of the CSR (obs_start: n + 1).  One elementwise kernel.
+ * PLF_E_BADARG: a NULL required array, n < 0, neither point_nobs nor obs_start + obs_kf, n_kf < 0. */
+int plf_map_point_culling(int32_t n, const int32_t *found, const int32_t *visible, const int64_t *first_kf_id, const int32_t *point_nobs,
+                          const int32_t *obs_start, const int32_t *obs_kf, const uint8_t *obs_w, int32_t n_kf, const uint8_t *point_bad,
+                          int64_t cur_kf_id, int32_t cn_th_obs, int32_t *decision, int32_t device, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

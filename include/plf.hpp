@@ -389,6 +389,27 @@ struct MapLine {
     }
 };
 
+// void LocalMapping::KeyFrameCulling() (so@0x643e0) over device arrays: the candidates are rows of the view in the reference's order (a row of
+// plf_covis_count's ord_kf when a keyframe's row index is its slot).  PLF_CULL_SEQUENTIAL gives the one-by-one loop with the erasures of
+// KeyFrame::SetBadFlag applied in between; status_dev[0] < n_cand means more than max_culls erasures: call again for the rest (plf_keyframe_culling).
+inline void KeyFrameCulling(const plf_cull_view &map_dev, const plf_cull_params &params, const int32_t *cand_row_dev, const uint8_t *cand_flags_dev, int n_cand,
+                            int32_t *n_mps_dev, int32_t *n_redundant_dev, int32_t *decision_dev, uint8_t *kf_erased_dev, uint8_t *point_went_bad_dev,
+                            int32_t *point_nobs_dev, int32_t *status_dev, int device = 0, void *stream = nullptr)
+{
+    check(plf_keyframe_culling(&map_dev, &params, cand_row_dev, cand_flags_dev, n_cand, n_mps_dev, n_redundant_dev, decision_dev, kf_erased_dev,
+                               point_went_bad_dev, point_nobs_dev, status_dev, device, stream), "LocalMapping::KeyFrameCulling");
+}
+inline plf_cull_params KeyFrameCullingParams(int mode = PLF_CULL_SEQUENTIAL) { return plf_cull_params{mode, 3, 0, 0, 0.9}; }   // the reference's constants
+// void LocalMapping::MapPointCulling() (so@0x593f0) over mlpRecentAddedMapPoints as device arrays, Observations() given per point: decision 0 keep,
+// 1 erase from the list, 2 SetBadFlag() and erase.  cnThObs is 2 for a monocular system, 3 otherwise.
+inline void MapPointCulling(int n, const int32_t *mnFound_dev, const int32_t *mnVisible_dev, const int64_t *mnFirstKFid_dev, const int32_t *nObs_dev,
+                            const uint8_t *point_bad_dev, long unsigned int nCurrentKFid, int cnThObs, int32_t *decision_dev, int device = 0,
+                            void *stream = nullptr)
+{
+    check(plf_map_point_culling(n, mnFound_dev, mnVisible_dev, mnFirstKFid_dev, nObs_dev, nullptr, nullptr, nullptr, 0, point_bad_dev, (int64_t)nCurrentKFid,
+                                cnThObs, decision_dev, device, stream), "LocalMapping::MapPointCulling");
+}
+
 // ------------------------------------------------------------------ batches of independent host frames on all GPUs of the node
 // The caller loop of the reference (Examples/RGB-D/rgbd_tum.cc:84-128 -> System::TrackRGBD -> Tracking::GrabImageRGBD -> RGB-D Frame::Frame,
 // include/Frame.h:60) for N frames at once: plf_batch_* shards the frames over the GPUs in contiguous blocks (no collective), stages them through
@@ -1339,6 +1360,96 @@ private:
     int device_, first_stride_;
     std::unordered_map<KeyFrameT *, Row> rows_;
 };
+// LocalMapping::KeyFrameCulling (so@0x643e0) over the reference's own KeyFrame / MapPoint classes: the candidates are
+// mpCurrentKeyFrame->GetVectorCovisibleKeyFrames(), in that order.  Reads pKF->mnId, GetMapPointMatches(), mvKeysUn, mvDepth, mvuRight (the weight of an
+// observation: 2 where mvuRight[idx] >= 0), mThDepth (the first candidate's: one camera), pMP->isBad() and GetObservations().  mbNotErase is protected in the
+// reference, so the forwarder inside LocalMapping.cc / KeyFrame.cc passes it (vbNotErase, parallel to the candidates; empty = none).  The decisions equal
+// the reference's one-by-one loop, the erasures between candidates included; the call resumes by itself when a list needs more than one call's erasures.
+// NOTHING is applied to the objects: the caller runs pKF->SetBadFlag() on `erase` in order, which repeats on the host members exactly the erasures the device
+// applied to its copy.  Uploads the rows of the candidates and the observations of their points once per call.  Map lines are not weighed.
+template <class KeyFrameT> struct KeyFrameCullingResult {
+    std::vector<int32_t> nMPs, nRedundantObservations, decision;   // per candidate: PLF decision 0 keep, 1 erase, 2 redundant but mbNotErase, 3 skipped (mnId == 0)
+    std::vector<KeyFrameT *> erase;                                // the candidates with decision 1, in order
+    int calls = 0;                                                 // device calls the list took
+};
+template <class KeyFrameT> KeyFrameCullingResult<KeyFrameT> KeyFrameCulling(const std::vector<KeyFrameT *> &vpLocalKeyFrames, bool mbMonocular,
+                                                                           const std::vector<bool> &vbNotErase = std::vector<bool>(), int device = 0,
+                                                                           int max_culls = 0)
+{
+    KeyFrameCullingResult<KeyFrameT> out;
+    const int C = (int)vpLocalKeyFrames.size();
+    out.nMPs.assign(C, -1); out.nRedundantObservations.assign(C, -1); out.decision.assign(C, 3);
+    if (C == 0) return out;
+    detail::KeyFrameSlots kf_slot;
+    std::unordered_map<const void *, int> point_id;
+    std::vector<int32_t> row_start{0}, row_point, row_kf, row_level, obs_start{0}, obs_kf, obs_level, cand_row(C);
+    std::vector<float> row_depth;
+    std::vector<uint8_t> obs_w, point_bad, cand_flags(C, 0);
+    auto slot_of = [&](auto *pKF) { return kf_slot(pKF, [](auto *) {}); };
+    float th_depth = 0.0f;
+    for (int j = 0; j < C; j++) {
+        KeyFrameT *pKF = vpLocalKeyFrames[j];
+        cand_row[j] = j;
+        cand_flags[j] = (uint8_t)((pKF->mnId == 0 ? 1 : 0) | (j < (int)vbNotErase.size() && vbNotErase[j] ? 2 : 0));
+        if (j == 0) th_depth = pKF->mThDepth;
+        row_kf.push_back(slot_of(pKF));
+        const auto vpMapPoints = pKF->GetMapPointMatches();
+        for (size_t i = 0; i < vpMapPoints.size(); i++) {
+            auto *pMP = vpMapPoints[i];
+            row_level.push_back(i < pKF->mvKeysUn.size() ? pKF->mvKeysUn[i].octave : 0);
+            row_depth.push_back(i < pKF->mvDepth.size() ? pKF->mvDepth[i] : 0.0f);
+            if (!pMP) { row_point.push_back(-1); continue; }
+            const auto at = point_id.emplace((const void *)pMP, (int)point_bad.size());
+            if (at.second) {
+                point_bad.push_back(pMP->isBad());
+                const auto observations = pMP->GetObservations();
+                for (const auto &ob : observations) {
+                    auto *pKFi = ob.first;
+                    const size_t idx = ob.second;
+                    obs_kf.push_back(slot_of(pKFi));
+                    obs_level.push_back(idx < pKFi->mvKeysUn.size() ? pKFi->mvKeysUn[idx].octave : 0);
+                    obs_w.push_back(idx < pKFi->mvuRight.size() && pKFi->mvuRight[idx] >= 0 ? 2 : 1);
+                }
+                obs_start.push_back((int32_t)obs_kf.size());
+            }
+            row_point.push_back(at.first->second);
+        }
+        row_start.push_back((int32_t)row_point.size());
+    }
+    const int P = (int)point_bad.size(), S = (int)kf_slot.size();
+    // one element of padding each: never an empty allocation; beyond the CSR ranges, never read
+    row_point.push_back(-1); row_level.push_back(0); row_depth.push_back(0.0f); obs_kf.push_back(-1); obs_level.push_back(0); obs_w.push_back(1); point_bad.push_back(0);
+    std::vector<uint8_t> gone(S + 1, 0);
+    plf::DeviceArray<int32_t> d_row_start(row_start, device), d_row_point(row_point, device), d_row_kf(row_kf, device), d_row_level(row_level, device),
+        d_obs_start(obs_start, device), d_obs_kf(obs_kf, device), d_obs_level(obs_level, device), d_cand(cand_row, device), d_mps(C, device), d_red(C, device),
+        d_dec(C, device), d_status(2, device);
+    plf::DeviceArray<float> d_row_depth(row_depth, device);
+    plf::DeviceArray<uint8_t> d_obs_w(obs_w, device), d_bad(point_bad, device), d_flags(cand_flags, device), d_gone(gone, device), d_erased(gone, device),
+        d_went(point_bad.size(), device);
+    d_went.fill(0);
+    plf_cull_view v = {};
+    v.n_rows = C; v.row_start = d_row_start.get(); v.row_point = d_row_point.get(); v.row_kf = d_row_kf.get(); v.n_points = P; v.obs_start = d_obs_start.get();
+    v.obs_kf = d_obs_kf.get(); v.obs_w = d_obs_w.get(); v.point_bad = d_bad.get(); v.n_kf = S; v.kf_gone = d_gone.get(); v.row_level = d_row_level.get();
+    v.obs_level = d_obs_level.get(); v.row_depth = mbMonocular ? nullptr : d_row_depth.get(); v.th_depth = th_depth; v.monocular = mbMonocular ? 1 : 0;
+    const plf_cull_params p = {PLF_CULL_SEQUENTIAL, 3, max_culls, 0, 0.9};
+    for (int done = 0; done < C;) {
+        plf::check(plf_keyframe_culling(&v, &p, d_cand.get() + done, d_flags.get() + done, C - done, d_mps.get() + done, d_red.get() + done, d_dec.get() + done,
+                                        d_erased.get(), d_went.get(), nullptr, d_status.get(), device, nullptr), "LocalMapping::KeyFrameCulling");
+        out.calls++;
+        const int decided = d_status.download()[0];                 // a NULL-stream download waits for the device first
+        if (decided <= 0) break;                                    // cannot happen: a call decides at least its first candidate
+        done += decided;
+        if (done < C) {                                             // more erasures than one call applies: go on from the applied state
+            const std::vector<uint8_t> went = d_went.download(), erased = d_erased.download();
+            for (int q = 0; q < P; q++) point_bad[q] = point_bad[q] || went[q] == 1;
+            for (int s = 0; s < S; s++) gone[s] = erased[s] == 1;
+            d_bad.upload(point_bad.data(), point_bad.size()); d_gone.upload(gone.data(), gone.size());
+        }
+    }
+    out.nMPs = d_mps.download(); out.nRedundantObservations = d_red.download(); out.decision = d_dec.download();
+    for (int j = 0; j < C; j++) if (out.decision[j] == 1) out.erase.push_back(vpLocalKeyFrames[j]);
+    return out;
+}
 }  // namespace ORB_SLAM2_PLF
 #endif
 #endif

@@ -12,3 +12,5 @@ from . import mappoints  # noqa: F401
 from .mappoints import distinctive_descriptors, update_normal_and_depth, kf_keys_table, MapPoint, MapLine  # noqa: F401
 from . import covisibility  # noqa: F401
 from .covisibility import update_connections, local_keyframe_votes, Covisibility  # noqa: F401
+from . import culling  # noqa: F401
+from .culling import keyframe_culling, map_point_culling, CullMap  # noqa: F401

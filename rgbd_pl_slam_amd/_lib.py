@@ -244,3 +244,25 @@ def covis_prototypes(l):
     l.plf_covis_count.argtypes = [C.POINTER(CovisView), C.POINTER(CovisParams), P, P, P, P, P, P, P, P, I, P]
     l.plf_covis_by_weight.argtypes = [P, P, I, I, I, P, I, P]
     return l
+
+
+# ---- culling (include/plf.h, "Culling")
+CULL_SNAPSHOT, CULL_SEQUENTIAL = 0, 1
+
+
+class CullView(C.Structure):
+    _fields_ = [("n_rows", C.c_int32), ("row_start", C.c_void_p), ("row_point", C.c_void_p), ("row_kf", C.c_void_p), ("n_points", C.c_int32),
+                ("obs_start", C.c_void_p), ("obs_kf", C.c_void_p), ("obs_idx", C.c_void_p), ("obs_w", C.c_void_p), ("point_bad", C.c_void_p),
+                ("n_kf", C.c_int32), ("kf_gone", C.c_void_p), ("row_level", C.c_void_p), ("obs_level", C.c_void_p), ("kf_keys", C.c_void_p),
+                ("row_depth", C.c_void_p), ("kf_depth", C.c_void_p), ("th_depth", C.c_float), ("monocular", C.c_int32)]
+
+
+class CullParams(C.Structure):
+    _fields_ = [("mode", C.c_int32), ("th_obs", C.c_int32), ("max_culls", C.c_int32), ("force_class", C.c_int32), ("ratio", C.c_double)]
+
+
+def cull_prototypes(l):
+    P, I = C.c_void_p, C.c_int32
+    l.plf_keyframe_culling.argtypes = [C.POINTER(CullView), C.POINTER(CullParams), P, P, I, P, P, P, P, P, P, P, I, P]
+    l.plf_map_point_culling.argtypes = [I, P, P, P, P, P, P, P, I, P, C.c_int64, I, P, I, P]
+    return l
