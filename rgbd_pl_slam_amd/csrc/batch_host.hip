@@ -19,10 +19,7 @@
 #include <pthread.h>
 #include "plf_common.h"
 #include "orb_geom.h"
-
-// status words of the extractor handles, copied asynchronously on `s` (orb_host.hip / line_host.hip)
-int plf_orb_status_async(plf_orb *h, int32_t *host_dst, hipStream_t s);
-int plf_line_status_async(plf_line *h, int32_t *host_dst, int32_t *host_flags, int n, hipStream_t s);
+#include "lsd_geom.h"
 
 namespace {
 

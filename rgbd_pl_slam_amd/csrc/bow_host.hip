@@ -4,15 +4,7 @@
 #include <string.h>
 #include <ctype.h>
 #include <vector>
-#include "plf_common.h"
-
-__global__ void k_bow_descend16(const int4 *, const uint8_t *, const double *, const uint8_t *, const int32_t *, int, int, int, uint32_t *, double *, uint32_t *);
-__global__ void k_bow_descend32(const int4 *, const uint8_t *, const double *, const uint8_t *, const int32_t *, int, int, int, uint32_t *, double *, uint32_t *);
-__global__ void k_bow_frame(const int32_t *, int, int, int, int, const uint32_t *, const double *, const uint32_t *, uint32_t *, double *, int32_t *, uint32_t *,
-                            int32_t *, int32_t *, int32_t *);
-__global__ void k_bow_score(int, const uint32_t *, const double *, int, const uint32_t *, const double *, const int32_t *, int, double *);
-
-#define BOW_T 256   // threads of k_bow_frame (bow_kernels.hip)
+#include "bow_common.h"
 
 struct plf_vocab {
     int device;

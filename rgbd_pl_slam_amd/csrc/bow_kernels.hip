@@ -3,6 +3,7 @@
 // ScoringObject.cpp:23-120 and :271-311, FORB.cpp:82-102.  Everything a double passes through is written as the reference writes it
 // (sequential adds, ascending word id; the Makefile's -ffp-contract=off keeps mul and add apart), so the outputs are bit-equal.
 #include "plf_common.h"
+#include "bow_common.h"
 #include "bow_score.h"
 
 // min over the 16 lanes of a DPP row; every lane of the row ends up with the row's minimum (the steps of plf_wave_sum)
@@ -71,7 +72,6 @@ __global__ void __launch_bounds__(256) k_bow_descend32(const int4 *t_info, const
 }
 
 // ---- per-frame accumulation: one workgroup per frame
-#define BOW_T 256
 #define BOW_NONE 0xFFFFFFFFFFFFFFFFull
 
 // ascending bitonic sort of P (a power of two) 64-bit keys in LDS

@@ -28,3 +28,7 @@ static inline size_t covis_lds_bytes(int dense, int n_kf, int table_slots, int l
 {
     return (size_t)list_cap * 8 + (dense ? (size_t)n_kf * 4 : (size_t)table_slots * 8);
 }
+
+__global__ void k_covis_rows(CovisArgs a);
+__global__ void k_covis_rank(const int64_t *key, int n, int32_t *rank, int32_t *inv);
+__global__ void k_covis_by_weight(const int32_t *ord_w, const int32_t *n_ord, int n_rows, int stride, int w, int32_t *n_out);

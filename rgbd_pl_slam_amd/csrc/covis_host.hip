@@ -4,10 +4,6 @@
 #include <algorithm>
 #include "covis_common.h"
 
-__global__ void k_covis_rows(CovisArgs);
-__global__ void k_covis_rank(const int64_t *, int, int32_t *, int32_t *);
-__global__ void k_covis_by_weight(const int32_t *, const int32_t *, int, int, int, int32_t *);
-
 #define COVIS_MAX_GRID 1024
 #define COVIS_SCRATCH_BYTES ((size_t)256 << 20)   // bound of the per-workgroup scratch: fewer workgroups rather than more memory
 static PlfLdsOnce g_covis_lds = {(const void *)k_covis_rows, (int)covis_lds_bytes(1, COVIS_DENSE_LIMIT, 0, COVIS_SORT_CAP)};

@@ -34,3 +34,8 @@ struct CullPointArgs {
     int n_kf, cur, cn_th_obs;
     int32_t *decision;
 };
+
+__global__ void k_cull_eval(CullArgs a);
+__global__ void k_cull_commit(CullArgs a);
+__global__ void k_cull_nobs(CullArgs a);
+__global__ void k_cull_points(CullPointArgs a);

@@ -4,11 +4,6 @@
 #include <algorithm>
 #include "culling_common.h"
 
-__global__ void k_cull_eval(CullArgs);
-__global__ void k_cull_commit(CullArgs);
-__global__ void k_cull_nobs(CullArgs);
-__global__ void k_cull_points(CullPointArgs);
-
 extern "C" int plf_keyframe_culling(const plf_cull_view *v, const plf_cull_params *p, const int32_t *cand_row, const uint8_t *cand_flags, int32_t n_cand,
                                     int32_t *n_mps, int32_t *n_redundant, int32_t *decision, uint8_t *kf_erased, uint8_t *point_went_bad,
                                     int32_t *point_nobs, int32_t *status, int32_t device, void *stream)

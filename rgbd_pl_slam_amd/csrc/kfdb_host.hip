@@ -4,22 +4,8 @@
 #include <stdlib.h>
 #include <algorithm>
 #include <vector>
-#include "plf_common.h"
+#include "kfdb_common.h"
 
-__global__ void k_kfdb_store(const uint32_t *, const double *, const int32_t *, int, const int32_t *, int, uint32_t *, double *, int32_t *, float *);
-__global__ void k_kfdb_hist(const int32_t *, const int32_t *, const uint32_t *, int, int, int, int32_t *, int32_t *, int);
-__global__ void k_kfdb_scan(int32_t *, int, int32_t *);
-__global__ void k_kfdb_order(const int32_t *, const int32_t *, const int32_t *, int, int32_t *);
-__global__ void k_kfdb_count(const uint32_t *, const int32_t *, int, int, int, const int32_t *, const int32_t *, int, int, int32_t *);
-__global__ void k_kfdb_exclude(const int32_t *, const int32_t *, int, int, int32_t *);
-__global__ void k_kfdb_select(const int32_t *, int, int4 *, uint32_t *, int32_t *);
-__global__ void k_kfdb_score(int, const uint32_t *, const double *, const int32_t *, int, int, const uint32_t *, const double *, const int32_t *, int, int,
-                             const uint32_t *, const int32_t *, float *, uint32_t *);
-__global__ void k_kfdb_carry(const int32_t *, const int4 *, int, int, float *, float *);
-__global__ void k_kfdb_group(int, const int32_t *, const float *, uint32_t *, const int4 *, const float *, int, int, int, const int32_t *, const int32_t *,
-                             const int32_t *, const int32_t *, int, unsigned long long *, int, int32_t *, int32_t *, int32_t *);
-
-#define KFDB_T 256
 #define KFDB_CHUNK_CELLS (1 << 22)   // queries of a chunk x slots (plf.h: the scratch bound)
 
 struct plf_kfdb {

@@ -3,9 +3,9 @@
 // Integers are counted with atomics (order-free); every float step is the reference's single operation (the Makefile's -ffp-contract=off).
 // Per chunk of queries the host (kfdb_host.hip) keeps three dense [query][slot] arrays: cnt (common words), sc (float score), minw.
 #include "plf_common.h"
+#include "kfdb_common.h"
 #include "bow_score.h"
 
-#define KFDB_T 256
 #define KFDB_LDS_KEYS 4096
 #define KFDB_NONE 0xFFFFFFFFFFFFFFFFull
 

@@ -50,51 +50,6 @@ const double *plf_nfa_table_host(double log_nt)
     return cache.emplace(log_nt, std::move(tab)).first->second.data();
 }
 
-__global__ void k_lsd_pre(const uint8_t *, ptrdiff_t, ptrdiff_t, float *, double *, double2 *, float2 *, LsdGeom, LsdTaps, const int *, const float2 *,
-                          const int *, const float2 *, int *);
-__global__ void k_lsd_balance(const int *, int *, int, int);
-__global__ void k_lsd_regions2(float *, const double *, const double2 *, const float2 *, uint32_t *, LsdRect *, int *, int *, LsdGeom, const uint32_t *, int, const int *);
-__global__ void k_lsd_regions_lat(float *, const double *, const double2 *, const float2 *, uint32_t *, LsdRect *, int *, int *, LsdGeom, const uint32_t *, int *);
-// the same kernels with the time budget of plf_line_params.max_ms compiled in (separate instances: the default ones read no clock)
-__global__ void k_lsd_regions2_budget(float *, const double *, const double2 *, const float2 *, uint32_t *, LsdRect *, int *, int *, LsdGeom, const uint32_t *, int, const int *);
-__global__ void k_lsd_regions_lat_budget(float *, const double *, const double2 *, const float2 *, uint32_t *, LsdRect *, int *, int *, LsdGeom, const uint32_t *, int *);
-__global__ void k_lsd_spec_fused_budget(float *, const double *, const double2 *, const float2 *, uint32_t *, LsdRect *, int *, int *, LsdGeom, SpecBufs, int *, int);
-__global__ void k_lsd_spec_grow_budget(float *, const double *, const double2 *, const float2 *, LsdGeom, SpecBufs);
-__global__ void k_lsd_spec_commit_budget(float *, const double *, const double2 *, const float2 *, uint32_t *, LsdRect *, int *, int *, LsdGeom, SpecBufs, int *);
-__global__ void k_lsd_maxgrad(const float *, const double *, double *, LsdGeom);
-__global__ void k_lsd_seedkeys(const float *, const double *, const double *, uint32_t *, LsdGeom);
-__global__ void k_lsd_count_used(const float *, int *, LsdGeom);
-struct NfaEntry { LsdRect r; int frame, nprec, pad0, pad1; };
-struct NfaCounts { int total, alg[6], pad; };
-struct NfaState { LsdRect rec; double log_nfa; int frame, rect; };
-__global__ void k_nfa_init(const LsdRect *, const int *, uint8_t *, NfaEntry *, NfaState *, int *, int *, LsdGeom);
-__global__ void k_nfa_clamp(int *, int *, LsdGeom);
-__global__ void k_nfa_count(const float *, const NfaEntry *, const int *, int, int, NfaCounts *, LsdGeom);
-__global__ void k_nfa_count1(const float *, const NfaEntry *, const int *, int, int, NfaCounts *, LsdGeom);
-__global__ void k_nfa_count_w(const float *, const NfaEntry *, const int *, int, int, NfaCounts *, LsdGeom);
-__global__ void k_nfa_count1_w(const float *, const NfaEntry *, const int *, int, int, NfaCounts *, LsdGeom);
-__global__ void k_nfa_eval(int, const double *, const double *, const NfaCounts *, const NfaEntry *, const int *, double *, LsdGeom);
-__global__ void k_nfa_small(const float *, const double *, const LsdRect *, const int *, uint8_t *, float4 *, NfaEntry *, NfaState *, int *, int *, LsdGeom, int, NfaState *, int *, int);
-__global__ void k_nfa_small2(const float *, const double *, const LsdRect *, uint8_t *, float4 *, NfaEntry *, NfaState *, int *, int *, LsdGeom, int, const NfaState *, const int *, int);
-__global__ void k_nfa_math(int, const double *, const NfaEntry *, const NfaState *, NfaState *, NfaEntry *, int *, float4 *, uint8_t *, LsdGeom);
-__global__ void k_nfa_fused(const float *, const double *, const double *, const LsdRect *, const int *, uint8_t *, float4 *, LsdGeom);
-__global__ void k_lsd_finalize(const float4 *, const uint8_t *, const int *, float4 *, int *, plf_keyline *, plf_keyline *, double *, int *,
-                               int, int *, unsigned long long *, LsdGeom);
-__global__ void k_sobel3(const uint8_t *, ptrdiff_t, ptrdiff_t, short2 *, LsdGeom);
-__global__ void k_blur5_sobel3(const uint8_t *, ptrdiff_t, ptrdiff_t, short2 *, LsdGeom, int4);
-__global__ void k_lbd(const short2 *, const plf_keyline *, const int *, uint8_t *, int, LsdGeom, const LbdCoefs *);
-
-__global__ void k_lsd_spec_fused(float *, const double *, const double2 *, const float2 *, uint32_t *, LsdRect *, int *, int *, LsdGeom, SpecBufs, int *, int);
-__global__ void k_lsd_spec_rows(const float *, LsdGeom, SpecBufs, int *);
-__global__ void k_lsd_spec_bands(LsdGeom, SpecBufs, const int *, int *);
-__global__ void k_lsd_spec_grow(float *, const double *, const double2 *, const float2 *, LsdGeom, SpecBufs);
-__global__ void k_lsd_spec_commit(float *, const double *, const double2 *, const float2 *, uint32_t *, LsdRect *, int *, int *, LsdGeom, SpecBufs, int *);
-__global__ void k_lsd_spec_commit_rest(float *, const double *, const double2 *, const float2 *, uint32_t *, LsdRect *, int *, int *, LsdGeom, SpecBufs, int *, int);
-__global__ void k_lsd_spec_prefix(SpecBufs, int);
-__global__ void k_lsd_spec_clear(SpecBufs, int *, int);
-__global__ void k_lsd_spec_validate(float *, const double *, const double2 *, const float2 *, LsdGeom, SpecBufs, int);
-__global__ void k_lsd_spec_assemble(LsdRect *, int *, int *, LsdGeom, SpecBufs, int);
-
 // Schedule knobs of the line extractor.  Read ONCE, when the handle is created (environment: PLF_LSD_* / PLF_NFA_FUSED, for experiments and the test hooks that force a
 // schedule), changed afterwards only through plf_line_tune(); a call never looks at the environment (round 3 did, ~30 getenv per call).  PLF_TUNE_AUTO = chosen per
 // call from the number of frames in flight (the table in line_enqueue).
@@ -585,8 +540,8 @@ static int line_enqueue(plf_line *h, const uint8_t *d_gray, int B, ptrdiff_t pit
     const int bm_words = (g.sw * g.sh + 31) / 32, list_words = (g.rcap + 1 + 15) & ~15;
     const int coarse_words = (((((g.sw + 7) >> 3) + 31) & ~31) >> 5) * ((g.sh + 7) >> 3);   // tile rows padded to whole words (spec_commit_body)
     // commit wave: T and S in LDS when they fit, otherwise S in global memory
-    const bool s_global = (size_t)(list_words + 2 * bm_words + coarse_words + 5 * 512 + 512 / 32 + 1024 + 33) * 4 + 64 > 150 * 1024;
-    const int commit_extra = 5 * 512 + 512 / 32 + 1024 + 1 + 16 + 16;   // SPEC_COMMIT_EXTRA_WORDS of lsd_kernels.hip (+ the 16-word alignment of the tile map): record headers, SUSPECT mask, "defined, no record" bits
+    const bool s_global = (size_t)(list_words + 2 * bm_words + coarse_words + SPEC_COMMIT_EXTRA_WORDS + 16) * 4 + 64 > 150 * 1024;
+    const int commit_extra = SPEC_COMMIT_EXTRA_WORDS + 16;   // (+ the 16-word alignment of the tile map)
     const size_t lds_grow = (size_t)(list_words + bm_words) * 4, lds_commit = (size_t)(list_words + (s_global ? 1 : 2) * bm_words + coarse_words + commit_extra) * 4 + 64;
     int spec_bands = spec_bands_req;
     if (T.spec_bands == PLF_TUNE_AUTO && B <= 16) {

@@ -109,3 +109,76 @@ struct SpecBufs {
 // host-filled tables (line_host.hip), computed once per process (the NFA table once per LOG_NT) and kept: uploaded by every line handle and by plf_debug_math
 const double *plf_lgamma_table_host();
 const double *plf_nfa_table_host(double log_nt);
+
+// ---- the NFA validation stage (k_nfa_*): one work-list entry per rectangle, the pixel counts of its precisions, and the state of its "keep it if better" chain
+struct NfaEntry { LsdRect r; int frame, nprec, pad0, pad1; };   // nprec: 0 = skip, 1 = r.prec only, 6 = r.prec and r.p/2^k, k=1..5
+struct NfaCounts { int total, alg[6], pad; };
+struct NfaState { LsdRect rec; double log_nfa; int frame, rect; };
+
+// ---- the commit wave of the speculative schedule (spec_commit_body): LDS words it needs beyond the region list, the bitmaps and the tile map
+#define SPEC_HCAP 512    // record headers of a commit segment held in LDS
+#define SPEC_NRW 1024    // words (32 pixels each) of a commit segment
+#define SPEC_COMMIT_EXTRA_WORDS (5 * SPEC_HCAP + SPEC_HCAP / 32 + SPEC_NRW + 1 + 16)   // record headers, SUSPECT mask, "defined, no record" bits
+
+#ifdef __HIPCC__
+#include "plf_common.h"
+// batch driver (batch_host.hip): the status word of the batch just enqueued on `s`, copied to pinned host memory in stream order (line_host.hip)
+int plf_line_status_async(plf_line *h, int32_t *host_dst, int32_t *host_flags, int n, hipStream_t s);
+
+// ---- kernels launched by line_host.hip.  lsd_kernels.hip: pre-pass, seeds, region growing
+__global__ void k_lsd_pre(const uint8_t *in, ptrdiff_t pitch, ptrdiff_t fstride, float *ang, double *modgrad, double2 *cs, float2 *cs0, LsdGeom g, LsdTaps t, const int *xofs, const float2 *xa,
+                          const int *yofs, const float2 *yb, int *defcount);
+__global__ void k_lsd_balance(const int *cost, int *perm, int B, int fpw);
+__global__ void k_lsd_maxgrad(const float *ang_all, const double *modgrad_all, double *maxgrad, LsdGeom g);
+__global__ void k_lsd_seedkeys(const float *ang_all, const double *modgrad_all, const double *maxgrad, uint32_t *keys_all, LsdGeom g);
+__global__ void k_lsd_count_used(const float *ang_all, int *out, LsdGeom g);
+__global__ void k_lsd_regions2(float *ang_all, const double *modgrad_all, const double2 *cs_all, const float2 *cs0_all, uint32_t *rxy_all, LsdRect *rects_all, int *nrect, int *status, LsdGeom g,
+                               const uint32_t *seeds_all, int nframes, const int *perm);
+__global__ void k_lsd_regions_lat(float *ang_all, const double *modgrad_all, const double2 *cs_all, const float2 *cs0_all, uint32_t *rxy_all, LsdRect *rects_all, int *nrect, int *status, LsdGeom g,
+                                  const uint32_t *seeds_all, int *sink);
+// the speculative schedule: row bands grown by waves of their own, validated in rounds or committed in order
+__global__ void k_lsd_spec_fused(float *ang_all, const double *modgrad_all, const double2 *cs_all, const float2 *cs0_all, uint32_t *rxy_all, LsdRect *rects_all, int *nrect, int *status, LsdGeom g,
+                                 SpecBufs SB, int *stats, int B);
+__global__ void k_lsd_spec_rows(const float *ang_all, LsdGeom g, SpecBufs SB, int *rowcnt);
+__global__ void k_lsd_spec_bands(LsdGeom g, SpecBufs SB, const int *rowcnt, int *sweep_scratch);
+__global__ void k_lsd_spec_grow(float *ang_all, const double *modgrad_all, const double2 *cs_all, const float2 *cs0_all, LsdGeom g, SpecBufs SB);
+__global__ void k_lsd_spec_commit(float *ang_all, const double *modgrad_all, const double2 *cs_all, const float2 *cs0_all, uint32_t *rxy_all, LsdRect *rects_all, int *nrect, int *status, LsdGeom g,
+                                  SpecBufs SB, int *stats);
+__global__ void k_lsd_spec_commit_rest(float *ang_all, const double *modgrad_all, const double2 *cs_all, const float2 *cs0_all, uint32_t *rxy_all, LsdRect *rects_all, int *nrect, int *status,
+                                       LsdGeom g, SpecBufs SB, int *stats, int zlast);
+__global__ void k_lsd_spec_prefix(SpecBufs SB, int round);
+__global__ void k_lsd_spec_clear(SpecBufs SB, int *rowcnt, int rounds_state);
+__global__ void k_lsd_spec_validate(float *ang_all, const double *modgrad_all, const double2 *cs_all, const float2 *cs0_all, LsdGeom g, SpecBufs SB, int round);
+__global__ void k_lsd_spec_assemble(LsdRect *rects_all, int *nrect, int *status, LsdGeom g, SpecBufs SB, int last);
+// the same kernels with the time budget of plf_line_params.max_ms compiled in (separate instances: the default ones read no clock)
+__global__ void k_lsd_regions2_budget(float *ang_all, const double *modgrad_all, const double2 *cs_all, const float2 *cs0_all, uint32_t *rxy_all, LsdRect *rects_all, int *nrect, int *status,
+                                      LsdGeom g, const uint32_t *seeds_all, int nframes, const int *perm);
+__global__ void k_lsd_regions_lat_budget(float *ang_all, const double *modgrad_all, const double2 *cs_all, const float2 *cs0_all, uint32_t *rxy_all, LsdRect *rects_all, int *nrect, int *status,
+                                         LsdGeom g, const uint32_t *seeds_all, int *sink);
+__global__ void k_lsd_spec_fused_budget(float *ang_all, const double *modgrad_all, const double2 *cs_all, const float2 *cs0_all, uint32_t *rxy_all, LsdRect *rects_all, int *nrect, int *status,
+                                        LsdGeom g, SpecBufs SB, int *stats, int B);
+__global__ void k_lsd_spec_grow_budget(float *ang_all, const double *modgrad_all, const double2 *cs_all, const float2 *cs0_all, LsdGeom g, SpecBufs SB);
+__global__ void k_lsd_spec_commit_budget(float *ang_all, const double *modgrad_all, const double2 *cs_all, const float2 *cs0_all, uint32_t *rxy_all, LsdRect *rects_all, int *nrect, int *status,
+                                         LsdGeom g, SpecBufs SB, int *stats);
+// NFA validation
+__global__ void k_nfa_init(const LsdRect *rects_all, const int *nrect, uint8_t *keep_all, NfaEntry *entries, NfaState *states, int *counters, int *status, LsdGeom g);
+__global__ void k_nfa_clamp(int *counters, int *status, LsdGeom g);
+__global__ void k_nfa_count(const float *ang_all, const NfaEntry *entries, const int *counters, int cidx, int mult, NfaCounts *counts, LsdGeom g);
+__global__ void k_nfa_count1(const float *ang_all, const NfaEntry *entries, const int *counters, int cidx, int mult, NfaCounts *counts, LsdGeom g);
+__global__ void k_nfa_count_w(const float *ang_all, const NfaEntry *entries, const int *counters, int cidx, int mult, NfaCounts *counts, LsdGeom g);
+__global__ void k_nfa_count1_w(const float *ang_all, const NfaEntry *entries, const int *counters, int cidx, int mult, NfaCounts *counts, LsdGeom g);
+__global__ void k_nfa_eval(int stage, const double *lgam, const double *tab, const NfaCounts *counts, const NfaEntry *entries, const int *counters, double *vals, LsdGeom g);
+__global__ void k_nfa_small(const float *ang_all, const double *tab, const LsdRect *rects_all, const int *nrect, uint8_t *keep_all, float4 *seg_all, NfaEntry *entries, NfaState *states, int *counters,
+                            int *status, LsdGeom g, int nframes, NfaState *surv, int *fcnt, int scap);
+__global__ void k_nfa_small2(const float *ang_all, const double *tab, const LsdRect *rects_all, uint8_t *keep_all, float4 *seg_all, NfaEntry *entries, NfaState *states, int *counters, int *status,
+                             LsdGeom g, int nframes, const NfaState *surv, const int *fcnt, int scap);
+__global__ void k_nfa_math(int stage, const double *vals, const NfaEntry *entries, const NfaState *st_in, NfaState *st_out, NfaEntry *ent_out, int *counters, float4 *seg_all, uint8_t *keep_all,
+                           LsdGeom g);
+__global__ void k_nfa_fused(const float *ang_all, const double *lgam, const double *nfatab, const LsdRect *rects_all, const int *nrect, uint8_t *keep_all, float4 *seg_all, LsdGeom g);
+// line_kernels.hip: segment list, gradients, LBD descriptors
+__global__ void k_lsd_finalize(const float4 *seg_all, const uint8_t *keep_all, const int *nrect, float4 *segs_out, int *nseg_out, plf_keyline *kl_tmp_all, plf_keyline *lines, double *lineeq,
+                               int *n_out, int capacity, int *status, unsigned long long *sort_scratch, LsdGeom g);
+__global__ void k_sobel3(const uint8_t *in, ptrdiff_t pitch, ptrdiff_t fstride, short2 *grad, LsdGeom g);
+__global__ void k_blur5_sobel3(const uint8_t *in, ptrdiff_t pitch, ptrdiff_t fstride, short2 *grad, LsdGeom g, int4 k5 /* k[0], k[1], k[2] */);
+__global__ void k_lbd(const short2 *grad_all, const plf_keyline *lines, const int *n_out, uint8_t *desc, int capacity, LsdGeom g, const LbdCoefs *cf);
+#endif

@@ -1953,9 +1953,6 @@ __device__ __forceinline__ unsigned long long spec_readlane64(unsigned long long
     return ((unsigned long long)hi << 32) | lo;
 }
 
-#define SPEC_HCAP 512    // record headers of a commit segment held in LDS
-#define SPEC_NRW 1024    // words (32 pixels each) of a commit segment
-#define SPEC_COMMIT_EXTRA_WORDS (5 * SPEC_HCAP + SPEC_HCAP / 32 + SPEC_NRW + 1 + 16)   // line_host.hip sizes the dynamic LDS with the same expression
 template <bool SG, bool BUDGET>
 __device__ __forceinline__ void spec_commit_body(int f, float *__restrict__ ang_all, const double *__restrict__ modgrad_all, const double2 *__restrict__ cs_all,
                                                  const float2 *__restrict__ cs0_all, uint32_t *__restrict__ rxy_all, LsdRect *__restrict__ rects_all,
@@ -2818,10 +2815,6 @@ struct EdgePt { int x, y, taken; };
 // Work lists are global (all frames of the batch) and compacted with atomics; order is irrelevant because every
 // result is written to its rectangle's own slot.
 // ------------------------------------------------------------------------------------------------
-struct NfaEntry { LsdRect r; int frame, nprec, pad0, pad1; };   // nprec: 0 = skip, 1 = r.prec only, 6 = r.prec and r.p/2^k, k=1..5
-struct NfaCounts { int total, alg[6], pad; };
-struct NfaState { LsdRect rec; double log_nfa; int frame, rect; };
-
 #define NFA_U 4   // gathers in flight per lane in rect_count's column loop
 // pixel count of one rectangle by a group of 16 lanes (4 rectangles per wave: most candidate rectangles span
 // only a few rows, so a full wave per rectangle would idle)

@@ -42,6 +42,11 @@ struct MapArgs {
 
 static inline size_t map_block_lds(int waves, int cap) { return (size_t)cap * 33 + (size_t)waves * (8 + MAP_HIST * 4 + 4); }
 
+__global__ void k_map_bin(MapArgs a);
+__global__ void k_map_small(MapArgs a);
+__global__ void k_map_wave(MapArgs a);
+__global__ void k_map_block(MapArgs a, int cap);
+
 // ---- MapPoint::UpdateNormalAndDepth / MapLine::UpdateAverageDir (mapgeom_kernels.hip, mapgeom_host.hip).  The size classes are those above
 // (MAP_SMALL_MAX, MAP_WAVE_MAX); the workgroup schedule stages the terms of MAPGEOM_CHUNK observations at a time, so it has no upper limit.
 #define MAPGEOM_CHUNK 2048   // terms (x, y, z, counted) per LDS round of the workgroup schedule: 32 KB
@@ -54,3 +59,8 @@ struct MapGeomArgs {
     int32_t *n_obs_used;
     MapBins bins;
 };
+
+__global__ void k_mapgeom_bin(MapGeomArgs a);
+__global__ void k_mapgeom_small(MapGeomArgs a);
+__global__ void k_mapgeom_wave(MapGeomArgs a);
+__global__ void k_mapgeom_block(MapGeomArgs a);

@@ -5,11 +5,6 @@
 #include "plf_common.h"
 #include "map_common.h"
 
-__global__ void k_map_bin(MapArgs);
-__global__ void k_map_small(MapArgs);
-__global__ void k_map_wave(MapArgs);
-__global__ void k_map_block(MapArgs, int);
-
 static PlfLdsOnce g_map_lds = {(const void *)k_map_block, (int)map_block_lds(16, MAP_BLOCK_CAP)};
 
 extern "C" int plf_map_distinctive_descriptors(const plf_map_obs_view *obs, uint8_t *map_desc, int32_t map_rows, int32_t *best_obs,

@@ -4,11 +4,6 @@
 #include "plf_common.h"
 #include "map_common.h"
 
-__global__ void k_mapgeom_bin(MapGeomArgs);
-__global__ void k_mapgeom_small(MapGeomArgs);
-__global__ void k_mapgeom_wave(MapGeomArgs);
-__global__ void k_mapgeom_block(MapGeomArgs);
-
 extern "C" int plf_map_update_normal_depth(const plf_map_geom_view *v, const float *world_pos, float *normal, float *min_distance, float *max_distance,
                                            int32_t map_rows, int32_t *n_obs_used, int32_t device, void *stream)
 {

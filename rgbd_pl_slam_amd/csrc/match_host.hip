@@ -6,57 +6,7 @@
 #include <string.h>
 #include <vector>
 #include "plf_common.h"
-
-#define GRID_COLS 64
-#define GRID_ROWS 48
-#define GRID_CELLS (GRID_COLS * GRID_ROWS)
-
-struct FrameDev {
-    int n;
-    const int *n_dev;
-    const plf_keypoint *keys;
-    const float *uright;
-    const uint8_t *desc;
-    float min_x, min_y, max_x, max_y, inv_w, inv_h;
-    const float *scale_factors;
-    int nlevels;
-    const int *cell_start;
-    const int *cell_idx;
-    const float4 *cell_kp;
-};
-struct MapDev { int m; const float *proj_x, *proj_y, *proj_xr; const int *level; const float *view_cos; const uint8_t *in_view, *desc, *obs_positive; };
-struct RelocDev { int on; const float *min_dist, *max_dist; float log_scale; int orb_dist; };
-struct LastDev { int n; const uint8_t *has_mp, *outlier; const float *xw; const plf_keypoint *keys; const uint8_t *mp_desc; const uint8_t *obs_positive; };
-struct BowDev { int n_kf, n_f; const uint8_t *kf_desc, *f_desc; const float *kf_angle, *f_angle; const uint8_t *kf_has_mp, *f_has_mp; int kf_nodes, f_nodes;
-                const uint32_t *kf_node_id, *f_node_id; const int *kf_node_start, *f_node_start; const int *kf_feat, *f_feat; };
-struct Pts3Dev { int m; const float *xw, *normal, *min_dist, *max_dist; const uint8_t *desc, *valid; };
-struct ProjKf { float R[9], t[3], R2[9], t2[3], Ow[3]; float fx, fy, cx, cy, bf, log_scale; float inv_sigma2[16]; int two_stage, view_test, chi2, accept; };
-struct LineFrameDev { int n; const int *n_dev; const plf_keyline *lines; const uint8_t *desc; const float *scale_factors; };
-struct MapLineDev { int m; const float *x1, *y1, *x2, *y2; const int *level; const float *view_cos; const uint8_t *in_view; const uint8_t *desc; };
-
-__global__ void k_build_grid(const FrameDev *, int *, int *, int *, int);
-__global__ void k_mp_candidates(const FrameDev *, MapDev, float, const int *, int, uint8_t *, uint32_t *, int2 *, int, int *, int *);
-__global__ void k_mp_rounds(const FrameDev *, MapDev, float, int *, int, int *, const uint8_t *, int, const uint32_t *, const int2 *, int, const int *, unsigned long long *, int);
-struct TriDev { const plf_keypoint *keys1, *keys2; const float *uright1, *uright2, *scale2, *sigma2_2; float F[9]; float ex, ey; int only_stereo; };
-__global__ void k_match_bow(const BowDev *, float, int, int, int *, int, int *, int *, int *, TriDev);
-__global__ void k_match_project_points_slow(const FrameDev *, MapDev, float, float, int *, int, int *, uint8_t *, int, const int *);
-__global__ void k_match_lastframe(const FrameDev *, LastDev, const plf_pose_pair *, RelocDev, float, int, int, int *, int, int *, uint8_t *, float4 *, int, int, const int *);
-__global__ void k_lf_candidates(const FrameDev *, LastDev, const plf_pose_pair *, float, int, const int *, int, uint8_t *, uint32_t *, int2 *, int, int, int *, int *);
-__global__ void k_lf_rounds(const FrameDev *, LastDev, int, int *, int, int *, const uint8_t *, int, int, const uint32_t *, const int2 *, int, int, const int *);
-__global__ void k_project_kf(FrameDev, Pts3Dev, ProjKf, float, int *, int *, int *);
-__global__ void k_sim3_agree(const int *, int, const int *, int, int *, int *);
-__global__ void k_project_kf_greedy(FrameDev, Pts3Dev, ProjKf, float, int *, int *, uint8_t *, float4 *, int);
-__global__ void k_knn2(const uint8_t *, int, const uint8_t *, int, int *, int *);
-__global__ void k_knn2_batch(const uint8_t *, int, const LineFrameDev *, int *, int *, int);
-__global__ void k_knn2_to_dmatch(const int *, const int *, int, plf_dmatch *);
-__global__ void k_line_mad(const int *, int, int, double *);
-struct LineTriDev { const uint8_t *has_ml1, *has_ml2, *stereo1, *stereo2; int only_stereo; };
-__global__ void k_lines_lastframe(const int *, const int *, int, const uint8_t *, int *, int *, int, int, int, const LineFrameDev *, double, LineTriDev);
-__global__ void k_lines_fuse_pick(const int *, const int *, const uint8_t *, int, int *, int *);
-__global__ void k_match_project_lines(const LineFrameDev *, MapLineDev, float, float, int *, int, int *, uint8_t *, int);
-__global__ void k_match_project_lines_g(const LineFrameDev *, MapLineDev, float, float, int *, int, int *, uint8_t *, int);
-__global__ void k_match_project_lines_w(const LineFrameDev *, MapLineDev, float, float, int *, int, int *, uint8_t *, int);
-__global__ void k_hamming_matrix(const uint8_t *, int, const uint8_t *, int, int *);
+#include "match_common.h"
 
 struct plf_matcher {
     int device, max_kp, max_mp, max_lines, max_batch;

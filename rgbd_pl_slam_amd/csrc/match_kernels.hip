@@ -18,27 +18,11 @@
 // lowest unfinished item always qualifies, and the result equals the sequential loop for any schedule.
 // No MFMA: 256-bit XOR + popcount per candidate; the work is gather / compare bound.
 #include "plf_common.h"
+#include "match_common.h"
 
-#define GRID_COLS 64
-#define GRID_ROWS 48
-#define GRID_CELLS (GRID_COLS * GRID_ROWS)
 #define TH_HIGH 100
 #define TH_LOW 50
 #define HISTO_LENGTH 30
-
-struct FrameDev {
-    int n;
-    const int *n_dev;
-    const plf_keypoint *keys;
-    const float *uright;
-    const uint8_t *desc;
-    float min_x, min_y, max_x, max_y, inv_w, inv_h;
-    const float *scale_factors;
-    int nlevels;
-    const int *cell_start;  // GRID_CELLS + 1
-    const int *cell_idx;    // n
-    const float4 *cell_kp;  // n: (x, y, octave, index) of the key points in cell order (cell_idx order)
-};
 
 __global__ void __launch_bounds__(256) k_build_grid(const FrameDev *__restrict__ frames, int *__restrict__ cell_start_all,
                                                     int *__restrict__ cell_idx_all, int *__restrict__ cell_of_all, int kp_stride)
@@ -140,16 +124,6 @@ __device__ __forceinline__ CellWin cell_window(const FrameDev &F, float x, float
                 }                                                                                             \
             }                                                                                                 \
     }
-
-struct MapDev {
-    int m;
-    const float *proj_x, *proj_y, *proj_xr;
-    const int *level;
-    const float *view_cos;
-    const uint8_t *in_view;
-    const uint8_t *desc;
-    const uint8_t *obs_positive;
-};
 
 __device__ __forceinline__ bool blocked(const int *claim, int k, const uint8_t *obs_positive)
 {
@@ -410,21 +384,10 @@ __global__ void __launch_bounds__(256) k_mp_rounds(const FrameDev *__restrict__ 
     if (t == 0) nmatches[f] = s_acc;
 }
 
-struct LastDev {
-    int n;
-    const uint8_t *has_mp, *outlier;
-    const float *xw;
-    const plf_keypoint *keys;
-    const uint8_t *mp_desc;
-    const uint8_t *obs_positive;   // Observations() > 0 per last-frame map point; NULL = all (motion-model overload only)
-};
-
 // one block; items = key points of the last frame.  proj[i] = (u, v, invzc, radius) prepared in the first phase.
 // Relocalisation overload, ORBmatcher::SearchByProjection(Frame&, KeyFrame*, const set<MapPoint*>&, th, ORBdist)
 // (include/ORBmatcher.h:82, so@0x7e8c0), shares the kernel: items = keyframe features with a usable map point, no depth-sign
 // and no uRight test, level window from MapPoint::PredictScale (so@0x8fc20), acceptance threshold ORBdist.
-struct RelocDev { int on; const float *min_dist, *max_dist; float log_scale; int orb_dist; };
-
 __global__ void __launch_bounds__(256) k_match_lastframe(const FrameDev *__restrict__ frames, LastDev Lf, const plf_pose_pair *__restrict__ poses, RelocDev RL,
                                                          float th, int mono, int check_ori, int *__restrict__ match_all, int kp_stride,
                                                          int *__restrict__ nmatches_all, uint8_t *__restrict__ done_all, float4 *__restrict__ proj_all, int kp_cap,
@@ -791,18 +754,6 @@ __global__ void __launch_bounds__(256) k_lf_rounds(const FrameDev *__restrict__ 
 // others (the map mutations that follow in Fuse stay on the host).  KeyFrame::GetFeaturesInArea (so@0x96fe0) is the
 // Frame cell walk without a level filter; KeyFrame::IsInImage (so@0x97480) is half-open.
 // ------------------------------------------------------------------------------------------------
-struct Pts3Dev { int m; const float *xw, *normal, *min_dist, *max_dist; const uint8_t *desc, *valid; };
-struct ProjKf {
-    float R[9], t[3];      // camera <- world
-    float R2[9], t2[3];    // second stage (SearchBySim3: sR21 / t21 applied to the camera-1 point)
-    float Ow[3];
-    float fx, fy, cx, cy, bf, log_scale;
-    float inv_sigma2[16];
-    int two_stage;         // 1: p = R2 * (R * xw + t) + t2, dist3D = |p|; 0: p = R * xw + t, dist3D = |xw - Ow|
-    int view_test;         // PO . Pn < 0.5 * dist3D rejects
-    int chi2;              // reprojection test of Fuse(KeyFrame*, ...)
-    int accept;            // TH_LOW / TH_HIGH
-};
 
 // gates of one map point: camera point, KeyFrame::IsInImage, invariance range, viewing angle; predicted level and search radius
 __device__ __forceinline__ bool project_gate(const FrameDev &F, const Pts3Dev &P, const ProjKf &C, float th, int i, float &u, float &v, float &invz,
@@ -968,17 +919,6 @@ __global__ void __launch_bounds__(256) k_sim3_agree(const int *__restrict__ vn1,
 // every feature has exactly one node at the chosen level) the nodes are independent and each thread takes whole
 // nodes.  Otherwise thread 0 replays the reference loop alone (same result, no parallelism).
 // ------------------------------------------------------------------------------------------------
-struct BowDev {
-    int n_kf, n_f;
-    const uint8_t *kf_desc, *f_desc;
-    const float *kf_angle, *f_angle;
-    const uint8_t *kf_has_mp, *f_has_mp;   // f_has_mp: second keyframe of the (KeyFrame, KeyFrame) overload, NULL for a Frame
-    int kf_nodes, f_nodes;
-    const uint32_t *kf_node_id, *f_node_id;
-    const int *kf_node_start, *f_node_start;
-    const int *kf_feat, *f_feat;
-};
-
 // one common node.  kfkf = 0: SearchByBoW(KeyFrame*, Frame&): slot = frame feature, value = keyframe feature, accept best <= TH_LOW.
 // kfkf = 1: SearchByBoW(KeyFrame*, KeyFrame*) (include/ORBmatcher.h:105, so@0x82cc0): slot = KF1 feature, value = KF2 feature,
 // KF2 features need a good map point and are marked in used2 (vbMatched2), accept best < TH_LOW (so@0x83490).
@@ -1009,7 +949,6 @@ __device__ __forceinline__ int bow_node(const BowDev &P, int a, int b, float nnr
 // kfkf = 2: ORBmatcher::SearchForTriangulation(pKF1, pKF2, F12, vMatchedPairs, bOnlyStereo)  include/ORBmatcher.h:111, so@0x86b30 -- the same node
 // walk; candidates are features WITHOUT a map point (kf_has_mp / f_has_mp = GetMapPoint(i) != NULL are skipped), gated by the epipole distance
 // (two mono key points) and ORBmatcher::CheckDistEpipolarLine (so@0x79b90, contractions as in the binary).
-struct TriDev { const plf_keypoint *keys1, *keys2; const float *uright1, *uright2, *scale2, *sigma2_2; float F[9]; float ex, ey; int only_stereo; };
 
 __device__ __forceinline__ bool check_dist_epipolar_line(const plf_keypoint &k1, const plf_keypoint &k2, const float *F, float level_sigma2)
 {
@@ -1159,7 +1098,6 @@ __global__ void __launch_bounds__(128) k_knn2(const uint8_t *__restrict__ q, int
 
 // the same brute-force 2-NN for a batch of current frames against ONE query set (the last frame's line descriptors): blockIdx.y = frame, the
 // frame's descriptors are staged through LDS in tiles of 128 so that every thread (= query) reads them as broadcasts
-struct LineFrameDev { int n; const int *n_dev; const plf_keyline *lines; const uint8_t *desc; const float *scale_factors; };
 __global__ void __launch_bounds__(128) k_knn2_batch(const uint8_t *__restrict__ q, int nq, const LineFrameDev *__restrict__ frames, int *__restrict__ idx_all,
                                                     int *__restrict__ dist_all, int stride)
 {
@@ -1251,7 +1189,6 @@ __global__ void __launch_bounds__(256) k_line_mad(const int *__restrict__ dist, 
 // Frame::lineDescriptorMAD + LSDmatcher::SearchByProjection(CurrentFrame, LastFrame); one block per current frame, nlast <= P2 (power of two)
 // tri != NULL: LSDmatcher::SearchForTriangulation (include/LSDmatcher.h:54) on the same 2-NN table -- queries = keyframe-1 lines, a pair (q, t) is kept
 // when neither line holds a MapLine (and, with only_stereo, both have stereo data); match_all[q] = t.
-struct LineTriDev { const uint8_t *has_ml1, *has_ml2, *stereo1, *stereo2; int only_stereo; };
 __global__ void __launch_bounds__(256) k_lines_lastframe(const int *__restrict__ idx_all, const int *__restrict__ dist_all, int nlast,
                                                          const uint8_t *__restrict__ last_has_mapline, int *__restrict__ match_all,
                                                          int *__restrict__ nmatches_all, int P2, int knn_stride, int line_stride,
@@ -1315,8 +1252,6 @@ __global__ void __launch_bounds__(256) k_lines_fuse_pick(const int *__restrict__
     const unsigned long long mk = __ballot(ok);
     if (plf_lane() == 0 && mk) atomicAdd(nfused, __popcll(mk));
 }
-
-struct MapLineDev { int m; const float *x1, *y1, *x2, *y2; const int *level; const float *view_cos; const uint8_t *in_view; const uint8_t *desc; };
 
 // Frame::GetLinesInArea test for line i
 __device__ __forceinline__ bool line_in_area(const plf_keyline &kl, float x1, float y1, float x2, float y2, float r, int minLevel, int maxLevel)

@@ -69,3 +69,19 @@ static inline void orb_part_rows(int ey0, int EH, int parts, int pi, int H, int 
     sh = sh < 0 ? 0 : (sh > srcH - 1 ? srcH - 1 : sh);
     *s_lo = sl; *s_hi = sh;
 }
+
+#ifdef __HIPCC__
+#include "plf_common.h"
+// the __constant__ tables of orb_kernels.hip, uploaded when a handle is created
+void plf_orb_upload_constants(const int *umax16);
+// batch driver (batch_host.hip): the status word of the batch just enqueued on `s`, copied to pinned host memory in stream order (orb_host.hip)
+int plf_orb_status_async(plf_orb *h, int32_t *host_dst, hipStream_t s);
+
+// ---- kernels launched by orb_host.hip (orb_front.hip, orb_octree.hip, orb_kernels.hip)
+__global__ void k_orb_level(const uint8_t *in, ptrdiff_t in_pitch, ptrdiff_t in_fstride, uint8_t *pyr, uint8_t *blur, int l, const int *xofs, const short2 *xa, const int *yofs, const short2 *yb,
+                            const int4 *cells, int2 *cellinfo, uint2 *pool, int *poolcnt, int *status, OrbGeom g, int4 taps);
+__global__ void k_octree(const int2 *cellinfo, const uint2 *pool, int *celloff, uint2 *keys_all, int *nodeof_all, uint8_t *quad_all, uint2 *sel, int *selcnt, int *ncand_dbg, int *status, OrbGeom g,
+                         int cap_nodes, int cap_sort);
+__global__ void k_orient_brief(const uint8_t *pyr, const uint8_t *blur, const uint2 *sel, const int *selcnt, plf_keypoint *kps, uint8_t *desc, int *n_out, int capacity, int *status, OrbGeom g,
+                               int nframes);
+#endif

@@ -12,14 +12,6 @@
 #include "plf_common.h"
 #include "orb_geom.h"
 
-// kernels (orb_kernels.hip, orb_octree.hip)
-void plf_orb_upload_constants(const int *umax16);
-__global__ void k_orb_level(const uint8_t *, ptrdiff_t, ptrdiff_t, uint8_t *, uint8_t *, int, const int *, const short2 *, const int *, const short2 *, const int4 *,
-                            int2 *, uint2 *, int *, int *, OrbGeom, int4);
-__global__ void k_octree(const int2 *, const uint2 *, int *, uint2 *, int *, uint8_t *, uint2 *, int *, int *, int *, OrbGeom, int, int);
-__global__ void k_orient_brief(const uint8_t *, const uint8_t *, const uint2 *, const int *, plf_keypoint *, uint8_t *, int *, int,
-                               int *, OrbGeom, int);
-
 struct plf_orb {
     plf_orb_params prm;
     int device;
