@@ -147,7 +147,7 @@ void plf_line_destroy(plf_line *h);
 /* Schedule knobs of a line-extractor handle (frames-in-flight thresholds of its schedules, band counts ...).  They are read from the environment ONCE, when the handle
  * is created (PLF_LSD_*, PLF_NFA_FUSED: experiments), and never again; this call changes one of them afterwards -- a tuning and test hook, not needed in production:
  * "spec_max" (frames in flight up to which the banded speculative schedule is used, 256), "spec_bands", "spec_z", "spec_rounds", "spec_halo", "spec_clip", "spec_fill",
- * "spec_fill_tol", "spec_stagger", "spec_nofuse", "spec_spins", "spec_reccap", "lat_max", "wpg", "slow_factor", "slow_floor_ms" (PLF_W_SLOW), "nfa_fused" (frames in flight up to which one wave per
+ * "spec_fill_tol", "spec_stagger", "spec_nofuse", "spec_spins", "spec_reccap", "lat_max", "wpg", "front_fork", "slow_factor", "slow_floor_ms" (PLF_W_SLOW), "nfa_fused" (frames in flight up to which one wave per
  * rectangle runs all NFA stages, 64).  Every schedule gives the same bits.  PLF_E_BADARG for an unknown name or a value out of range. */
 int plf_line_tune(plf_line *h, const char *name, double value);
 
@@ -187,6 +187,10 @@ int plf_line_debug_spec_rounds(plf_line *h, int32_t *out, int32_t n_frames);
 /* Diagnostics (tools/nfa_stats.py): out16[s] = rectangles of the last batch that entered rect_improve stage s (0..4; [5] = left over after stage 4), for batches
  * that took the staged NFA kernels (more than 64 frames in flight).  Synchronises the device. */
 int plf_line_debug_nfa_counters(plf_line *h, int32_t *out16);
+
+/* Test hook: the gradient plane the LBD descriptor of the last batch read, frame `frame` of it: dx / dy = the two cv::Sobel(CV_16S, 3 x 3) derivatives of octave 0
+ * of BinaryDescriptor's pyramid (PLF_LBD_BLURRED) or of the image itself (PLF_LBD_RAW), width x height values each, row-major.  Synchronises the device. */
+int plf_line_debug_gradient(plf_line *h, int32_t frame, int16_t *dx, int16_t *dy);
 
 /* Diagnostics (bench.py): out[f] = length of frame f's region-growing chain in the last batch = pixels left marked USED (accept steps minus the pixels
  * refine released again), n <= frames of that batch.  The launch of the one-wave-per-frame kernel lasts as long as its longest chain.  Zero for batches

@@ -76,6 +76,8 @@ struct LineTune {
     int nfa_two_pass;     // PLF_NFA_TWO_PASS     1: above nfa_fused frames in flight k_nfa_small only runs stage 0 and queues the undecided rectangles for k_nfa_small2 (stages 1-4)
     int nfa_table;        // PLF_NFA_TABLE        1: NFA values of rectangles of fewer than 512 pixels come from the per-image-size table (plf_nfa_table_host)
     int balance;          // PLF_LSD_BALANCE      1: large batches -- the frames are dealt to the waves of k_lsd_regions2 by chain length (k_lsd_balance); 0: in batch order
+    int front_fork;       // PLF_LSD_FRONT_FORK   1: the gradient pre-pass of k_lbd (k_blur5_sobel3 / k_sobel3) runs on the handle's side stream beside k_lsd_pre and is joined in
+                          //                      front of ev_front; 0: on the call's stream behind k_lsd_pre (AUTO: 1 for the batches that take k_lsd_regions2, see line_enqueue)
     float slow_factor;    // PLF_LSD_SLOW_FACTOR  PLF_W_SLOW: a host-output call that takes more than this many times the median per-frame time of the recent calls (10; 0: off)
     float slow_floor_ms;  // PLF_LSD_SLOW_FLOOR_MS  ... and more than this per frame (20 ms)
 };
@@ -104,6 +106,7 @@ static void line_tune_init(LineTune *t)
     t->nfa_small = tune_env_i("PLF_NFA_SMALL", 2);
     t->nfa_two_pass = tune_env_i("PLF_NFA_TWO_PASS", 1);
     t->balance = tune_env_i("PLF_LSD_BALANCE", 1);
+    t->front_fork = tune_env_i("PLF_LSD_FRONT_FORK", PLF_TUNE_AUTO);
 }
 
 struct plf_line {
@@ -167,6 +170,8 @@ struct plf_line {
     hipEvent_t prof_ev[2 * 512];  // (start, stop) pairs of the region kernel
     hipEvent_t ev_front;          // recorded after the front stages of the last batch (plf_line_wait_front)
     bool ev_front_set;
+    hipStream_t grad_stream;      // side stream of the gradient pre-pass (LineTune::front_fork), created on first use
+    hipEvent_t ev_fork, ev_grad;  // the call's stream at the top of the call -> grad_stream; the gradient plane written -> the call's stream
     uint8_t *h_pin;        // pinned staging of the host-output path for a few frames in flight (results of <= PIN_FRAMES frames come back in one go)
     size_t h_pin_bytes;
     double prof_ms;
@@ -194,6 +199,9 @@ static void line_free(plf_line *h)
     if (h->stream) (void)hipStreamDestroy(h->stream);
     for (int i = 0; i < 2 * 512; i++) if (h->prof_ev[i]) (void)hipEventDestroy(h->prof_ev[i]);
     if (h->ev_front) (void)hipEventDestroy(h->ev_front);
+    if (h->grad_stream) { (void)hipStreamSynchronize(h->grad_stream); (void)hipStreamDestroy(h->grad_stream); }
+    if (h->ev_fork) (void)hipEventDestroy(h->ev_fork);
+    if (h->ev_grad) (void)hipEventDestroy(h->ev_grad);
     if (h->h_pin) (void)hipHostFree(h->h_pin);
     free(h->retry_flags); h->retry_flags = nullptr;
     plf_order_free(h->order);
@@ -340,6 +348,10 @@ extern "C" int plf_line_create(const plf_line_params *p, plf_line **out)
         for (int i = 0; i < 7; i++) { const double x = i - 3.0; h->taps.k[i] = exp(scale2X * x * x); sum += h->taps.k[i]; }
         sum = 1. / sum;
         for (int i = 0; i < 7; i++) h->taps.k[i] *= sum;
+        // the row pass of k_lsd_pre shares the products of the taps q and 6 - q when they are the same bits (they are: exp of the same x * x, times the same sum);
+        // otherwise, and with PLF_LSD_ROW7 (test hook), it keeps a product per tap
+        h->taps.symmetric = tune_env_i("PLF_LSD_ROW7", 0) ? 0 : 1;
+        for (int i = 0; i < 3; i++) if (memcmp(&h->taps.k[i], &h->taps.k[6 - i], sizeof(double)) != 0) h->taps.symmetric = 0;
     }
     // cv::getGaussianKernel(5, 1, CV_32F) converted to 8-bit fixed point (createSeparableLinearFilter, 8U smoothing kernels): 14 63 103 63 14
     {
@@ -440,7 +452,7 @@ extern "C" int plf_line_tune(plf_line *h, const char *name, double value)
     const int v = (int)value;
     struct { const char *n; int *p; } ints[] = {{"lat_max", &t.lat_max}, {"spec_bands", &t.spec_bands}, {"spec_max", &t.spec_max}, {"spec_z", &t.spec_z},
         {"spec_rounds", &t.spec_rounds}, {"spec_halo", &t.spec_halo}, {"spec_fill", &t.spec_fill}, {"spec_clip", &t.spec_clip}, {"spec_nofuse", &t.spec_nofuse},
-        {"spec_spins", &t.spec_spins}, {"spec_reccap", &t.spec_reccap}, {"wpg", &t.wpg}, {"nfa_fused", &t.nfa_fused}, {"nfa_table", &t.nfa_table}, {"nfa_small", &t.nfa_small}, {"nfa_two_pass", &t.nfa_two_pass}, {"balance", &t.balance}};
+        {"spec_spins", &t.spec_spins}, {"spec_reccap", &t.spec_reccap}, {"wpg", &t.wpg}, {"nfa_fused", &t.nfa_fused}, {"nfa_table", &t.nfa_table}, {"nfa_small", &t.nfa_small}, {"nfa_two_pass", &t.nfa_two_pass}, {"balance", &t.balance}, {"front_fork", &t.front_fork}};
     for (auto &e : ints)
         if (!strcmp(name, e.n)) {
             if (!strcmp(name, "spec_rounds") && (v < 1 || v > 64)) return PLF_E_BADARG;
@@ -448,6 +460,7 @@ extern "C" int plf_line_tune(plf_line *h, const char *name, double value)
             if (!strcmp(name, "spec_spins") && v < 64) return PLF_E_BADARG;
             if (!strcmp(name, "wpg") && v != PLF_TUNE_AUTO && (v < 1 || v > 16)) return PLF_E_BADARG;
             if (!strcmp(name, "spec_bands") && v != PLF_TUNE_AUTO && (v < 0 || v > 64)) return PLF_E_BADARG;   // (0 / 1: speculation off; the call clamps to what the frame allows)
+            if (!strcmp(name, "front_fork") && v != PLF_TUNE_AUTO && (v < 0 || v > 1)) return PLF_E_BADARG;
             if ((!strcmp(name, "nfa_small") && (v < 0 || v > 2)) || ((!strcmp(name, "nfa_table") || !strcmp(name, "nfa_two_pass") || !strcmp(name, "balance")) && (v < 0 || v > 1)))
                 return PLF_E_BADARG;
             *e.p = v;
@@ -474,6 +487,19 @@ extern "C" void plf_line_destroy(plf_line *h)
 // 21.6 k -> 22.4 k with 4; from 2048 on the launch fills the chip either way and 8 keeps the LDS of a CU for the co-running tiles.
 static int line_wpg(const LineTune &T, int B) { return T.wpg != PLF_TUNE_AUTO ? T.wpg : (B <= 768 ? 2 : B <= 1536 ? 4 : 8); }
 
+// The side stream of the gradient pre-pass and its two events, on first use.  Non-blocking, at the device's highest priority: not below whatever stream the
+// caller gives the line extractor (the gradient plane is joined in front of ev_front, so it paces that stream).
+static int line_front_fork_init(plf_line *h)
+{
+    if (h->grad_stream) return PLF_OK;
+    int least = 0, greatest = 0;
+    PLF_HIP_TRY(hipDeviceGetStreamPriorityRange(&least, &greatest));
+    if (!h->ev_fork) PLF_HIP_TRY(hipEventCreateWithFlags(&h->ev_fork, hipEventDisableTiming));
+    if (!h->ev_grad) PLF_HIP_TRY(hipEventCreateWithFlags(&h->ev_grad, hipEventDisableTiming));
+    PLF_HIP_TRY(hipStreamCreateWithPriority(&h->grad_stream, hipStreamNonBlocking, greatest));
+    return PLF_OK;
+}
+
 static int line_enqueue(plf_line *h, const uint8_t *d_gray, int B, ptrdiff_t pitch, ptrdiff_t fstride, plf_keyline *d_lines, uint8_t *d_ldesc,
                         double *d_eq, int *d_nout, int capacity, hipStream_t s)
 {
@@ -481,6 +507,19 @@ static int line_enqueue(plf_line *h, const uint8_t *d_gray, int B, ptrdiff_t pit
     const size_t MB = (size_t)h->prm.max_batch;
     int *nrect = h->d_counters, *nseg = h->d_counters + MB, *status = h->d_counters + 3 * MB, *nfail_unused = h->d_counters + 3 * MB + 16;
     (void)nfail_unused;
+    // The gradient pre-pass feeds only k_lbd, the last kernel of the call: with front_fork it runs on the side stream BESIDE k_lsd_pre instead of alone behind it.
+    // AUTO: the batches that take k_lsd_regions2 (beyond the speculative and the latency schedule) -- there the front stages are throughput-bound launches of
+    // thousands of workgroups; few frames in flight keep the single-stream order (two more events and a second queue on a call of a few ms).
+    // d_grad between calls: the fork event of call k+1 is recorded on its stream behind call k's k_lbd (the same stream, or one that waited in plf_order_begin),
+    // so the next writer of the plane is ordered behind its last reader like every other buffer of the handle.
+    const bool fork = h->tune.front_fork != PLF_TUNE_AUTO ? h->tune.front_fork : (B > h->tune.spec_max && B > h->tune.lat_max);
+    hipStream_t sg = s;   // the stream of the gradient pre-pass
+    if (fork) {
+        PLF_TRY(line_front_fork_init(h));
+        sg = h->grad_stream;
+        PLF_HIP_TRY(hipEventRecord(h->ev_fork, s));
+        PLF_HIP_TRY(hipStreamWaitEvent(sg, h->ev_fork, 0));
+    }
     PLF_HIP_TRY(hipMemsetAsync(status, 0, (16 + MB) * sizeof(int), s));
     // large batches (the one-wave-per-frame kernel k_lsd_regions2): the frames are dealt to its waves by chain length = defined pixels, counted by k_lsd_pre
     const bool balance = h->tune.balance && B > h->tune.spec_max && B > h->tune.lat_max && B <= 65536 && h->prm.seed_order == 0;
@@ -498,9 +537,18 @@ static int line_enqueue(plf_line *h, const uint8_t *d_gray, int B, ptrdiff_t pit
         hipLaunchKernelGGL(k_lsd_balance, dim3((B + 255) / 256), dim3(256), 0, s, d_cost, d_perm, B, wpg);
     }
     if (h->prm.lbd_sobel_input == PLF_LBD_RAW)
-        hipLaunchKernelGGL(k_sobel3, dim3((((g.w + 3) / 4) * g.h + 255) / 256, 1, B), dim3(256), 0, s, d_gray, pitch, fstride, h->d_grad, g);
-    else
-        hipLaunchKernelGGL(k_blur5_sobel3, dim3((g.w + BS_TW - 1) / BS_TW, (g.h + BS_TH - 1) / BS_TH, B), dim3(256), 0, s, d_gray, pitch, fstride, h->d_grad, g, h->blur5);
+        hipLaunchKernelGGL(k_sobel3, dim3((((g.w + 3) / 4) * g.h + 255) / 256, 1, B), dim3(256), 0, sg, d_gray, pitch, fstride, h->d_grad, g);
+    else {
+        const int rows = plf_bs_rows(g.h, B);
+        hipLaunchKernelGGL(k_blur5_sobel3, dim3(((g.w + 3) / 4 + BS_GV - 1) / BS_GV, (plf_bs_bands(g.h, rows) + 3) / 4, B), dim3(256), 0, sg, d_gray, pitch, fstride, h->d_grad, g,
+                           h->blur5, rows);
+    }
+    if (fork) {
+        // joined HERE: ev_front then covers the whole front and the region kernel still follows it back to back (see above).  (A join in front of k_lbd instead
+        // measured the same step within the run-to-run spread, profiles/line_front.txt, and would let left-over Sobel workgroups compete with the region launch.)
+        PLF_HIP_TRY(hipEventRecord(h->ev_grad, sg));
+        PLF_HIP_TRY(hipStreamWaitEvent(s, h->ev_grad, 0));
+    }
     if (!h->ev_front) PLF_HIP_TRY(hipEventCreateWithFlags(&h->ev_front, hipEventDisableTiming));
     PLF_HIP_TRY(hipEventRecord(h->ev_front, s));
     h->ev_front_set = true;
@@ -1003,6 +1051,20 @@ extern "C" int plf_line_debug_nfa_counters(plf_line *h, int32_t *out16)
     if (!h || !out16 || !h->d_nfa_counters) return PLF_E_BADARG;
     PLF_HIP_TRY(hipDeviceSynchronize());
     PLF_HIP_TRY(hipMemcpy(out16, h->d_nfa_counters, 16 * sizeof(int), hipMemcpyDeviceToHost));
+    return PLF_OK;
+}
+
+// test hook: the gradient plane k_lbd read in the last batch -- frame's (dx, dy) of cv::Sobel on the image the descriptor uses (plf_line_params.lbd_sobel_input),
+// width x height values each
+extern "C" int plf_line_debug_gradient(plf_line *h, int32_t frame, int16_t *dx, int16_t *dy)
+{
+    if (!h || !dx || !dy || frame < 0 || frame >= h->last_frames || h->cur_w <= 0) return PLF_E_BADARG;
+    PLF_HIP_TRY(hipSetDevice(h->device));
+    PLF_HIP_TRY(hipDeviceSynchronize());
+    const size_t n = (size_t)h->g.w * h->g.h;
+    std::vector<short2> tmp(n);
+    PLF_HIP_TRY(hipMemcpy(tmp.data(), h->d_grad + (size_t)frame * h->g.full_stride, n * sizeof(short2), hipMemcpyDeviceToHost));
+    for (size_t i = 0; i < n; i++) { dx[i] = tmp[i].x; dy[i] = tmp[i].y; }
     return PLF_OK;
 }
 

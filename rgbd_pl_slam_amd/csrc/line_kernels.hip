@@ -144,142 +144,124 @@ __global__ void __launch_bounds__(256) k_sobel3(const uint8_t *__restrict__ in, 
 }
 
 // BinaryDescriptor::computeGaussianPyramid (opencv_contrib 3.3): octave 0 = cv::GaussianBlur(image.clone(), Size(5, 5), 1), then the two
-// cv::Sobel calls read THAT image (plf_line_params.lbd_sobel_input = PLF_LBD_BLURRED).  Fused: a 256-thread block produces a 64 x BS_TH tile of
-// (dx, dy); the 5-tap row sums (BS_TH + 6 rows x 66), the blurred bytes (BS_TH + 2 rows x 66) and nothing else live in LDS -- the blurred image never reaches HBM.
+// cv::Sobel calls read THAT image (plf_line_params.lbd_sobel_input = PLF_LBD_BLURRED).  Fused; the blurred image never reaches HBM.
 // 8U GaussianBlur = 8-bit fixed-point separable filter: taps k5 (14 63 103 63 14), row pass exact int32, column pass sum / 65536 rounded as
 // OpenCV 3.3's SymmColumnVec_32s8u does (half-to-even) for x < (w & ~3) and as its scalar tail ((s + 32768) >> 16) for the last w % 4
 // columns -- the same rule as the 7 x 7 blur of the ORB path (orb_kernels.hip); REFLECT_101 at the image edge for the blur AND for the Sobel.
-// Every phase works on groups of 4 pixels: the raw bytes of the tile are staged in LDS with dword loads (396 per tile; round 1 of this kernel issued
-// 7260 single-byte global loads per tile and ran at 1 TB/s), the 5-tap row sums are one v_dot4_u32_u8 + one multiply-add per pixel on byte windows
-// cut out with v_alignbyte, the column pass reads int4 row-sum vectors, the Sobel reads two dwords per row for 4 pixels.  The staged bytes are already
-// mirrored (REFLECT_101) at the image border, so the row pass has no border case.
-// (BS_TW, BS_TH: lsd_geom.h)
-#define BS_RAWW 80   // staged bytes per row: image x0 - 4 .. x0 + 75
-#define BS_RSW 68    // row sums per row:    image x0 - 1 .. x0 + 66 (66 used)
-#define BS_BLW 72    // blurred bytes per row: image x0 - 1 .. (68 written, 66 used)
-// INNER: the tile's rows y0 - 3 .. y0 + BS_TH + 2 all lie inside the image (every tile but the first and last row of tiles): no row is reflected, no row test
-template <bool INNER>
-__device__ __forceinline__ void blur5_sobel3_tile(const uint8_t *__restrict__ img, ptrdiff_t pitch, short2 *__restrict__ gout, int W, int H, int x0, int y0, int t, int4 k5,
-                                                  uint8_t (*raw)[BS_RAWW], int (*rows)[BS_RSW], uint8_t (*blur)[BS_BLW])
-{
-    // ---- 0. raw bytes, mirrored in x
-    for (int i = t; i < (BS_TH + 6) * (BS_RAWW / 4); i += 256) {
-        const int r = i / (BS_RAWW / 4), i4 = i - r * (BS_RAWW / 4);
-        const int Y = y0 - 3 + r, X4 = x0 - 4 + 4 * i4;
-        if (!INNER && (Y < 0 || Y >= H)) continue;   // only reached through reflection, which lands inside the image
-        const uint8_t *S = img + (size_t)Y * pitch;
-        uint32_t v;
-        if (X4 >= 0 && X4 + 3 < W) v = *(const plf_u32u *)(S + X4);
-        else {
-            v = 0;
-#pragma unroll
-            for (int j = 0; j < 4; j++) v |= (uint32_t)S[plf_reflect101(X4 + j, W)] << (8 * j);
-        }
-        *reinterpret_cast<uint32_t *>(&raw[r][4 * i4]) = v;
-    }
-    __syncthreads();
-    // ---- 1. row sums s(X) = k0 (S[X-2] + S[X+2]) + k1 (S[X-1] + S[X+1]) + k2 S[X], 4 per item: X = x0 - 1 + c has its taps at staged columns c + 1 .. c + 5
-    {
-        const uint32_t K = (uint32_t)k5.x | ((uint32_t)k5.y << 8) | ((uint32_t)k5.z << 16) | ((uint32_t)k5.y << 24);
-        for (int i = t; i < (BS_TH + 6) * (BS_RSW / 4); i += 256) {
-            const int r = i / (BS_RSW / 4), g4 = i - r * (BS_RSW / 4);
-            const int Y = y0 - 3 + r;
-            if (!INNER && (Y < 0 || Y >= H)) continue;
-            const uint32_t *rp = reinterpret_cast<const uint32_t *>(&raw[r][4 * g4]);
-            const uint32_t w0 = rp[0], w1 = rp[1], w2 = rp[2];
-            int4 o;
-            o.x = (int)__builtin_amdgcn_udot4(__builtin_amdgcn_alignbyte(w1, w0, 1), K, (uint32_t)k5.x * ((w1 >> 8) & 0xFFu), false);
-            o.y = (int)__builtin_amdgcn_udot4(__builtin_amdgcn_alignbyte(w1, w0, 2), K, (uint32_t)k5.x * ((w1 >> 16) & 0xFFu), false);
-            o.z = (int)__builtin_amdgcn_udot4(__builtin_amdgcn_alignbyte(w1, w0, 3), K, (uint32_t)k5.x * (w1 >> 24), false);
-            o.w = (int)__builtin_amdgcn_udot4(w1, K, (uint32_t)k5.x * (w2 & 0xFFu), false);
-            *reinterpret_cast<int4 *>(&rows[r][4 * g4]) = o;
-        }
-    }
-    __syncthreads();
-    // ---- 2. column pass + OpenCV's rounding, 4 per item
-    {
-        const int wvec = W & ~3;
-        for (int i = t; i < (BS_TH + 2) * (BS_RSW / 4); i += 256) {
-            const int r = i / (BS_RSW / 4), g4 = i - r * (BS_RSW / 4);
-            const int Y = y0 - 1 + r;
-            if (!INNER && (Y < 0 || Y >= H)) continue;
-#define ROW_(yy) (*reinterpret_cast<const int4 *>(&rows[(INNER ? (yy) : plf_reflect101((yy), H)) - (y0 - 3)][4 * g4]))
-            const int4 a = ROW_(Y - 2), b = ROW_(Y - 1), c = ROW_(Y), d = ROW_(Y + 1), e = ROW_(Y + 2);
-#undef ROW_
-#define COL_(m) ((int)(__umul24(k5.x, a.m + e.m) + __umul24(k5.y, b.m + d.m) + __umul24(k5.z, c.m)))   // (row sums <= 255 * 257: 24-bit multiplies are exact)
-            const int sv[4] = {COL_(x), COL_(y), COL_(z), COL_(w)};
-#undef COL_
-            uint32_t out = 0;
-#pragma unroll
-            for (int j = 0; j < 4; j++) {
-                const int X = x0 - 1 + 4 * g4 + j, s_ = sv[j];
-                // half to even = (s + 0x7FFF + bit 16 of s) >> 16 (as in the 7x7 blur of the ORB path); the scalar tail rounds half up
-                const int v = (s_ + 0x7FFF + (((s_ >> 16) & 1) | (X < wvec ? 0 : 1))) >> 16;
-                out |= (uint32_t)(v > 255 ? 255 : v) << (8 * j);
-            }
-            *reinterpret_cast<uint32_t *>(&blur[r][4 * g4]) = out;
-        }
-    }
-    __syncthreads();
-    // ---- 3. the two 3 x 3 Sobel derivatives of the blurred image, 4 pixels per item (BS_TH rows x 16 groups)
-    for (int it = t; it < BS_TH * 16; it += 256) {
-        const int ry = it >> 4, cx = (it & 15) * 4;
-        const int x = x0 + cx, y = y0 + ry;
-        if (x >= W || y >= H) continue;
-        const int ym = INNER ? ry : plf_reflect101(y - 1, H) - (y0 - 1), yc = ry + 1, yp = INNER ? ry + 2 : plf_reflect101(y + 1, H) - (y0 - 1);
-        short2 *out = gout + (size_t)y * W + x;
-        if (x >= 1 && x + 4 < W) {   // blurred columns x - 1 .. x + 4 exist: blur[][cx .. cx + 5]
-            // Packed 16-bit lanes (round 4; the scalar form extracted 36 bytes and did ~100 instructions per 4 pixels, a third of the kernel): the bytes b0..b5 of
-            // a row as pairs P01 P23 P45 (and Q12 Q34 for the rows' own sums), column sums C = top + 2 mid + bottom per pair, gx[j] = C[j+2] - C[j];
-            // row sums T = P + 2 Q + P', gy = bottom - top.  All values fit 11 bits + sign.
-            typedef short s2v __attribute__((ext_vector_type(2)));
-#define PERM_(hi, lo, sel) __builtin_bit_cast(s2v, __builtin_amdgcn_perm((hi), (lo), (sel)))
-            const uint32_t t0 = *reinterpret_cast<const uint32_t *>(&blur[ym][cx]), t1 = *reinterpret_cast<const uint32_t *>(&blur[ym][cx + 4]);
-            const uint32_t m0 = *reinterpret_cast<const uint32_t *>(&blur[yc][cx]), m1 = *reinterpret_cast<const uint32_t *>(&blur[yc][cx + 4]);
-            const uint32_t b0 = *reinterpret_cast<const uint32_t *>(&blur[yp][cx]), b1 = *reinterpret_cast<const uint32_t *>(&blur[yp][cx + 4]);
-            const s2v two = {2, 2};
-            const s2v tP01 = PERM_(0u, t0, 0x0C010C00u), tP23 = PERM_(0u, t0, 0x0C030C02u), tP45 = PERM_(0u, t1, 0x0C010C00u);
-            const s2v tQ12 = PERM_(0u, t0, 0x0C020C01u), tQ34 = PERM_(t1, t0, 0x0C040C03u);
-            const s2v mP01 = PERM_(0u, m0, 0x0C010C00u), mP23 = PERM_(0u, m0, 0x0C030C02u), mP45 = PERM_(0u, m1, 0x0C010C00u);
-            const s2v bP01 = PERM_(0u, b0, 0x0C010C00u), bP23 = PERM_(0u, b0, 0x0C030C02u), bP45 = PERM_(0u, b1, 0x0C010C00u);
-            const s2v bQ12 = PERM_(0u, b0, 0x0C020C01u), bQ34 = PERM_(b1, b0, 0x0C040C03u);
-            const s2v C01 = mP01 * two + tP01 + bP01, C23 = mP23 * two + tP23 + bP23, C45 = mP45 * two + tP45 + bP45;
-            const s2v gx01 = C23 - C01, gx23 = C45 - C23;
-            const s2v T01 = tQ12 * two + tP01 + tP23, T23 = tQ34 * two + tP23 + tP45;
-            const s2v B01 = bQ12 * two + bP01 + bP23, B23 = bQ34 * two + bP23 + bP45;
-            const s2v gy01 = B01 - T01, gy23 = B23 - T23;
-            const uint32_t X01 = __builtin_bit_cast(uint32_t, gx01), Y01 = __builtin_bit_cast(uint32_t, gy01);
-            const uint32_t X23 = __builtin_bit_cast(uint32_t, gx23), Y23 = __builtin_bit_cast(uint32_t, gy23);
-            uint4 o4;   // (gx, gy) of pixels 0..3 as short2 each
-            o4.x = __builtin_amdgcn_perm(Y01, X01, 0x05040100u); o4.y = __builtin_amdgcn_perm(Y01, X01, 0x07060302u);
-            o4.z = __builtin_amdgcn_perm(Y23, X23, 0x05040100u); o4.w = __builtin_amdgcn_perm(Y23, X23, 0x07060302u);
-#undef PERM_
-            plf_short8 v;
-            v.a = __builtin_bit_cast(short2, o4.x); v.b = __builtin_bit_cast(short2, o4.y); v.c = __builtin_bit_cast(short2, o4.z); v.d = __builtin_bit_cast(short2, o4.w);
-            *(plf_short8 *)out = v;
-            continue;
-        }
-        for (int j = 0; j < 4 && x + j < W; j++) {
-            const int xx = x + j;
-            const int xm = plf_reflect101(xx - 1, W) - (x0 - 1), xc = cx + j + 1, xp = plf_reflect101(xx + 1, W) - (x0 - 1);
-            const int gx = (blur[ym][xp] + 2 * blur[yc][xp] + blur[yp][xp]) - (blur[ym][xm] + 2 * blur[yc][xm] + blur[yp][xm]);
-            const int gy = (blur[yp][xm] + 2 * blur[yp][xc] + blur[yp][xp]) - (blur[ym][xm] + 2 * blur[ym][xc] + blur[ym][xp]);
-            out[j] = make_short2((short)gx, (short)gy);
-        }
-    }
-}
+//
+// Row-walking form (the shape of k_orb_level's blur): a lane owns 4 columns and walks down a band of `rb` rows; everything it carries from row to row lives in
+// registers -- the 5 live rows of row sums, and of the Sobel the horizontal difference d and the horizontal 1-2-1 sum h of the two previous blurred rows as packed
+// int16 pairs: gx(y) = d(y-1) + 2 d(y) + d(y+1), gy(y) = h(y+1) - h(y-1).  No LDS and no barrier: the only thing neighbouring column groups exchange is the
+// blurred dword of the row, by two ds_bpermute.  Lanes 0 and 63 of a wave only feed their neighbours, so a wave writes BS_GV = 62 groups = 248 columns.
+// (The four-phase LDS tile this replaces spent 66 lane-instructions per pixel, most of them index divisions per item and byte unpacking per output row.)
+//   * one unaligned 8-byte load per lane and row: the bytes x - 2 .. x + 5 of the 5-tap windows of 4 pixels.  At the left / right image border the load is moved
+//     inside the row (column lc) and two v_perm put every window byte where the interior has it, REFLECT_101 included: the selectors are settled once per lane,
+//     the row loop has no border case.  (w >= 10 -- the extractor refuses narrower images, line_geometry -- so the 8 bytes always exist.)
+//   * row sums: per pixel one v_dot4 with (k0 k1 k2 k1) on the window cut out with v_alignbyte, and the fifth tap as a second v_dot4 whose constant holds k0 in
+//     the byte of that tap -- no byte extract, no multiply.
+//   * rows: the walk runs over the VIRTUAL rows y0 - 3 .. y1 + 2 and loads row reflect(v).  The blurred row -1 the Sobel wants is blurred row 1 (and H is H - 2):
+//     with symmetric taps and exact integer sums the blur of the mirrored virtual rows around -1 IS the blur around 1, so the top and bottom of the image are no
+//     special case either.
+//   * the Sobel's column border (x - 1 < 0, x + 1 >= w) is again a matter of three per-lane selectors of the v_perm that unpack the blurred bytes.
+typedef short bs_s2v __attribute__((ext_vector_type(2)));
+struct BsRow { bs_s2v d01, d23, h01, h23; };   // per blurred row, pixels (0, 1) and (2, 3) of the lane: d = right - left neighbour, h = left + 2 centre + right
 
 __global__ void __launch_bounds__(256) k_blur5_sobel3(const uint8_t *__restrict__ in, ptrdiff_t pitch, ptrdiff_t fstride, short2 *__restrict__ grad,
-                                                      LsdGeom g, int4 k5 /* k[0], k[1], k[2] */)
+                                                      LsdGeom g, int4 k5 /* k[0], k[1], k[2] */, int rb)
 {
-    __shared__ __attribute__((aligned(16))) uint8_t raw[BS_TH + 6][BS_RAWW];   // image (x0 - 4 + i, y0 - 3 + r)
-    __shared__ __attribute__((aligned(16))) int rows[BS_TH + 6][BS_RSW];       // row sums at image (x0 - 1 + c, y0 - 3 + r)
-    __shared__ __attribute__((aligned(16))) uint8_t blur[BS_TH + 2][BS_BLW];   // blurred bytes at image (x0 - 1 + c, y0 - 1 + r)
-    const int x0 = blockIdx.x * BS_TW, y0 = blockIdx.y * BS_TH, f = blockIdx.z, t = threadIdx.x;
-    const uint8_t *img = in + (size_t)f * fstride;
-    short2 *gout = grad + (size_t)f * g.full_stride;
-    if (y0 >= 3 && y0 + BS_TH + 3 <= g.h) blur5_sobel3_tile<true>(img, pitch, gout, g.w, g.h, x0, y0, t, k5, raw, rows, blur);
-    else blur5_sobel3_tile<false>(img, pitch, gout, g.w, g.h, x0, y0, t, k5, raw, rows, blur);
+    const int W = g.w, H = g.h, lane = threadIdx.x & 63;
+    const int band = blockIdx.y * 4 + __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    const int y0 = band * rb;
+    if (y0 >= H) return;
+    const int y1 = min(y0 + rb, H);   // the band writes rows y0 .. y1 - 1
+    const int x = 4 * ((int)blockIdx.x * BS_GV + lane - 1);   // (-4 and columns beyond the image: lanes that only keep the wave's lanes aligned)
+    const uint8_t *img = in + (size_t)blockIdx.z * fstride;
+    // ---- settled once per lane: where the 8 source bytes come from, and the byte selectors
+    const int lc = min(max(x - 2, 0), W - 8);
+    uint32_t sel_lo = 0, sel_hi = 0;
+#pragma unroll
+    for (int j = 0; j < 8; j++) {
+        const uint32_t idx = (uint32_t)min(max(plf_reflect101(x - 2 + j, W) - lc, 0), 7);   // (clamped: only for pixels outside the image)
+        if (j < 4) sel_lo |= idx << (8 * j); else sel_hi |= idx << (8 * (j - 4));
+    }
+    // blurred bytes p0 .. p5 = columns x - 1 .. x + 4 from the dwords of the left neighbour (bytes 4..7 of the first two v_perm), this lane (0..3) and the right
+    // neighbour (4..7 of the third): pairs (p0 p1) (p2 p3) (p4 p5) as int16 lanes; a column outside the image is the one mirrored at the border column
+    const int jl = W - 1 - x;   // the lane's pixel that is the last column of the image, if 0..3
+    const uint32_t sel01 = x == 0 ? 0x0C000C01u : 0x0C000C07u;
+    const uint32_t sel23 = jl == 1 ? 0x0C000C01u : jl == 0 ? 0x0C020C07u : 0x0C020C01u;
+    const uint32_t sel45 = jl == 3 ? 0x0C020C03u : jl == 2 ? 0x0C040C01u : 0x0C040C03u;
+    const int addr_l = ((lane + 63) & 63) << 2, addr_r = ((lane + 1) & 63) << 2;
+    const bool tail = x >= (W & ~3);   // the w % 4 tail columns round half up (a whole group: x and w & ~3 are multiples of 4)
+    const bool writes = lane >= 1 && lane <= BS_GV && x >= 0 && x < W;
+    const uint32_t K = (uint32_t)k5.x | ((uint32_t)k5.y << 8) | ((uint32_t)k5.z << 16) | ((uint32_t)k5.y << 24), K0 = (uint32_t)k5.x;
+    short2 *out = grad + (size_t)blockIdx.z * g.full_stride + x;
+
+#define BS_LOAD(v) (*(const plf_u64u *)(img + (size_t)plf_reflect101((v), H) * pitch + lc))
+    // 5-tap row sums of the lane's 4 pixels from the 8 source bytes
+#define BS_ROWSUM(raw, o)                                                                                                     \
+    do {                                                                                                                      \
+        const uint32_t lo_ = __builtin_amdgcn_perm((uint32_t)((raw) >> 32), (uint32_t)(raw), sel_lo);                         \
+        const uint32_t hi_ = __builtin_amdgcn_perm((uint32_t)((raw) >> 32), (uint32_t)(raw), sel_hi);                         \
+        (o).x = (int)__builtin_amdgcn_udot4(lo_, K, __builtin_amdgcn_udot4(hi_, K0, 0u, false), false);                        \
+        (o).y = (int)__builtin_amdgcn_udot4(__builtin_amdgcn_alignbyte(hi_, lo_, 1), K, __builtin_amdgcn_udot4(hi_, K0 << 8, 0u, false), false);  \
+        (o).z = (int)__builtin_amdgcn_udot4(__builtin_amdgcn_alignbyte(hi_, lo_, 2), K, __builtin_amdgcn_udot4(hi_, K0 << 16, 0u, false), false); \
+        (o).w = (int)__builtin_amdgcn_udot4(__builtin_amdgcn_alignbyte(hi_, lo_, 3), K, __builtin_amdgcn_udot4(hi_, K0 << 24, 0u, false), false); \
+    } while (0)
+    // One step = blurred virtual row vb from the row sums of the virtual rows vb - 2 .. vb + 2 (ra .. re; re is filled here), its d and h, and from vb = y0 + 1 on
+    // the output row vb - 1.  Column pass + OpenCV's rounding: half to even = (s + 0x7FFF + bit 16 of s) >> 16 (as in the 7x7 blur of the ORB path); the scalar
+    // tail rounds half up.  (Row sums <= 255 * 257: the 24-bit multiplies are exact.)  The source row is loaded one step ahead of its use; the last load is
+    // for nothing, inside the image like every other.
+#define BS_COL(ra, rb, rc, rd, re, m) ((int)(__umul24(k5.x, ra.m + re.m) + __umul24(k5.y, rb.m + rd.m) + __umul24(k5.z, rc.m)))
+#define BS_RND(s_) min(((s_) + 0x7FFF + ((((s_) >> 16) & 1) | (tail ? 1 : 0))) >> 16, 255)
+#define BS_PERM(hi, lo, sel) __builtin_bit_cast(bs_s2v, __builtin_amdgcn_perm((hi), (lo), (sel)))
+#define BS_STEP(ra, rb, rc, rd, re)                                                                                                                        \
+    do {                                                                                                                                                   \
+        const unsigned long long nxt_ = BS_LOAD(vb + 3);                                                                                                   \
+        BS_ROWSUM(cur, re);                                                                                                                                \
+        cur = nxt_;                                                                                                                                        \
+        const int s0_ = BS_COL(ra, rb, rc, rd, re, x), s1_ = BS_COL(ra, rb, rc, rd, re, y), s2_ = BS_COL(ra, rb, rc, rd, re, z), s3_ = BS_COL(ra, rb, rc, rd, re, w); \
+        const uint32_t m_ = (uint32_t)BS_RND(s0_) | ((uint32_t)BS_RND(s1_) << 8) | ((uint32_t)BS_RND(s2_) << 16) | ((uint32_t)BS_RND(s3_) << 24);          \
+        const uint32_t ld_ = (uint32_t)__builtin_amdgcn_ds_bpermute(addr_l, (int)m_), rd_ = (uint32_t)__builtin_amdgcn_ds_bpermute(addr_r, (int)m_);       \
+        const bs_s2v P01 = BS_PERM(ld_, m_, sel01), P23 = BS_PERM(ld_, m_, sel23), P45 = BS_PERM(rd_, m_, sel45);                                          \
+        const bs_s2v Q12 = BS_PERM(0u, m_, 0x0C010C00u), Q34 = BS_PERM(0u, m_, 0x0C030C02u);                                                               \
+        BsRow N;                                                                                                                                           \
+        N.d01 = P23 - P01; N.d23 = P45 - P23;                                                                                                              \
+        N.h01 = Q12 * two + P01 + P23; N.h23 = Q34 * two + P23 + P45;                                                                                      \
+        if (vb > y0 && writes) {                                                                                                                           \
+            const bs_s2v gx01 = B.d01 * two + A.d01 + N.d01, gx23 = B.d23 * two + A.d23 + N.d23;                                                           \
+            const bs_s2v gy01 = N.h01 - A.h01, gy23 = N.h23 - A.h23;                                                                                       \
+            const uint32_t X01 = __builtin_bit_cast(uint32_t, gx01), Y01 = __builtin_bit_cast(uint32_t, gy01);                                             \
+            const uint32_t X23 = __builtin_bit_cast(uint32_t, gx23), Y23 = __builtin_bit_cast(uint32_t, gy23);                                             \
+            plf_short8 v;   /* (gx, gy) of pixels 0..3 as short2 each */                                                                                   \
+            v.a = __builtin_bit_cast(short2, __builtin_amdgcn_perm(Y01, X01, 0x05040100u)); v.b = __builtin_bit_cast(short2, __builtin_amdgcn_perm(Y01, X01, 0x07060302u)); \
+            v.c = __builtin_bit_cast(short2, __builtin_amdgcn_perm(Y23, X23, 0x05040100u)); v.d = __builtin_bit_cast(short2, __builtin_amdgcn_perm(Y23, X23, 0x07060302u)); \
+            short2 *o = out + (size_t)(vb - 1) * W;                                                                                                        \
+            if (__builtin_expect(jl >= 3, 1)) *(plf_short8 *)o = v;                                                                                        \
+            else { o[0] = v.a; if (jl >= 1) o[1] = v.b; if (jl >= 2) o[2] = v.c; }                                                                         \
+        }                                                                                                                                                  \
+        A = B; B = N;                                                                                                                                      \
+    } while (0)
+    int4 r0, r1, r2, r3, r4;   // row sums of five consecutive virtual rows, rotating (the loop is unrolled 5 times so that the rotation is a matter of names)
+    { const unsigned long long q = BS_LOAD(y0 - 3); BS_ROWSUM(q, r0); }
+    { const unsigned long long q = BS_LOAD(y0 - 2); BS_ROWSUM(q, r1); }
+    { const unsigned long long q = BS_LOAD(y0 - 1); BS_ROWSUM(q, r2); }
+    { const unsigned long long q = BS_LOAD(y0); BS_ROWSUM(q, r3); }
+    unsigned long long cur = BS_LOAD(y0 + 1);
+    BsRow A = {}, B = {};   // blurred rows vb - 2 and vb - 1
+    const bs_s2v two = {2, 2};
+    for (int vb = y0 - 1;;) {   // blurred virtual rows y0 - 1 .. y1
+        BS_STEP(r0, r1, r2, r3, r4); if (++vb > y1) break;
+        BS_STEP(r1, r2, r3, r4, r0); if (++vb > y1) break;
+        BS_STEP(r2, r3, r4, r0, r1); if (++vb > y1) break;
+        BS_STEP(r3, r4, r0, r1, r2); if (++vb > y1) break;
+        BS_STEP(r4, r0, r1, r2, r3); if (++vb > y1) break;
+    }
+#undef BS_STEP
+#undef BS_PERM
+#undef BS_RND
+#undef BS_COL
+#undef BS_LOAD
+#undef BS_ROWSUM
 }
 
 __constant__ int c_lbd_comb[64] = {0, 1, 0, 2, 0, 3, 0, 4, 0, 5, 0, 6, 1, 2, 1, 3, 1, 4, 1, 5, 1, 6, 2, 3, 2, 4, 2, 5, 2, 6, 2, 7,

@@ -5,7 +5,8 @@
 
 struct LsdRect { double x1, y1, x2, y2, width, x, y, theta, dx, dy, prec, p; };
 
-struct LsdTaps { double k[7]; };  // cv::getGaussianKernel(7, 0.75, CV_64F)
+struct LsdTaps { double k[7]; int symmetric; };  // cv::getGaussianKernel(7, 0.75, CV_64F); symmetric: k[q] and k[6 - q] are the same bits (checked on the host), so that
+                                                  // k_lsd_pre's row pass may compute a product k[q] * d once for both taps
 
 struct LbdCoefs { float gL[21]; float gG[63]; };  // (float) of the double LBD band / global Gaussian weights
 
@@ -30,11 +31,18 @@ struct LbdCoefs { float gL[21]; float gG[63]; };  // (float) of the double LBD b
 #define PRE_NT 512   // 8 waves share the tile's LDS (4 tiles per CU = 8 waves per SIMD); 256 / 384 / 448 / 512 / 1024 threads: 16.3 / 14.7 / 15.1 / 13.5 / 18.9 ms per 4096 frames (round 2)
 #endif
 
-// k_blur5_sobel3: 256 threads produce a BS_TW x BS_TH tile of (dx, dy)
-#define BS_TW 64
-#ifndef BS_TH
-#define BS_TH 32
-#endif
+// k_blur5_sobel3: a wave walks down a band of rows, 4 columns per lane; lanes 0 and 63 only feed their neighbours, so it writes BS_GV groups of 4 columns.
+// A block is 4 waves = 4 bands of the same columns.  Rows per band: the image height in equal parts of at most BS_RB rows (the 6 halo rows of a band are
+// computed twice: 10 % at 60 rows) -- for large batches.  A few frames in flight do not fill the chip with such bands (a VGA frame is 24 waves of 66 dependent
+// row steps), so they get shorter ones: the halo rows cost nothing there and the kernel's latency is in front of the region chain of the call.
+#define BS_GV 62
+#define BS_RB 64
+static inline int plf_bs_rows(int h, int frames)
+{
+    const int cap = frames <= 4 ? 8 : frames <= 16 ? 16 : frames <= 64 ? 32 : BS_RB, nb = (h + cap - 1) / cap;
+    return (h + nb - 1) / nb;
+}
+static inline int plf_bs_bands(int h, int rows) { return (h + rows - 1) / rows; }
 
 struct LsdGeom {
     int w, h;             // input image
@@ -179,6 +187,6 @@ __global__ void k_nfa_fused(const float *ang_all, const double *lgam, const doub
 __global__ void k_lsd_finalize(const float4 *seg_all, const uint8_t *keep_all, const int *nrect, float4 *segs_out, int *nseg_out, plf_keyline *kl_tmp_all, plf_keyline *lines, double *lineeq,
                                int *n_out, int capacity, int *status, unsigned long long *sort_scratch, LsdGeom g);
 __global__ void k_sobel3(const uint8_t *in, ptrdiff_t pitch, ptrdiff_t fstride, short2 *grad, LsdGeom g);
-__global__ void k_blur5_sobel3(const uint8_t *in, ptrdiff_t pitch, ptrdiff_t fstride, short2 *grad, LsdGeom g, int4 k5 /* k[0], k[1], k[2] */);
+__global__ void k_blur5_sobel3(const uint8_t *in, ptrdiff_t pitch, ptrdiff_t fstride, short2 *grad, LsdGeom g, int4 k5 /* k[0], k[1], k[2] */, int rows_per_band);
 __global__ void k_lbd(const short2 *grad_all, const plf_keyline *lines, const int *n_out, uint8_t *desc, int capacity, LsdGeom g, const LbdCoefs *cf);
 #endif

@@ -73,58 +73,107 @@ __global__ void __launch_bounds__(PRE_NT) k_lsd_pre(const uint8_t *__restrict__ 
     const int r_lo = min(max(yofs[dy0], 0), g.h - 1), r_hi = min(max(yofs[dy1] + 1, 0), g.h - 1);
     const int nc = c_hi - c_lo + 1, nr = r_hi - r_lo + 1;
     const uint8_t *img = in + (size_t)f * fstride;
-    // row pass, one item = 4 consecutive columns of one row: their 10 source bytes are converted once (7 conversions per output before: the pass
-    // was a third of the kernel's instructions); per output the same products and the same order of additions as cv::RowFilter
-    for (int i = tid; i < (nr + 6) * (PRE_SC / 4); i += PRE_NT) {
-        const int r = i / (PRE_SC / 4), c = 4 * (i - r * (PRE_SC / 4));
-        if (c >= nc) continue;
-        const uint8_t *row = img + (size_t)plf_reflect101(r_lo - 3 + r, g.h) * pitch;
-        const int x = c_lo + c;
-        double o[4];
-        if (x >= 3 && x + 8 < g.w) {   // interior: bytes x-3 .. x+6 from one unaligned 8-byte and one 4-byte load
-            const unsigned long long lo8 = *(const plf_u64u *)(row + x - 3);
-            const uint32_t hi4 = *(const plf_u32u_pre *)(row + x + 5);
-            double d[10];
+    // row pass: per output the same products and the same order of additions as cv::RowFilter, k[0] d[j] + k[1] d[j+1] + ... + k[6] d[j+6].
+    // One item = 8 consecutive outputs of one row = one thread ((PRE_SR + 6) rows x 11 groups <= PRE_NT: one round, one index division, one row address): their 14
+    // source bytes are converted once, and since k[q] and k[6 - q] are the same bits (LsdTaps::symmetric) k[q] * d and k[6 - q] * d are the same IEEE product of
+    // the same operands -- written with the four distinct taps the compiler computes each once: 44 products per item instead of 56, none of them different.
+    // (Items of 4 outputs in two rounds, a product per tap and plf_reflect101's loop on every item's row: 2 x 120 instructions for these 8 outputs, now ~150.)
+    if (t.symmetric) {
+        static_assert((PRE_SR + 6) * (PRE_SC / 8) <= PRE_NT && PRE_SC % 8 == 0, "one row-pass item per thread");
+        const int r = tid / (PRE_SC / 8), c = 8 * (tid - r * (PRE_SC / 8));
+        if (r < nr + 6 && c < nc) {
+            const uint8_t *row = img + (size_t)plf_reflect101_near(r_lo - 3 + r, g.h) * pitch;
+            const int x = c_lo + c;
+            double *dst = s_tmp + r * PRE_SC + c;
+            const double k0 = t.k[0], k1 = t.k[1], k2 = t.k[2], k3 = t.k[3];
+            if (g.w >= 16) {
+                unsigned long long w0, w1;   // the 14 source bytes x - 3 .. x + 10: byte q is byte sel(q) of (w0, w1)
+                double d[14];
+                if (x >= 3 && x + 10 < g.w) {   // interior: two unaligned 8-byte loads, x - 3 .. x + 4 and x + 3 .. x + 10
+                    w0 = *(const plf_u64u *)(row + x - 3); w1 = *(const plf_u64u *)(row + x + 3);
 #pragma unroll
-            for (int q = 0; q < 8; q++) d[q] = (double)(int)((lo8 >> (8 * q)) & 0xFF);
-            d[8] = (double)(int)(hi4 & 0xFF); d[9] = (double)(int)((hi4 >> 8) & 0xFF);
+                    for (int q = 0; q < 14; q++) d[q] = (double)(int)(((q < 8 ? w0 : w1) >> (8 * (q < 8 ? q : q - 6))) & 0xFF);
+                } else {
+                    // image border (the first / last groups of a row): the reflected source bytes are picked out of one 16-byte window that lies inside the
+                    // row.  (A per-tap reflected byte load here ran on every wave of the tiles at the left / right image edge, because each of their waves
+                    // holds a border group: a third of the kernel's time, 13.5 -> 9.1 ms per 4096 frames.)
+                    const int base = min(max(x - 3, 0), g.w - 16);
+                    w0 = *(const plf_u64u *)(row + base); w1 = *(const plf_u64u *)(row + base + 8);
 #pragma unroll
-            for (int j = 0; j < 4; j++) {
-                double s_ = t.k[0] * d[j];
+                    for (int q = 0; q < 14; q++) {
+                        const int pq = min(max(plf_reflect101_near(x - 3 + q, g.w) - base, 0), 15);   // (clamped: only for outputs beyond the tile's last column)
+                        d[q] = (double)(int)((((pq & 8) ? w1 : w0) >> (8 * (pq & 7))) & 0xFF);
+                    }
+                }
 #pragma unroll
-                for (int q = 1; q < 7; q++) s_ += t.k[q] * d[j + q];
-                o[j] = s_;
-            }
-        } else if (g.w >= 16) {
-            // image border (the first / last groups of a row): the 10 reflected source bytes are picked out of one 16-byte window that lies inside the
-            // row.  (A per-tap reflected byte load here -- 28 loads, ~450 instructions -- ran on every wave of the tiles at the left / right image edge,
-            // because each of their waves holds a border group: a third of the kernel's time, 13.5 -> 9.1 ms per 4096 frames.)
-            const int base = min(max(x - 3, 0), g.w - 16);
-            const unsigned long long w0 = *(const plf_u64u *)(row + base), w1 = *(const plf_u64u *)(row + base + 8);
-            double d[10];
-#pragma unroll
-            for (int q = 0; q < 10; q++) {
-                const int pq = plf_reflect101(x - 3 + q, g.w) - base;
-                d[q] = (double)(int)((((pq & 8) ? w1 : w0) >> (8 * (pq & 7))) & 0xFF);
-            }
-#pragma unroll
-            for (int j = 0; j < 4; j++) {
-                double s_ = t.k[0] * d[j];
-#pragma unroll
-                for (int q = 1; q < 7; q++) s_ += t.k[q] * d[j + q];
-                o[j] = s_;
-            }
-        } else {   // images narrower than 16 pixels
+                for (int j = 0; j < 8; j++) {
+                    double s_ = k0 * d[j];
+                    s_ += k1 * d[j + 1]; s_ += k2 * d[j + 2]; s_ += k3 * d[j + 3]; s_ += k2 * d[j + 4]; s_ += k1 * d[j + 5]; s_ += k0 * d[j + 6];
+                    dst[j] = s_;
+                }
+            } else {   // images narrower than 16 pixels
 #pragma unroll 1
-            for (int j = 0; j < 4; j++) {
-                double s_ = t.k[0] * (double)row[plf_reflect101(x + j - 3, g.w)];
+                for (int j = 0; j < 8; j++) {
+                    double s_ = t.k[0] * (double)row[plf_reflect101(x + j - 3, g.w)];
 #pragma unroll 1
-                for (int q = 1; q < 7; q++) s_ += t.k[q] * (double)row[plf_reflect101(x + j - 3 + q, g.w)];
-                o[j] = s_;
+                    for (int q = 1; q < 7; q++) s_ += t.k[q] * (double)row[plf_reflect101(x + j - 3 + q, g.w)];
+                    dst[j] = s_;
+                }
             }
         }
-#pragma unroll
-        for (int j = 0; j < 4; j++) s_tmp[r * PRE_SC + c + j] = o[j];
+    } else {
+        // taps that are not pairwise the same bits: one item = 4 consecutive columns of one row (10 source bytes converted once), a product per tap
+        for (int i = tid; i < (nr + 6) * (PRE_SC / 4); i += PRE_NT) {
+            const int r = i / (PRE_SC / 4), c = 4 * (i - r * (PRE_SC / 4));
+            if (c >= nc) continue;
+            const uint8_t *row = img + (size_t)plf_reflect101(r_lo - 3 + r, g.h) * pitch;
+            const int x = c_lo + c;
+            double o[4];
+            if (x >= 3 && x + 8 < g.w) {   // interior: bytes x-3 .. x+6 from one unaligned 8-byte and one 4-byte load
+                const unsigned long long lo8 = *(const plf_u64u *)(row + x - 3);
+                const uint32_t hi4 = *(const plf_u32u_pre *)(row + x + 5);
+                double d[10];
+    #pragma unroll
+                for (int q = 0; q < 8; q++) d[q] = (double)(int)((lo8 >> (8 * q)) & 0xFF);
+                d[8] = (double)(int)(hi4 & 0xFF); d[9] = (double)(int)((hi4 >> 8) & 0xFF);
+    #pragma unroll
+                for (int j = 0; j < 4; j++) {
+                    double s_ = t.k[0] * d[j];
+    #pragma unroll
+                    for (int q = 1; q < 7; q++) s_ += t.k[q] * d[j + q];
+                    o[j] = s_;
+                }
+            } else if (g.w >= 16) {
+                // image border (the first / last groups of a row): the 10 reflected source bytes are picked out of one 16-byte window that lies inside the
+                // row.  (A per-tap reflected byte load here -- 28 loads, ~450 instructions -- ran on every wave of the tiles at the left / right image edge,
+                // because each of their waves holds a border group: a third of the kernel's time, 13.5 -> 9.1 ms per 4096 frames.)
+                const int base = min(max(x - 3, 0), g.w - 16);
+                const unsigned long long w0 = *(const plf_u64u *)(row + base), w1 = *(const plf_u64u *)(row + base + 8);
+                double d[10];
+    #pragma unroll
+                for (int q = 0; q < 10; q++) {
+                    const int pq = plf_reflect101(x - 3 + q, g.w) - base;
+                    d[q] = (double)(int)((((pq & 8) ? w1 : w0) >> (8 * (pq & 7))) & 0xFF);
+                }
+    #pragma unroll
+                for (int j = 0; j < 4; j++) {
+                    double s_ = t.k[0] * d[j];
+    #pragma unroll
+                    for (int q = 1; q < 7; q++) s_ += t.k[q] * d[j + q];
+                    o[j] = s_;
+                }
+            } else {   // images narrower than 16 pixels
+    #pragma unroll 1
+                for (int j = 0; j < 4; j++) {
+                    double s_ = t.k[0] * (double)row[plf_reflect101(x + j - 3, g.w)];
+    #pragma unroll 1
+                    for (int q = 1; q < 7; q++) s_ += t.k[q] * (double)row[plf_reflect101(x + j - 3 + q, g.w)];
+                    o[j] = s_;
+                }
+            }
+    #pragma unroll
+            for (int j = 0; j < 4; j++) s_tmp[r * PRE_SC + c + j] = o[j];
+        }
     }
     __syncthreads();
     {

@@ -21,16 +21,6 @@
 
 typedef uint32_t __attribute__((aligned(1))) plf_u32u;
 
-// plf_reflect101 for indices at most one image size outside [0, n): two selects instead of the general loop (which the compiler keeps as a data-dependent loop
-// in every place it is inlined: the tile phases carried five of them); anything further out -- halo wider than a tiny level -- still takes the loop
-__device__ __forceinline__ int of_reflect101(int p, int n)
-{
-    int q = p < 0 ? -p : p;
-    q = q >= n ? 2 * (n - 1) - q : q;
-    if (__builtin_expect((unsigned)q >= (unsigned)n, 0)) return plf_reflect101(p, n);
-    return q;
-}
-
 // cornerScore<16> of cv::FAST (largest threshold for which the pixel is still a corner) minus 1, clamped at 0; d[k] = I_p - I_ring[k]
 // (scalar form: the definition; the kernel runs the packed form orb_fast_score_pk below)
 __device__ __forceinline__ int orb_fast_score(const int d[16], int t)
@@ -185,7 +175,7 @@ __global__ void OF_OCC __launch_bounds__(OF_NT) k_orb_level(const uint8_t *__res
                 int mx[4] = {x, x + 1, x + 2, x + 3};
                 if (!whole) {
 #pragma unroll
-                    for (int j = 0; j < 4; j++) mx[j] = of_reflect101(x + j, W);
+                    for (int j = 0; j < 4; j++) mx[j] = plf_reflect101_near(x + j, W);
                 }
                 const int in0 = max(0, -ey0), in1 = min(EH, H - ey0);   // tile rows [in0, in1) lie inside the image
                 int ey = slot;
@@ -203,7 +193,7 @@ __global__ void OF_OCC __launch_bounds__(OF_NT) k_orb_level(const uint8_t *__res
                 if (in0 > 0 || in1 < EH) {
                     for (int e2 = slot; e2 < EH; e2 += nslots) {
                         if (e2 >= in0 && e2 < in1) continue;
-                        const uint8_t *r2 = img + (size_t)of_reflect101(ey0 + e2, H) * in_pitch;
+                        const uint8_t *r2 = img + (size_t)plf_reflect101_near(ey0 + e2, H) * in_pitch;
                         *reinterpret_cast<uint32_t *>(P + e2 * PW + c4) = (uint32_t)r2[mx[0]] | ((uint32_t)r2[mx[1]] << 8) | ((uint32_t)r2[mx[2]] << 16) | ((uint32_t)r2[mx[3]] << 24);
                     }
                 }
@@ -225,7 +215,7 @@ __global__ void OF_OCC __launch_bounds__(OF_NT) k_orb_level(const uint8_t *__res
                 uint32_t cf[4];
 #pragma unroll
                 for (int j = 0; j < 4; j++) {
-                    const int X = of_reflect101(ex0 + 4 * i + j, W);
+                    const int X = plf_reflect101_near(ex0 + 4 * i + j, W);
                     const int sx = xofs[L.tabx_off + X];
                     const short2 a = xa[L.tabx_off + X];
                     off[j] = sx - sx_lo; nxt[j] = min(sx + 1, SL.w - 1) - sx_lo;
@@ -242,7 +232,7 @@ __global__ void OF_OCC __launch_bounds__(OF_NT) k_orb_level(const uint8_t *__res
                     XT[4 * i + j] = t;
                 }
             } else {
-                const int Y = of_reflect101(ey0 + (i - ngrp), H);
+                const int Y = plf_reflect101_near(ey0 + (i - ngrp), H);
                 const int sy = yofs[L.taby_off + Y];
                 const short2 b = yb[L.taby_off + Y];
                 OrbRowTab t;
@@ -369,7 +359,7 @@ __global__ void OF_OCC __launch_bounds__(OF_NT) k_orb_level(const uint8_t *__res
 #pragma unroll
                 for (int j = 0; j < 4; j++) {
                     ok[j] = x4 + j + PLF_EDGE >= pxs && x4 + j + PLF_EDGE < pxe;
-                    sc[j] = of_reflect101(x4 + j, W) - ex0;
+                    sc[j] = plf_reflect101_near(x4 + j, W) - ex0;
                 }
             }
             uint8_t *dcol = plane + PLF_EDGE + x4;
@@ -398,7 +388,7 @@ __global__ void OF_OCC __launch_bounds__(OF_NT) k_orb_level(const uint8_t *__res
                 for (int py = pys + pslot; py < pye; py += NRp) {
                     if (py >= pin0 && py < pin1) continue;
                     const int ly = py - PLF_EDGE;
-                    const uint8_t *prow = P + (of_reflect101(ly, H) - ey0) * PW;
+                    const uint8_t *prow = P + (plf_reflect101_near(ly, H) - ey0) * PW;
                     uint8_t *d = dcol + (size_t)py * ppitch;
                     if (full) *(plf_u32u *)d = *reinterpret_cast<const uint32_t *>(prow + (x4 - ex0));
                     else {

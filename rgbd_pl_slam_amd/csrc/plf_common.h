@@ -69,6 +69,17 @@ __device__ __forceinline__ int plf_reflect101(int p, int n)
     return p;
 }
 
+// plf_reflect101 for indices at most one image size outside [0, n): two selects instead of the general loop (which the compiler keeps as a data-dependent loop
+// in every place it is inlined: the tile phases of k_orb_level carried five of them, the row pass of k_lsd_pre one per item); anything further out -- a halo
+// wider than a tiny image -- still takes the loop
+__device__ __forceinline__ int plf_reflect101_near(int p, int n)
+{
+    int q = p < 0 ? -p : p;
+    q = q >= n ? 2 * (n - 1) - q : q;
+    if (__builtin_expect((unsigned)q >= (unsigned)n, 0)) return plf_reflect101(p, n);
+    return q;
+}
+
 // Block-wide exclusive scan of a[0..n) (ints, LDS or global), in place; returns the total.
 // `tmp` must hold blockDim.x + 1 ints of LDS.  All threads of the block must call it.
 __device__ inline int plf_block_excl_scan(int *a, int n, int *tmp)

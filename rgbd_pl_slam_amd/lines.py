@@ -135,6 +135,14 @@ class LineSegment:
         L.check(L.lib().plf_line_debug_nfa_counters(self._h, L.vp(out)), "plf_line_debug_nfa_counters")
         return out
 
+    def gradient(self, frame, w, h):
+        """test hook: (dx, dy) int16 [h, w] planes the LBD descriptor of the last batch read for `frame` (plf_line_debug_gradient); w, h = that batch's image size"""
+        dx = np.zeros((h, w), np.int16); dy = np.zeros((h, w), np.int16)
+        f = L.lib().plf_line_debug_gradient
+        f.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]
+        L.check(f(self._h, frame, L.vp(dx), L.vp(dy)), "plf_line_debug_gradient")
+        return dx, dy
+
     def segments(self, frame=0):
         """test hook: all LSD segments of the last call in detection order"""
         n = C.c_int32()
