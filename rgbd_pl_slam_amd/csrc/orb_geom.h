@@ -31,6 +31,7 @@ struct OrbLevel {
     // k_orb_level: the effective cell grid (cells skipped by the reference's loop are at the row / column ends), tiles of 2 x 2 cells, and the
     // end of the last cell's computed region (cell sub-image minus its 3-pixel frame; the regions of neighbouring cells abut)
     int ncx, ncy, tcx, tcy, rex, rey;
+    int tile_base;       // k_orb_level covers all levels in one launch: first workgroup of this level (OrbGeom::tiles_total in all)
 };
 
 struct OrbGeom {
@@ -43,32 +44,34 @@ struct OrbGeom {
     uint32_t blur_stride;  // bytes per frame
     uint32_t pool_stride;  // entries per frame
     uint32_t sel_stride;   // entries per frame
-    // LDS layout of k_orb_level (bytes; maxima over the levels): pixel tile pitch, source tile pitch, score tile pitch, byte offsets
-    int lds_pw, lds_spw, lds_sp, lds_eh, lds_off_a, lds_off_s, lds_off_list, lds_off_tab, lds_total;
+    int tiles_total;       // workgroups of k_orb_level (tiles of all levels of one frame)
+    // LDS layout of k_orb_level (bytes; maxima over the levels): pixel tile pitch, score tile pitch, byte offsets of the survivor list, the score tile and the
+    // per-wave corner queues of the non-maximum suppression
+    int lds_pw, lds_sp, lds_off_list, lds_off_s, lds_off_q, lds_total;
     int lds_list_cap;    // entries of the FAST survivor list: half the pixels of the largest computed region of a tile (k_orb_level redoes denser passes in two row halves)
-    int lds_parts;       // the source rows of a tile are staged in this many passes (rows of the tile split evenly): bounds the staging buffer
     OrbLevel lv[PLF_MAX_LEVELS];
 };
 
-// Source rows (of level l - 1) behind part `pi` of `parts` of a tile's rows [ey0, ey0 + EH) of level l: rows of the tile are split evenly, rows outside
-// the level are REFLECT_101 mirrors (they fall inside the part's clamped range: a tile keeps >= 4 rows inside).  yofs: the level's row table.
-// Used by the host (LDS sizing) and by k_orb_level (staging) -- the same arithmetic on both sides.
+// Row-walking kernels of the ORB front (k_orb_pyramid, k_orb_blur): a wave owns PLF_ORB_SPAN columns (4 per lane) and a band of rows.  The band height follows the
+// frames in flight: a few frames need many short waves to fill the chip, a large batch long ones that amortise a band's lead-in.
+#define PLF_ORB_SPAN 256
 #ifdef __HIPCC__
 __host__ __device__
 #endif
-static inline void orb_part_rows(int ey0, int EH, int parts, int pi, int H, int srcH, const int *yofs, int *s_lo, int *s_hi)
-{
-    const int e0 = pi * EH / parts, e1 = (pi + 1) * EH / parts;
-    const int a = ey0 + e0, b = ey0 + e1 - 1;
-    const int ra = a < 0 ? -a : (a >= H ? 2 * (H - 1) - a : a), rb = b < 0 ? -b : (b >= H ? 2 * (H - 1) - b : b);
-    int lo = ra < rb ? ra : rb, hi = ra < rb ? rb : ra;
-    if (a < 0 && b >= 0) lo = 0;
-    if (a <= H - 1 && b > H - 1) hi = H - 1;
-    int sl = yofs[lo], sh = yofs[hi] + 1;
-    sl = sl < 0 ? 0 : (sl > srcH - 1 ? srcH - 1 : sl);
-    sh = sh < 0 ? 0 : (sh > srcH - 1 ? srcH - 1 : sh);
-    *s_lo = sl; *s_hi = sh;
-}
+static inline int orb_band_shift(int frames) { return frames <= 4 ? 3 : frames <= 16 ? 4 : 5; }   // bands of 8 / 16 / 32 rows
+// workgroups (one wave each) of a level: k_orb_pyramid covers the padded plane's columns and the level's rows, k_orb_blur the level's columns and rows
+#ifdef __HIPCC__
+__host__ __device__
+#endif
+static inline int orb_pyr_spans(const OrbLevel &L) { return (L.ppitch + PLF_ORB_SPAN - 1) / PLF_ORB_SPAN; }
+#ifdef __HIPCC__
+__host__ __device__
+#endif
+static inline int orb_blur_spans(const OrbLevel &L) { return (L.w + PLF_ORB_SPAN - 1) / PLF_ORB_SPAN; }
+#ifdef __HIPCC__
+__host__ __device__
+#endif
+static inline int orb_bands(const OrbLevel &L, int band_shift) { return (L.h + (1 << band_shift) - 1) >> band_shift; }
 
 #ifdef __HIPCC__
 #include "plf_common.h"
@@ -77,9 +80,25 @@ void plf_orb_upload_constants(const int *umax16);
 // batch driver (batch_host.hip): the status word of the batch just enqueued on `s`, copied to pinned host memory in stream order (orb_host.hip)
 int plf_orb_status_async(plf_orb *h, int32_t *host_dst, hipStream_t s);
 
-// ---- kernels launched by orb_host.hip (orb_front.hip, orb_octree.hip, orb_kernels.hip)
-__global__ void k_orb_level(const uint8_t *in, ptrdiff_t in_pitch, ptrdiff_t in_fstride, uint8_t *pyr, uint8_t *blur, int l, const int *xofs, const short2 *xa, const int *yofs, const short2 *yb,
-                            const int4 *cells, int2 *cellinfo, uint2 *pool, int *poolcnt, int *status, OrbGeom g, int4 taps);
+// Register budget of the ORB front kernels: 8 waves per SIMD = at most 64 VGPRs.  Not for their own occupancy but for co-residency: four region-growing waves
+// hold 416 of a SIMD's 512 VGPRs for 80 ms, and in the 96 that are left a 56-register ORB wave fits TOGETHER with a matcher wave (40-48), an 80-register one
+// alone: +2.5 % for the pipeline.
+#ifndef PLF_ORB_LEVEL_WPE
+#define PLF_ORB_LEVEL_WPE 8
+#endif
+#define OF_OCC __attribute__((amdgpu_waves_per_eu(PLF_ORB_LEVEL_WPE, PLF_ORB_LEVEL_WPE)))
+// issue priority above the other throughput kernels (matchers, k_lsd_pre, NFA stages: 0), below the region chain (3)
+#ifndef PLF_ORB_PRIO
+#define PLF_ORB_PRIO 2
+#endif
+typedef uint32_t __attribute__((aligned(1))) plf_u32u;
+typedef short plf_s2v __attribute__((ext_vector_type(2)));
+
+// ---- kernels launched by orb_host.hip (orb_pyramid.hip, orb_front.hip, orb_octree.hip, orb_kernels.hip)
+__global__ void k_orb_pyramid(const uint8_t *in, ptrdiff_t in_pitch, ptrdiff_t in_fstride, uint8_t *pyr, int l, int band_shift, const int *xofs, const short2 *xa, const int *yofs, const short2 *yb,
+                              OrbGeom g);
+__global__ void k_orb_blur(const uint8_t *pyr, uint8_t *blur, int band_shift, OrbGeom g, int4 taps);
+__global__ void k_orb_level(const uint8_t *pyr, const int4 *cells, int2 *cellinfo, uint2 *pool, int *poolcnt, int *status, OrbGeom g);
 __global__ void k_octree(const int2 *cellinfo, const uint2 *pool, int *celloff, uint2 *keys_all, int *nodeof_all, uint8_t *quad_all, uint2 *sel, int *selcnt, int *ncand_dbg, int *status, OrbGeom g,
                          int cap_nodes, int cap_sort);
 __global__ void k_orient_brief(const uint8_t *pyr, const uint8_t *blur, const uint2 *sel, const int *selcnt, plf_keypoint *kps, uint8_t *desc, int *n_out, int capacity, int *status, OrbGeom g,

@@ -96,7 +96,7 @@ static int orb_geometry(plf_orb *h, int w, int h_, OrbGeom *g, std::vector<int4>
     g->in_w = w; g->in_h = h_;
     size_t pyr = 0, blur = 0;
     uint32_t pool = 0, sel = 0, tabx = 0, taby = 0;
-    int cellbase = 0, maxsel = 0;
+    int cellbase = 0, maxsel = 0, tilebase = 0;
     for (int l = 0; l < g->nlevels; l++) {
         OrbLevel &L = g->lv[l];
         L.w = cv_round_f((float)w * h->inv[l]);  // so@0x7051e: float multiply, cvtss2si
@@ -152,6 +152,8 @@ static int orb_geometry(plf_orb *h, int w, int h_, OrbGeom *g, std::vector<int4>
             L.rex = (int)mx - 3; L.rey = (int)my - 3;
         }
         L.tcx = (L.ncx + 1) / 2; L.tcy = (L.ncy + 1) / 2;
+        L.tile_base = tilebase;
+        tilebase += L.tcx * L.tcy;
         if (2 * L.wCell > 250 || 2 * L.hCell > 250) return PLF_E_BADARG;   // tile-relative coordinates are packed in 8 bits
         L.quota = h->per_level[l];
         L.scale = h->scale[l];
@@ -164,7 +166,7 @@ static int orb_geometry(plf_orb *h, int w, int h_, OrbGeom *g, std::vector<int4>
         L.tabx_off = tabx; L.taby_off = taby;
         tabx += (uint32_t)L.w; taby += (uint32_t)L.h;
     }
-    g->cells_total = cellbase; g->maxsel = maxsel;
+    g->cells_total = cellbase; g->maxsel = maxsel; g->tiles_total = tilebase;
     g->pyr_stride = (uint32_t)pyr; g->blur_stride = (uint32_t)blur; g->pool_stride = pool; g->sel_stride = sel;
     return PLF_OK;
 }
@@ -232,12 +234,11 @@ static int orb_configure(plf_orb *h, int w, int hh)
     PLF_HIP_TRY(hipMemcpy(h->d_yofs, yofs.data(), sizeof(int) * ty, hipMemcpyHostToDevice));
     PLF_HIP_TRY(hipMemcpy(h->d_yb, yb.data(), sizeof(short2) * ty, hipMemcpyHostToDevice));
     PLF_HIP_TRY(hipMemcpy(h->d_cells, cells.data(), sizeof(int4) * cells.size(), hipMemcpyHostToDevice));
-    // LDS layout of k_orb_level: maxima over all tiles of all levels.  The kernel is latency-bound per tile, so its run time is inversely
-    // proportional to the tiles a CU holds (measured: 52 / 37 / 30 ms per 4096 frames for 2 / 3 / 4 resident tiles): the source rows of a tile are
-    // staged in `parts` passes and the score tile only spans the cells' computed columns, so that 5 tiles fit (38.5 -> 30.8 KB at VGA).
+    // LDS layout of k_orb_level: maxima over all tiles of all levels.  The kernel is latency-bound per tile, so its run time follows the tiles a CU holds;
+    // with the pyramid and the blur in kernels of their own (orb_pyramid.hip) a tile keeps the pixels of its computed regions + the FAST
+    // radius, the survivor list, the score tile (only the cells' computed columns) and the suppression queues.
     {
-        int maxEW = 0, maxEH = 0, maxSW = 0, maxRW = 0, maxRH = 0, maxOW = 0;
-        int maxSHp[5] = {0, 0, 0, 0, 0};   // [parts]: tallest staged source block when the tile rows are split into 1..4 parts
+        int maxEW = 0, maxEH = 0, maxRW = 0, maxRH = 0;
         for (int l = 0; l < g.nlevels; l++) {
             const OrbLevel &L = g.lv[l];
             for (int ty = 0; ty < L.tcy; ty++)
@@ -245,57 +246,35 @@ static int orb_configure(plf_orb *h, int w, int hh)
                     const int cx0 = 2 * txi, cx1 = std::min(cx0 + 2, L.ncx), cy0 = 2 * ty, cy1 = std::min(cy0 + 2, L.ncy);
                     const int rx0 = PLF_EDGE + cx0 * L.wCell, rx1 = cx1 == L.ncx ? L.rex : PLF_EDGE + cx1 * L.wCell;
                     const int ry0 = PLF_EDGE + cy0 * L.hCell, ry1 = cy1 == L.ncy ? L.rey : PLF_EDGE + cy1 * L.hCell;
-                    const int xs = txi == 0 ? 0 : rx0, xe = txi == L.tcx - 1 ? L.w : rx1, ys = ty == 0 ? 0 : ry0, ye = ty == L.tcy - 1 ? L.h : ry1;
-                    const int ex0 = (xs & ~3) - 4, EW = ((xe - 1) & ~3) + 8 - ex0, EH = ye - ys + 6, ey0 = ys - 3;
-                    if (rx1 <= rx0 || ry1 <= ry0 || xe - xs < 4 || ye - ys < 4) return PLF_E_BADARG;
-                    maxEW = std::max(maxEW, EW); maxEH = std::max(maxEH, EH); maxOW = std::max(maxOW, xe - xs);
+                    const int ex0 = (rx0 & ~3) - 4, EW = ((rx1 - 1) & ~3) + 8 - ex0, EH = ry1 - ry0 + 6, ey0 = ry0 - 3;
+                    if (rx1 <= rx0 || ry1 <= ry0) return PLF_E_BADARG;
+                    // the tile (computed regions + halo) is loaded from the padded plane as whole dwords: all of it must lie inside the plane
+                    if (ex0 < -PLF_EDGE || ex0 + EW > L.w + PLF_EDGE || ey0 < -PLF_EDGE || ey0 + EH > L.h + PLF_EDGE) return PLF_E_BADARG;
+                    maxEW = std::max(maxEW, EW); maxEH = std::max(maxEH, EH);
                     maxRW = std::max(maxRW, rx1 - rx0); maxRH = std::max(maxRH, ry1 - ry0);
-                    if (l > 0) {
-                        const OrbLevel &S = g.lv[l - 1];
-                        const int lx_lo = std::max(ex0, 0), lx_hi = std::min(ex0 + EW - 1, L.w - 1);
-                        const int sx_lo = xofs[L.tabx_off + lx_lo] & ~3, sx_hi = std::min(xofs[L.tabx_off + lx_hi] + 1, S.w - 1);
-                        maxSW = std::max(maxSW, sx_hi - sx_lo + 1);
-                        for (int parts = 1; parts <= 4; parts++)
-                            for (int pi = 0; pi < parts; pi++) {
-                                int s_lo, s_hi;
-                                orb_part_rows(ey0, EH, parts, pi, L.h, S.h, &yofs[L.taby_off], &s_lo, &s_hi);
-                                maxSHp[parts] = std::max(maxSHp[parts], s_hi - s_lo + 1);
-                            }
-                    }
                 }
         }
         if (maxEW > 255 || maxRH > 255) return PLF_E_BADARG;   // survivors are packed as (tile column | row << 8)
         g.lds_pw = (maxEW + 3) & ~3;
-        g.lds_spw = ((maxSW + 8 + 15) & ~15) + 16;   // (rows are filled 16 bytes at a time)
         g.lds_sp = (maxRW + 6 + 3) & ~3;              // score tile: columns (rx0 - ex0) & ~3 .. of the tile, i.e. the computed regions + alignment slack
-        g.lds_eh = maxEH;
         auto up16 = [](size_t v) { return (v + 15) & ~(size_t)15; };
         const size_t sz_p = (size_t)g.lds_pw * (maxEH + 1) + 16;
         const size_t sz_s = (size_t)g.lds_sp * maxRH + 16;
-        // resize tables; the non-maximum suppression re-uses the area for its per-wave corner queues (128 uint16 each: k_orb_level phase 5)
-        const size_t sz_t = std::max((size_t)(g.lds_pw + maxEH) * 8 + (size_t)(g.lds_pw / 4 + 1) * 2 + 16, (size_t)(PLF_ORB_LEVEL_THREADS / 64) * 256 + 16);
-#ifndef PLF_ORB_TILES_TARGET
-#define PLF_ORB_TILES_TARGET 6   // resident tiles per CU the staging passes are chosen for (round 6: 5 -> 6 with the halved survivor list)
-#endif
-        // FAST survivor list (aliases the staged source): half the pixels of the largest computed region, rounded up to whole rows + one group -- any half of a tile's
-        // rows fits; a pass with more survivors is redone in two row halves (k_orb_level: fast_pass)
+        // per-wave corner queues of the non-maximum suppression (128 uint16 each)
+        const size_t sz_q = (size_t)(PLF_ORB_LEVEL_THREADS / 64) * 256 + 16;
+        // FAST survivor list: half the pixels of the largest computed region, rounded up to whole rows + one group -- any half of a tile's rows fits; a pass
+        // with more survivors is redone in two row halves (k_orb_level: fast_pass)
         g.lds_list_cap = maxRW * ((maxRH + 1) / 2) + 4;
         const size_t sz_list = (size_t)g.lds_list_cap * 2 + 16;
-        size_t sz_a = 0;
-        for (g.lds_parts = 1; g.lds_parts <= 4; g.lds_parts++) {
-            sz_a = std::max((size_t)g.lds_spw * (maxSHp[g.lds_parts] + 1) + 16, sz_list);
-            // five tiles per CU: 160 KB / 5 minus the 2064 static bytes (the NMS masks, round 6: one set for both passes); stop splitting when the survivor list is what is left
-            if (up16(sz_p) + up16(sz_a) + up16(sz_s) + up16(sz_t) <= 160 * 1024 / PLF_ORB_TILES_TARGET - 2064 - 64 || sz_a == sz_list || g.lds_parts == 4) break;
-        }
-        g.lds_off_a = (int)up16(sz_p);
-        g.lds_off_s = g.lds_off_a + (int)up16(sz_a);
-        g.lds_off_list = g.lds_off_a;
-        g.lds_off_tab = g.lds_off_s + (int)up16(sz_s);
-        g.lds_total = g.lds_off_tab + (int)up16(sz_t);
+        // (the suppression reads the 8 neighbours of a score unconditionally: the list in front of the score tile and the queues behind it are valid LDS)
+        g.lds_off_list = (int)up16(sz_p);
+        g.lds_off_s = g.lds_off_list + (int)up16(sz_list);
+        g.lds_off_q = g.lds_off_s + (int)up16(sz_s);
+        g.lds_total = g.lds_off_q + (int)up16(sz_q);
         if (g.lds_total > 150 * 1024) return PLF_E_BADARG;
         if (getenv("PLF_ORB_DEBUG_LDS"))
-            fprintf(stderr, "[plf] k_orb_level LDS: P %zu, SRC/LIST %zu (%d parts), S %zu, tables %zu -> %d dynamic + 2064 static (pw %d, spw %d, sp %d, eh %d, maxRW %d, maxRH %d)\n",
-                    sz_p, sz_a, g.lds_parts, sz_s, sz_t, g.lds_total, g.lds_pw, g.lds_spw, g.lds_sp, g.lds_eh, maxRW, maxRH);
+            fprintf(stderr, "[plf] k_orb_level LDS: P %zu, LIST %zu, S %zu, queues %zu -> %d dynamic + 2064 static (pw %d, sp %d, maxEH %d, maxRW %d, maxRH %d)\n",
+                    sz_p, sz_list, sz_s, sz_q, g.lds_total, g.lds_pw, g.lds_sp, maxEH, maxRW, maxRH);
     }
     // keep the per-frame strides of the allocation (max size) so that buffer sizes stay valid
     g.pyr_stride = big.pyr_stride; g.blur_stride = big.blur_stride; g.pool_stride = big.pool_stride; g.sel_stride = big.sel_stride;
@@ -418,13 +397,16 @@ static int orb_enqueue(plf_orb *h, const uint8_t *d_gray, int n_frames, ptrdiff_
     int *poolcnt = h->d_counters, *selcnt = h->d_counters + (size_t)h->prm.max_batch * nl,
         *ncand = h->d_counters + 2 * (size_t)h->prm.max_batch * nl, *status = h->d_counters + 3 * (size_t)h->prm.max_batch * nl;
     PLF_HIP_TRY(hipMemsetAsync(h->d_counters, 0, (3 * (size_t)h->prm.max_batch * nl + 16) * sizeof(int), s));
-    // one fused launch per level (k_orb_level: pyramid plane + blur + FAST score / NMS / cell candidates from one LDS tile); level l is
-    // resized from level l-1, so the launches are stream-ordered
+    // the pyramid, one launch per level (level l is resized from plane l - 1: stream-ordered); then the blur and the FAST tiles of all levels, one launch each
+    const int bs = orb_band_shift(B);
+    int blur_blocks = 0;
     for (int l = 0; l < nl; l++) {
         const OrbLevel &L = g.lv[l];
-        hipLaunchKernelGGL(k_orb_level, dim3(L.tcx * L.tcy, B), dim3(PLF_ORB_LEVEL_THREADS), (size_t)g.lds_total + PLF_ORB_LDS_PAD, s, d_gray, pitch, fstride, h->d_pyr, h->d_blur, l, h->d_xofs, h->d_xa,
-                           h->d_yofs, h->d_yb, h->d_cells, h->d_cellinfo, h->d_pool, poolcnt, status, g, h->taps);
+        hipLaunchKernelGGL(k_orb_pyramid, dim3(orb_pyr_spans(L) * orb_bands(L, bs), B), dim3(64), 0, s, d_gray, pitch, fstride, h->d_pyr, l, bs, h->d_xofs, h->d_xa, h->d_yofs, h->d_yb, g);
+        blur_blocks += orb_blur_spans(L) * orb_bands(L, bs);
     }
+    hipLaunchKernelGGL(k_orb_blur, dim3(blur_blocks, B), dim3(64), 0, s, h->d_pyr, h->d_blur, bs, g, h->taps);
+    hipLaunchKernelGGL(k_orb_level, dim3(g.tiles_total, B), dim3(PLF_ORB_LEVEL_THREADS), (size_t)g.lds_total + PLF_ORB_LDS_PAD, s, h->d_pyr, h->d_cells, h->d_cellinfo, h->d_pool, poolcnt, status, g);
 // k_octree is a chain of LDS sweeps and barriers over <= 250 nodes: latency-bound per workgroup.  128 threads: twice as many independent workgroups per wave slot
     // (4.9 -> 3.0 ms per 4096 frames solo, and two of them fit in the one-wave-per-SIMD room next to the region-growing kernel)
 #ifndef PLF_OCTREE_THREADS

@@ -1,9 +1,10 @@
 // orb_kernels.hip -- HIP kernels of the ORB extractor for gfx950 (MI355X).
 //
 // Pipeline per batch of B frames (every launch covers all frames):
-//   k_orb_level x nlevels         ORBextractor::ComputePyramid (include/ORBextractor.h:89, so@0x70430) + the cv::FAST cell calls of
-//                                 ComputeKeyPointsOctTree (so@0x75fa0: score, threshold / retry, NMS) + GaussianBlur 7x7 (so@0x77487),
-//                                 fused per tile of 2 x 2 cells (orb_front.hip)
+//   k_orb_pyramid x nlevels       ORBextractor::ComputePyramid (include/ORBextractor.h:89, so@0x70430): padded planes, row-walking waves (orb_pyramid.hip)
+//   k_orb_blur                    GaussianBlur 7x7 (so@0x77487) of all levels, row-walking waves (orb_pyramid.hip)
+//   k_orb_level                   the cv::FAST cell calls of ComputeKeyPointsOctTree (so@0x75fa0: score, threshold / retry, NMS) of all levels,
+//                                 per tile of 2 x 2 cells loaded from the padded plane (orb_front.hip)
 //   k_octree                      DistributeOctTree / DivideNode          (orb_octree.hip)
 //   k_orient_brief                IC_Angle + steered BRIEF + final layout (so@0x6fb10, so@0x777b5)
 //
@@ -16,7 +17,7 @@
 #include "orb_geom.h"
 #include "orb_pattern.inc"
 
-typedef uint32_t __attribute__((aligned(1))) plf_u32u;   // dword access at byte alignment (legal on gfx950 global memory)
+// (plf_u32u, orb_geom.h: dword access at byte alignment, legal on gfx950 global memory)
 typedef unsigned long long __attribute__((aligned(1))) plf_u64u;
 struct __attribute__((aligned(4))) plf_int4u { int x, y, z, w; };
 

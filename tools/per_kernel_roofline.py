@@ -22,7 +22,9 @@ for l in range(8):
     sp += lw * lh; plast = lw * lh
 M, C = 5000, 0
 TERMS = {   # kernel -> (SURVEY 8d term, bytes per frame)
-    "k_orb_level": ("(SP - P_last) resize reads + (SP - P_0) level writes + SP FAST read + 2 SP blur, over the 8 launches", (sp - plast) + (sp - P0) + sp + 2 * sp),
+    "k_orb_pyramid": ("(SP - P_last) resize reads + P_0 input read + SP level writes, over the 8 launches", (sp - plast) + P0 + sp),
+    "k_orb_blur": ("2 SP blur", 2 * sp),
+    "k_orb_level": ("SP FAST read", sp),
     "k_orient_brief": ("(749 + 512 + 32 + 28) K", (749 + 512 + 32 + 28) * K),
     "k_lsd_pre": ("(P_0 + P_s) blur / downscale + 9 P_s gradient", (P0 + Ps) + 9 * Ps),
     "k_lsd_regions2": ("6 P_s region growing", 6 * Ps),
@@ -50,7 +52,7 @@ rows = []
 for n, s in sorted(ser.items(), key=lambda kv: -kv[1]["per_step_ms"])[:10]:
     term, bpf = TERMS.get(n, ("not a term of SURVEY 8d", None))
     launches = max(1, round(s["calls_per_step"]))
-    alg = None if bpf is None else int(bpf * B / (8 if n == "k_orb_level" else 1))   # per launch (k_orb_level: the term covers its 8 launches)
+    alg = None if bpf is None else int(bpf * B / (8 if n == "k_orb_pyramid" else 1))   # per launch (k_orb_pyramid: the term covers its 8 launches)
     f = pmc["counters"]["FETCH_SIZE"].get(n, {}).get("per_launch_KB"); w = pmc["counters"]["WRITE_SIZE"].get(n, {}).get("per_launch_KB")
     traffic = None if f is None or w is None else int((f + w) * 1024 * B / pmc["frames_per_launch"])
     row = {"name": n, "launches_per_step": launches, "term": term, "algorithmic_bytes_per_launch": alg, "solo_ms_per_launch": round(s["avg_ms"], 3),
