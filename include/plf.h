@@ -935,7 +935,7 @@ int plf_map_update_normal_depth(const plf_map_geom_view *v, const float *world_p
  * (so@0x4d68a, 0x4d69b); in key order a keyframe that isBad() (kf_bad, so@0x4d8d7) is skipped, the others are conn_* in key order
  * (mvpLocalKeyFrames before its expansion) and the first strict maximum among them is max_kf / max_w (pKFmax, from max = 0).  No threshold,
  * no sort: ord_kf / ord_w are not written and ord_* may be NULL (all three or none; when given, n_ord[r] = 0 is written for every row).  A count that is not empty but holds only bad keyframes has a result: n_conn = 0,
- * max_kf = -1, max_w = 0.  The expansion by neighbours, children and parent is pointer-graph logic and stays with the caller.
+ * max_kf = -1, max_w = 0.  The expansion by neighbours, children and parent is plf_local_keyframes ("Local map" below), which takes conn_kf / n_conn as its seed.
  *
  * GetBestCovisibilityKeyFrames(N) (so@0x9cdb0) is the first min(N, n_ord) entries of a row of ord_kf.  GetCovisiblesByWeight(w) (so@0x9cff0):
  * upper_bound with a > b (so@0x9d088-0x9d0bc) = the prefix before the first weight < w.  DIFFERS FROM UPSTREAM ORB-SLAM2: when no weight is
@@ -1099,6 +1099,130 @@ int plf_keyframe_culling(const plf_cull_view *v, const plf_cull_params *p, const
 int plf_map_point_culling(int32_t n, const int32_t *found, const int32_t *visible, const int64_t *first_kf_id, const int32_t *point_nobs,
                           const int32_t *obs_start, const int32_t *obs_kf, const uint8_t *obs_w, int32_t n_kf, const uint8_t *point_bad,
                           int64_t cur_kf_id, int32_t cn_th_obs, int32_t *decision, int32_t device, void *stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * Local map -- what Tracking::TrackLocalMap runs between the votes of plf_covis_count and the frustum / projection calls: the expansion of
+ * void Tracking::UpdateLocalKeyFrames() (so@0x4d5a0), void Tracking::UpdateLocalPoints() (so@0x49cc0), the head of
+ * void Tracking::SearchLocalPoints() (so@0x49b20), and the gather of the local points' rows of the resident map into the dense arrays that
+ * plf_frustum_points and plf_mappoint_view read.  Integer work (the gather copies bits): every output is exact and two identical calls write
+ * identical bits.  Any number of frames (rows) per call.
+ *
+ * UpdateLocalKeyFrames after the votes, from the binary:
+ *  1. mvpLocalKeyFrames = the voted keyframes that are not bad, in key order, each marked (mnTrackReferenceForFrame, KeyFrame+0x28 =
+ *     mCurrentFrame.mnId, Tracking+0x12338): conn_kf of a PLF_COVIS_VOTES call, here seed_kf.  ALL of them, however many.
+ *  2. begin() and end() are read once before the loop (so@0x4d9b5-0x4d9c4): the loop runs over the seeds only, keyframes pushed during the
+ *     loop are never expanded.
+ *  3. every iteration opens with size-in-bytes > 0x287 (cmp $0x287; ja, so@0x4d9d8 and 0x4db53): size() > 80 ends the loop.  Nothing is
+ *     tested inside an iteration, so the list ends at up to 83 entries (or at the seed count, if that is larger).
+ *  4. per seed: of GetBestCovisibilityKeyFrames(10) (so@0x4da23) the first entry that is not isBad() (so@0x4da4b) and not marked
+ *     (so@0x4da63) is pushed and marked, and the neighbour loop ends (so@0x4db68 -> 0x4da76); likewise the first such child of GetChilds()
+ *     (so@0x4da7e; a std::set<KeyFrame*> copy walked in key order; so@0x4dba7 -> 0x4dac8); GetParent() (so@0x4dacd) that is non-null and not
+ *     marked (no isBad() test, so@0x4dad2-0x4dae7) is pushed and marked, and then THE WHOLE EXPANSION ENDS (jne 0x4d90e -> 0x4d964: upstream's
+ *     `break` sits inside the parent's if).  A null or marked parent ends nothing.
+ *  5. mpReferenceKF = pKFmax: max_kf of the votes call.
+ * Here: covis_kf / n_covis are ord_kf / n_ord of a whole-graph PLF_COVIS_CONNECTIONS call, row s = slot s; min(n_best, n_covis[s],
+ * covis_stride) entries are read.  child_start / child_kf: a CSR by slot whose ranges are in std::set order (ascending key).  A slot outside
+ * [0, n_kf) is skipped wherever it is read (a seed, a neighbour, a child, a parent: -1 = none), so the -1 filler of ord_kf is harmless.
+ * Seeds are taken as given: they are not tested against kf_bad again, and they are expected to be distinct (a slot named twice is pushed twice).
+ * One wave per row; the iterations are serial, inside one the lanes test neighbours and children 64 at a time and a ballot takes the
+ * first hit.  Marks: an LDS bitmap while n_kf <= dense_max_kf (0 = 65536; at most 262144 = 32 KB), an LDS hash set of the row's own marks
+ * beyond (sized for min(seed_stride, n_kf) + 3 * (max_local + 1) marks at half load).  Both give the same bits.
+ * PLF_E_BADARG before any device work: a NULL array (kf_bad may be NULL), negative sizes, strides < 1, n_best < 0, max_local < 0, and, on
+ * the hash path, more than 8192 marks to hold (min(n_kf, min(seed_stride, n_kf) + 3 * (max_local + 1))).
+ *
+ * UpdateLocalPoints, from the binary: over mvpLocalKeyFrames in order, over GetMapPointMatches() in order: a null entry is skipped, a point
+ * whose mnTrackReferenceForFrame (MapPoint+0x38) is the frame's id already (so@0x49d49) is skipped, a point that isBad() (so@0x49d52) is
+ * skipped -- it is NOT marked, which changes nothing: it is bad wherever it appears again --, any other is pushed and marked.  The result is the
+ * non-bad points in order of first occurrence.  Here: the rows of kf_row_start / kf_row_item by slot (the rows plf_covis_count takes, row s =
+ * slot s, -1 = null), concatenated in the order of local_kf; an id outside [0, n_items) is skipped.  A local_kf entry outside [0, n_kf) is
+ * skipped.  `seen` = the point is named by a non-bad entry of the frame's own row (frame_row_*, optional): after the first loop of
+ * SearchLocalPoints its mnLastFrameSeen (MapPoint+0x40) is the frame's id, and the second loop skips it (so@0x49bec).
+ * The pass is exact whatever the scheduling: every position of the concatenation enters (id -> smallest position) into a table with an
+ * integer atomic minimum, a position is kept when the table holds that very position and the point is not bad, and the kept positions are
+ * compacted in order by a workgroup scan, one keyframe row at a time.  The table: an LDS open-addressing table of table_slots entries (0 = 8192
+ * = 64 KB, two workgroups per CU; rounded up to a power of two, at most 16384) for a row whose concatenated length is at most table_slots / 2,
+ * and for longer rows the workgroup's own array of n_items entries in stream-ordered global scratch (at most 1 GB of it, fewer workgroups beyond),
+ * indexed by id.  Both give the same bits.  The call is two launches, one per class, each skipping the other's rows: the long rows run without the
+ * table's LDS, and a workgroup fills its array only when it meets such a row.
+ * A row whose concatenated length reaches 0x3F000000 (1.05e9) is not processed: n_local_item = 0, status bit 8.
+ * MapLines: UpdateLocalLines / SearchLocalLines (include/Tracking.h:159,166) have no body anywhere in the reference; they are taken as the
+ * same rules over the mvpMapLines rows -- PARITY UNPINNED.  The calls do not know which of the two they serve.
+ *
+ * Head of SearchLocalPoints, from the binary: for each entry of the frame's own mvpMapPoints a null is skipped, a bad point is set to null,
+ * any other gets IncreaseVisible(1), mnLastFrameSeen = id, mbTrackInView = false; then every local point whose mnLastFrameSeen is not the id
+ * (so@0x49bec) and that is not bad and isInFrustum(pMP, 0.5) gets IncreaseVisible(1) and nToMatch++.  plf_local_visible is that, after
+ * plf_frustum_*: in_view[i] &= !seen[i], n_to_match = the entries left, and visible[id] += 1 once per non-bad entry of the own row (a point
+ * listed twice there is raised twice, as in the reference) and once per entry left in view.  Null-ing the bad own points is the caller's.
+ *
+ * Layout: row r writes local_kf at r * kf_stride and local_item / seen at r * item_stride.  n_local_kf[r], n_local_item[r] are the TRUE counts;
+ * entries at the stride and beyond are not written, and neither are the entries between the count and the stride (the Python mirror
+ * allocates the lists filled with -1).  status[r]: 1 = the seed was truncated (n_seed > seed_stride), 2 = the keyframe list exceeds kf_stride
+ * (plf_local_keyframes); 4 = the item list exceeds item_stride, 8 = the row is too long (plf_local_items).  Each call writes its own bits only.
+ * A row with an empty seed writes n_local_kf = 0 and status = 0, nothing else.
+ * Stateless; every array is DEVICE memory; asynchronous on `stream` (NULL = the null stream); nothing is read back; scratch comes from the
+ * stream-ordered pool.  PLF_E_BADARG is returned before any device work.
+ * ---------------------------------------------------------------------------------------------- */
+typedef struct {
+    int32_t n_rows;
+    const int32_t *seed_kf;          /* n_rows x seed_stride: conn_kf of a votes call */
+    const int32_t *n_seed;           /* n_rows: its n_conn (true counts; min(n_seed, seed_stride) entries are read) */
+    int32_t seed_stride;
+    const int32_t *covis_kf;         /* n_kf x covis_stride: ord_kf of a whole-graph connections call, row s = slot s */
+    const int32_t *n_covis;          /* n_kf: its n_ord */
+    int32_t covis_stride;
+    const int32_t *child_start;      /* n_kf + 1: CSR by slot of GetChilds(), each range in ascending key order */
+    const int32_t *child_kf;
+    const int32_t *kf_parent;        /* n_kf: slot of GetParent(), -1 = none */
+    const uint8_t *kf_bad;           /* optional, n_kf */
+    int32_t n_kf;
+} plf_local_kf_view;
+typedef struct {
+    int32_t n_best;                  /* 10 in the reference */
+    int32_t max_local;               /* 80 in the reference: size() > max_local ends the expansion */
+    int32_t kf_stride;
+    int32_t dense_max_kf;            /* 0 = default; as in plf_covis_params: 1 forces the hash marks */
+} plf_local_kf_params;
+int plf_local_keyframes(const plf_local_kf_view *v, const plf_local_kf_params *p, int32_t *local_kf, int32_t *n_local_kf, int32_t *status,
+                        int32_t device, void *stream);
+
+typedef struct {
+    int32_t n_rows;
+    const int32_t *local_kf;         /* n_rows x kf_stride */
+    const int32_t *n_local_kf;       /* n_rows (true counts; min(n_local_kf, kf_stride) entries are read) */
+    int32_t kf_stride;
+    const int32_t *kf_row_start;     /* n_kf + 1: each keyframe's mvpMapPoints (mvpMapLines) by slot */
+    const int32_t *kf_row_item;      /* ids; -1 or outside [0, n_items) = null */
+    int32_t n_kf;
+    const uint8_t *item_bad;         /* optional, n_items */
+    int32_t n_items;
+    const int32_t *frame_row_start;  /* optional, both or neither: n_rows + 1, the frames' own mvpMapPoints -- the rows of the votes call */
+    const int32_t *frame_row_item;
+} plf_local_items_view;
+typedef struct { int32_t item_stride, table_slots; } plf_local_items_params;   /* table_slots: 0 = default */
+/* seen (n_rows x item_stride, uint8) may be NULL */
+int plf_local_items(const plf_local_items_view *v, const plf_local_items_params *p, int32_t *local_item, int32_t *n_local_item, uint8_t *seen,
+                    int32_t *status, int32_t device, void *stream);
+
+/* Entry i of row r (i < min(n_local_item[r], item_stride)) copies row local_item[r, i] of the resident map arrays -- the ones
+ * plf_map_update_normal_depth and plf_map_distinctive_descriptors write in place -- to position r * item_stride + i of the outputs: the dense
+ * arrays of plf_frustum_points / plf_frustum_lines (world_pos: pos_floats = 3 or 6 floats per row, normal: 3, min_distance, max_distance) and
+ * the desc of plf_mappoint_view / plf_mapline_view (32 bytes, both sides 16-byte aligned).  A pair whose source or destination is NULL is
+ * skipped; an id outside [0, map_rows) copies nothing.  Positions from the count on are not written: what the frustum call makes of them is
+ * cleared by plf_local_visible.  One row or a span of rows: local_item / n_local_item point at the first.
+ * PLF_E_BADARG: NULL lists, negative sizes, item_stride < 1, pos_floats not 3 or 6, a misaligned desc. */
+typedef struct { const float *world_pos, *normal, *min_distance, *max_distance; const uint8_t *desc; int32_t map_rows, pos_floats; } plf_local_map_src;
+typedef struct { float *world_pos, *normal, *min_distance, *max_distance; uint8_t *desc; } plf_local_map_dst;
+int plf_local_gather(const int32_t *local_item, const int32_t *n_local_item, int32_t n_rows, int32_t item_stride, const plf_local_map_src *src,
+                     const plf_local_map_dst *dst, int32_t device, void *stream);
+
+/* in_view (n_rows x item_stride, uint8: what plf_frustum_* wrote for the gathered arrays) is rewritten IN PLACE: in_view[r, i] &= !seen[r, i]
+ * below the count, 0 from the count to item_stride; n_to_match[r] = the entries left.  visible (optional, n_items int32, the map's mnVisible):
+ * integer atomics, see above; it needs the frames' own rows (frame_row_*, item_bad as in plf_local_items) for the first loop's share, which is
+ * left out when they are NULL.  seen may be NULL (nothing seen).  Only the entries below item_stride exist for this call: for a row whose list
+ * exceeded item_stride (status 4 of plf_local_items) n_to_match and the second loop's share of visible are those of the kept head. */
+int plf_local_visible(const int32_t *local_item, const int32_t *n_local_item, const uint8_t *seen, int32_t n_rows, int32_t item_stride,
+                      uint8_t *in_view, int32_t *n_to_match, int32_t *visible, const int32_t *frame_row_start, const int32_t *frame_row_item,
+                      const uint8_t *item_bad, int32_t n_items, int32_t device, void *stream);
 
 #ifdef __cplusplus
 }

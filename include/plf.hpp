@@ -293,7 +293,7 @@ public:
     DeviceArray &operator=(const DeviceArray &) = delete;
     void reset(size_t n, int device = 0) { plf_device_free(p_); p_ = nullptr; n_ = n; void *q = nullptr; check(plf_device_alloc(device, n * sizeof(T), &q), "plf_device_alloc"); p_ = (T *)q; }
     void upload(const void *host, size_t n) { check(plf_upload(p_, host, n * sizeof(T), nullptr), "plf_upload"); }
-    void fill(int byte) { check(plf_fill(p_, byte, n_ * sizeof(T), nullptr), "plf_fill"); }
+    void fill(int byte, void *stream = nullptr) { check(plf_fill(p_, byte, n_ * sizeof(T), stream), "plf_fill"); }   // NULL: synchronous; else enqueued on `stream`
     std::vector<T> download() const { std::vector<T> v(n_); check(plf_download(v.data(), p_, n_ * sizeof(T), nullptr), "plf_download"); return v; }
     T *get() const { return p_; }
     size_t size() const { return n_; }
@@ -645,6 +645,61 @@ private:
     }
     plf_kfdb *db_ = nullptr;
     int S_, C_, device_ = 0;
+};
+
+// The local map of tracked frames over arrays the caller keeps on the device (include/plf.h, "Local map"): plf_local_keyframes, then plf_local_items, for
+// n_rows frames per call; Gather / Visible are plf_local_gather / plf_local_visible on the lists it holds.  Every call only enqueues on `stream` (the fills
+// that leave -1 beyond the counts included), so an object reused frame after frame on one stream is ordered behind its own readers there; readers on
+// OTHER streams are the caller's to order.  Nothing is read back: the members are the device lists, to be handed on to the frustum and projection calls or downloaded by the caller.
+class LocalMap {
+public:
+    struct Graph {   // the covisibility rows and the spanning tree by slot: plf_local_kf_view without the seed
+        const int32_t *covis_kf, *n_covis; int32_t covis_stride; const int32_t *child_start, *child_kf, *kf_parent; const uint8_t *kf_bad; int32_t n_kf;
+    };
+    struct Rows {    // each keyframe's mvpMapPoints (mvpMapLines) by slot
+        const int32_t *kf_row_start, *kf_row_item; const uint8_t *item_bad; int32_t n_items;
+    };
+    LocalMap(int n_rows, int kf_stride, int item_stride, int device = 0)
+        : local_kf((size_t)n_rows * kf_stride, device), n_local_kf(n_rows, device), kf_status(n_rows, device), local_item((size_t)n_rows * item_stride, device),
+          n_local_item(n_rows, device), item_status(n_rows, device), seen((size_t)n_rows * item_stride, device), n_rows_(n_rows), kf_stride_(kf_stride),
+          item_stride_(item_stride), device_(device) {}
+    // seed_kf / n_seed: conn_kf / n_conn of a PLF_COVIS_VOTES call; frame_row_*: its rows (may be NULL: nothing is seen)
+    void Update(const int32_t *seed_kf, const int32_t *n_seed, int seed_stride, const Graph &g, const Rows &r, const int32_t *frame_row_start = nullptr,
+                const int32_t *frame_row_item = nullptr, void *stream = nullptr, int n_best = 10, int max_local = 80)
+    {
+        local_kf.fill(0xFF, stream);                                    // on the caller's stream: behind whatever still reads the lists there, and no host wait
+        const plf_local_kf_view kv = {n_rows_, seed_kf, n_seed, seed_stride, g.covis_kf, g.n_covis, g.covis_stride, g.child_start, g.child_kf, g.kf_parent, g.kf_bad, g.n_kf};
+        const plf_local_kf_params kp = {n_best, max_local, kf_stride_, 0};
+        check(plf_local_keyframes(&kv, &kp, local_kf.get(), n_local_kf.get(), kf_status.get(), device_, stream), "Tracking::UpdateLocalKeyFrames");
+        Items(g.n_kf, r, frame_row_start, frame_row_item, stream);
+    }
+    // UpdateLocalPoints alone, over whatever local_kf / n_local_kf hold
+    void Items(int n_kf, const Rows &r, const int32_t *frame_row_start = nullptr, const int32_t *frame_row_item = nullptr, void *stream = nullptr)
+    {
+        const plf_local_items_view iv = {n_rows_, local_kf.get(), n_local_kf.get(), kf_stride_, r.kf_row_start, r.kf_row_item, n_kf, r.item_bad, r.n_items,
+                                         frame_row_start, frame_row_item};
+        const plf_local_items_params ip = {item_stride_, 0};
+        local_item.fill(0xFF, stream); seen.fill(0, stream);
+        check(plf_local_items(&iv, &ip, local_item.get(), n_local_item.get(), seen.get(), item_status.get(), device_, stream), "Tracking::UpdateLocalPoints");
+    }
+    void Gather(const plf_local_map_src &src, const plf_local_map_dst &dst, void *stream = nullptr) const
+    {
+        check(plf_local_gather(local_item.get(), n_local_item.get(), n_rows_, item_stride_, &src, &dst, device_, stream), "plf_local_gather");
+    }
+    // after plf_frustum_points / plf_frustum_lines on the gathered arrays: in_view &= !seen, n_to_match (n_rows), optionally the map's mnVisible
+    void Visible(uint8_t *in_view, int32_t *n_to_match, int32_t *visible = nullptr, const int32_t *frame_row_start = nullptr, const int32_t *frame_row_item = nullptr,
+                 const uint8_t *item_bad = nullptr, int n_items = 0, void *stream = nullptr) const
+    {
+        check(plf_local_visible(local_item.get(), n_local_item.get(), seen.get(), n_rows_, item_stride_, in_view, n_to_match, visible, frame_row_start, frame_row_item,
+                                item_bad, n_items, device_, stream), "Tracking::SearchLocalPoints");
+    }
+    DeviceArray<int32_t> local_kf, n_local_kf, kf_status, local_item, n_local_item, item_status;
+    DeviceArray<uint8_t> seen;
+    int n_rows() const { return n_rows_; }
+    int kf_stride() const { return kf_stride_; }
+    int item_stride() const { return item_stride_; }
+private:
+    int n_rows_, kf_stride_, item_stride_, device_;
 };
 
 }  // namespace plf
@@ -1448,6 +1503,138 @@ template <class KeyFrameT> KeyFrameCullingResult<KeyFrameT> KeyFrameCulling(cons
     }
     out.nMPs = d_mps.download(); out.nRedundantObservations = d_red.download(); out.decision = d_dec.download();
     for (int j = 0; j < C; j++) if (out.decision[j] == 1) out.erase.push_back(vpLocalKeyFrames[j]);
+    return out;
+}
+// Tracking::UpdateLocalMap -- UpdateLocalKeyFrames (so@0x4d5a0) and UpdateLocalPoints (so@0x49cc0) -- over the reference's own Frame / KeyFrame / MapPoint
+// classes, for one frame: the votes, the expansion and the point list run on the device back to back (plf_covis_count, plf_local_keyframes,
+// plf_local_items), one download at the end.  Reads mCurrentFrame.mvpMapPoints, pMP->isBad() / GetObservations(), pKF->isBad() / GetMapPointMatches() /
+// GetBestCovisibilityKeyFrames(10) / GetChilds() / GetParent(); writes what the two functions leave: a bad own point set to NULL, mvpLocalKeyFrames,
+// mvpLocalMapPoints, mpReferenceKF (when there is a pKFmax).  The marks (mnTrackReferenceForFrame) are not written: nothing reads them afterwards.
+// The device work runs on `stream` (NULL: the null stream); the uploads before it and the download after it are synchronous.
+// `seen` says which local points carry mnLastFrameSeen == the frame's id after the first loop of SearchLocalPoints.
+// A frame without a single vote keeps mvpLocalKeyFrames, as the reference does, and only the points are listed again.
+// EVERY CALL uploads what it reads, starting from host pointer members: every keyframe that observes an own point (the possible seeds) with its ten
+// neighbours, children and parent, and the rows of all of these; a caller whose map is resident uses plf::LocalMap and uploads nothing.
+template <class KeyFrameT, class MapPointT> struct LocalMapResult {
+    std::vector<uint8_t> seen;            // parallel to mvpLocalMapPoints
+    KeyFrameT *pKFmax = nullptr;
+    int votes = 0;                        // of pKFmax
+};
+template <class KeyFrameT, class MapPointT, class FrameT>
+LocalMapResult<KeyFrameT, MapPointT> UpdateLocalMap(FrameT &mCurrentFrame, std::vector<KeyFrameT *> &mvpLocalKeyFrames, std::vector<MapPointT *> &mvpLocalMapPoints,
+                                                     KeyFrameT *&mpReferenceKF, int device = 0, void *stream = nullptr)
+{
+    LocalMapResult<KeyFrameT, MapPointT> out;
+    std::vector<KeyFrameT *> kfs;
+    detail::KeyFrameSlots kf_slot;
+    auto slot_of = [&](KeyFrameT *pKF) { return kf_slot(pKF, [&](KeyFrameT *first) { kfs.push_back(first); }); };
+    std::vector<MapPointT *> pts;
+    std::unordered_map<MapPointT *, int> point_id;
+    std::vector<uint8_t> point_bad;
+    auto id_of = [&](MapPointT *pMP) {
+        const auto at = point_id.emplace(pMP, (int)pts.size());
+        if (at.second) { pts.push_back(pMP); point_bad.push_back(pMP->isBad()); }
+        return at.first->second;
+    };
+    // ---- the frame's own row and the observations of its points: the votes
+    std::vector<int32_t> frame_start{0}, frame_item, obs_start{0}, obs_kf;
+    for (auto &pMP : mCurrentFrame.mvpMapPoints) {
+        if (pMP && pMP->isBad()) pMP = nullptr;
+        if (!pMP) { frame_item.push_back(-1); continue; }
+        const size_t known = pts.size();
+        const int id = id_of(pMP);
+        if (pts.size() != known) {
+            const auto observations = pMP->GetObservations();
+            for (const auto &ob : observations) obs_kf.push_back(slot_of(ob.first));
+            obs_start.push_back((int32_t)obs_kf.size());
+        }
+        frame_item.push_back(id);
+    }
+    frame_start.push_back((int32_t)frame_item.size());
+    const int own_points = (int)pts.size(), S1 = (int)kfs.size();
+    const bool voted = S1 > 0;
+    // ---- the possible seeds with their neighbours, children and parent; without a vote the list that stays
+    std::vector<int32_t> covis, n_covis, child_start{0}, child_kf, parent, keep;
+    const int n_best = 10;
+    for (int s = 0; s < S1; s++) {
+        KeyFrameT *pKF = kfs[s];                                        // (kfs grows: no reference is held across slot_of)
+        const std::vector<KeyFrameT *> vNeighs = pKF->GetBestCovisibilityKeyFrames(n_best);
+        n_covis.push_back((int32_t)std::min<size_t>(vNeighs.size(), (size_t)n_best));
+        for (int i = 0; i < n_best; i++) covis.push_back(i < (int)vNeighs.size() ? slot_of(vNeighs[i]) : -1);
+        const std::set<KeyFrameT *> spChilds = pKF->GetChilds();
+        for (KeyFrameT *pChild : spChilds) child_kf.push_back(slot_of(pChild));
+        child_start.push_back((int32_t)child_kf.size());
+        KeyFrameT *pParent = pKF->GetParent();
+        parent.push_back(pParent ? slot_of(pParent) : -1);
+    }
+    if (!voted) for (KeyFrameT *pKF : mvpLocalKeyFrames) keep.push_back(slot_of(pKF));
+    const int S = (int)kfs.size();
+    if (S == 0) { mvpLocalMapPoints.clear(); return out; }
+    covis.resize((size_t)S * n_best, -1); n_covis.resize(S, 0); child_start.resize(S + 1, (int32_t)child_kf.size()); parent.resize(S, -1);
+    // ---- slots in ADDRESS order from here on: the slot is then the key of the reference's std::map<KeyFrame*, int>, and the votes need no kf_key
+    std::vector<int> order(S);
+    for (int s = 0; s < S; s++) order[s] = s;
+    std::sort(order.begin(), order.end(), [&](int x, int y) { return (uintptr_t)kfs[x] < (uintptr_t)kfs[y]; });
+    std::vector<int32_t> to(S);
+    for (int i = 0; i < S; i++) to[order[i]] = i;
+    auto moved = [&](int32_t s) { return s < 0 ? -1 : to[s]; };
+    {
+        std::vector<KeyFrameT *> kfs2(S);
+        std::vector<int32_t> covis2((size_t)S * n_best), n_covis2(S), parent2(S), child_start2{0}, child_kf2;
+        for (int i = 0; i < S; i++) {
+            const int o = order[i];
+            kfs2[i] = kfs[o]; n_covis2[i] = n_covis[o]; parent2[i] = moved(parent[o]);
+            for (int j = 0; j < n_best; j++) covis2[(size_t)i * n_best + j] = moved(covis[(size_t)o * n_best + j]);
+            for (int32_t c = child_start[o]; c < child_start[o + 1]; c++) child_kf2.push_back(moved(child_kf[c]));
+            child_start2.push_back((int32_t)child_kf2.size());
+        }
+        kfs.swap(kfs2); covis.swap(covis2); n_covis.swap(n_covis2); parent.swap(parent2); child_start.swap(child_start2); child_kf.swap(child_kf2);
+        for (int32_t &k : obs_kf) k = moved(k);
+        for (int32_t &k : keep) k = moved(k);
+    }
+    // ---- the rows of every keyframe that can end up in the list
+    std::vector<int32_t> row_start{0}, row_item;
+    std::vector<uint8_t> kf_bad(S);
+    for (int s = 0; s < S; s++) {
+        kf_bad[s] = kfs[s]->isBad();
+        const std::vector<MapPointT *> vpMPs = kfs[s]->GetMapPointMatches();
+        for (MapPointT *pMP : vpMPs) row_item.push_back(pMP ? id_of(pMP) : -1);
+        row_start.push_back((int32_t)row_item.size());
+    }
+    const int P = (int)pts.size(), kf_stride = std::max(S, (int)keep.size()), item_stride = std::max(P, 1);
+    // one element of padding each: never an empty allocation; beyond the CSR ranges, never read
+    frame_item.push_back(-1); obs_kf.push_back(-1); child_kf.push_back(-1); row_item.push_back(-1); point_bad.push_back(0);
+    plf::DeviceArray<int32_t> d_fs(frame_start, device), d_fi(frame_item, device), d_os(obs_start, device), d_ok(obs_kf, device), d_cov(covis, device), d_ncov(n_covis, device),
+        d_cs(child_start, device), d_ck(child_kf, device), d_par(parent, device), d_rs(row_start, device), d_ri(row_item, device), d_seed(std::max(S1, 1), device),
+        d_w(std::max(S1, 1), device), d_nseed(1, device), d_mk(1, device), d_mw(1, device);
+    plf::DeviceArray<uint8_t> d_pbad(point_bad, device), d_kbad(kf_bad, device);
+    plf::LocalMap lm(1, kf_stride, item_stride, device);
+    const plf::LocalMap::Rows rows = {d_rs.get(), d_ri.get(), d_pbad.get(), P};
+    if (voted) {
+        const plf_covis_view v = {1, d_fs.get(), d_fi.get(), nullptr, own_points, d_os.get(), d_ok.get(), d_pbad.get(), S, d_kbad.get(), nullptr};
+        const plf_covis_params p = {PLF_COVIS_VOTES, 1, std::max(S1, 1), 0, 0};
+        plf::check(plf_covis_count(&v, &p, d_seed.get(), d_w.get(), d_nseed.get(), nullptr, nullptr, nullptr, d_mk.get(), d_mw.get(), device, stream),
+                   "Tracking::UpdateLocalKeyFrames");
+        const plf::LocalMap::Graph g = {d_cov.get(), d_ncov.get(), n_best, d_cs.get(), d_ck.get(), d_par.get(), d_kbad.get(), S};
+        lm.Update(d_seed.get(), d_nseed.get(), std::max(S1, 1), g, rows, d_fs.get(), d_fi.get(), stream, n_best, 80);
+    } else {
+        keep.resize(kf_stride, -1);
+        const std::vector<int32_t> n_keep(1, (int32_t)mvpLocalKeyFrames.size());
+        lm.local_kf.upload(keep.data(), keep.size()); lm.n_local_kf.upload(n_keep.data(), 1);
+        lm.Items(S, rows, d_fs.get(), d_fi.get(), stream);
+    }
+    // ---- one download: the lists by pointer
+    const std::vector<int32_t> h_item = lm.local_item.download(), h_n = lm.n_local_item.download();   // a NULL-stream download waits for the device first
+    const std::vector<uint8_t> h_seen = lm.seen.download();
+    if (voted) {
+        const std::vector<int32_t> h_kf = lm.local_kf.download(), h_nkf = lm.n_local_kf.download();
+        mvpLocalKeyFrames.clear();
+        for (int i = 0; i < h_nkf[0]; i++) mvpLocalKeyFrames.push_back(kfs[h_kf[i]]);
+        const int kmax = d_mk.download()[0];
+        if (kmax >= 0) { out.pKFmax = kfs[kmax]; out.votes = d_mw.download()[0]; mpReferenceKF = out.pKFmax; }
+    }
+    mvpLocalMapPoints.clear();
+    for (int i = 0; i < h_n[0]; i++) { mvpLocalMapPoints.push_back(pts[h_item[i]]); out.seen.push_back(h_seen[i]); }
     return out;
 }
 }  // namespace ORB_SLAM2_PLF

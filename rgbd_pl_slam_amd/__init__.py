@@ -14,3 +14,5 @@ from . import covisibility  # noqa: F401
 from .covisibility import update_connections, local_keyframe_votes, Covisibility  # noqa: F401
 from . import culling  # noqa: F401
 from .culling import keyframe_culling, map_point_culling, CullMap  # noqa: F401
+from . import localmap  # noqa: F401
+from .localmap import local_keyframes, local_items, local_gather, local_visible, update_local_map, children_csr, LocalMap  # noqa: F401

@@ -266,3 +266,42 @@ def cull_prototypes(l):
     l.plf_keyframe_culling.argtypes = [C.POINTER(CullView), C.POINTER(CullParams), P, P, I, P, P, P, P, P, P, P, I, P]
     l.plf_map_point_culling.argtypes = [I, P, P, P, P, P, P, P, I, P, C.c_int64, I, P, I, P]
     return l
+
+
+# ---- local map (include/plf.h, "Local map")
+class LocalKfView(C.Structure):
+    _fields_ = [("n_rows", C.c_int32), ("seed_kf", C.c_void_p), ("n_seed", C.c_void_p), ("seed_stride", C.c_int32), ("covis_kf", C.c_void_p),
+                ("n_covis", C.c_void_p), ("covis_stride", C.c_int32), ("child_start", C.c_void_p), ("child_kf", C.c_void_p), ("kf_parent", C.c_void_p),
+                ("kf_bad", C.c_void_p), ("n_kf", C.c_int32)]
+
+
+class LocalKfParams(C.Structure):
+    _fields_ = [("n_best", C.c_int32), ("max_local", C.c_int32), ("kf_stride", C.c_int32), ("dense_max_kf", C.c_int32)]
+
+
+class LocalItemsView(C.Structure):
+    _fields_ = [("n_rows", C.c_int32), ("local_kf", C.c_void_p), ("n_local_kf", C.c_void_p), ("kf_stride", C.c_int32), ("kf_row_start", C.c_void_p),
+                ("kf_row_item", C.c_void_p), ("n_kf", C.c_int32), ("item_bad", C.c_void_p), ("n_items", C.c_int32), ("frame_row_start", C.c_void_p),
+                ("frame_row_item", C.c_void_p)]
+
+
+class LocalItemsParams(C.Structure):
+    _fields_ = [("item_stride", C.c_int32), ("table_slots", C.c_int32)]
+
+
+class LocalMapSrc(C.Structure):
+    _fields_ = [("world_pos", C.c_void_p), ("normal", C.c_void_p), ("min_distance", C.c_void_p), ("max_distance", C.c_void_p), ("desc", C.c_void_p),
+                ("map_rows", C.c_int32), ("pos_floats", C.c_int32)]
+
+
+class LocalMapDst(C.Structure):
+    _fields_ = [("world_pos", C.c_void_p), ("normal", C.c_void_p), ("min_distance", C.c_void_p), ("max_distance", C.c_void_p), ("desc", C.c_void_p)]
+
+
+def localmap_prototypes(l):
+    P, I = C.c_void_p, C.c_int32
+    l.plf_local_keyframes.argtypes = [C.POINTER(LocalKfView), C.POINTER(LocalKfParams), P, P, P, I, P]
+    l.plf_local_items.argtypes = [C.POINTER(LocalItemsView), C.POINTER(LocalItemsParams), P, P, P, P, I, P]
+    l.plf_local_gather.argtypes = [P, P, I, I, C.POINTER(LocalMapSrc), C.POINTER(LocalMapDst), I, P]
+    l.plf_local_visible.argtypes = [P, P, P, I, I, P, P, P, P, P, P, I, I, P]
+    return l
