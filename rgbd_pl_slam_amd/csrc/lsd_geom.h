@@ -133,18 +133,38 @@ struct NfaState { LsdRect rec; double log_nfa; int frame, rect; };
 // batch driver (batch_host.hip): the status word of the batch just enqueued on `s`, copied to pinned host memory in stream order (line_host.hip)
 int plf_line_status_async(plf_line *h, int32_t *host_dst, int32_t *host_flags, int n, hipStream_t s);
 
-// ---- kernels launched by line_host.hip.  lsd_kernels.hip: pre-pass, seeds, region growing
+// ---- kernels launched by line_host.hip (line_enqueue), under the file that defines them.  Stage map of a call, B frames per launch:
+//   k_lsd_pre                            GaussianBlur(7x7, sigma 0.75) on the image converted to double, resize(0.8, INTER_LINEAR), ll_angle: 2x2 gradient, modgrad,
+//                                        level-line angle (cv::fastAtan2); the bitmap of the static singles
+//   k_lsd_maxgrad, k_lsd_seedkeys        seed_order 1 only: keys of the published LSD seed order, sorted per frame (the default is the raster order of OpenCV 3.3)
+//   region growing                       seed scan + region_grow + region2rect + refine (ORDER-DEPENDENT: lsd_kernels.hip), by one of three schedules --
+//     k_lsd_spec_*                         few frames in flight: bands of rows grown speculatively by waves of their own, then validated in rounds or committed in order
+//     k_lsd_regions_lat                    few frames, no speculation possible: one wave per frame, three more warm the L2
+//     k_lsd_balance, k_lsd_regions2        large batches: one wave per frame, the frames dealt to the waves by chain length
+//   k_nfa_*                              rect_improve = 5 search stages of (pixel count, NFA math) per rectangle: k_nfa_small / k_nfa_small2 (16 lanes per rectangle) for
+//                                        the rectangles the NFA table covers, the staged k_nfa_init / _clamp / _count* / _eval / _math over work lists of the whole batch
+//                                        for the rest (a wave or 16 lanes count a rectangle's pixels, one lane does its NFA math), or k_nfa_fused (one wave per rectangle)
+//   k_blur5_sobel3 / k_sobel3            gradient plane of the descriptor (beside k_lsd_pre on a side stream, or behind it)
+//   k_lsd_finalize, k_lbd                ordered compaction -> segments -> KeyLine fields -> top-N by response; LBD descriptors
+// (DESIGN.md section 4 has the index: which knob and batch size launches which kernel, and the test that runs it.)
+// lsd_pre.hip: blur, resize, level-line angles; seed keys of the published order; the chain-length diagnostic
 __global__ void k_lsd_pre(const uint8_t *in, ptrdiff_t pitch, ptrdiff_t fstride, float *ang, double *modgrad, double2 *cs, float2 *cs0, LsdGeom g, LsdTaps t, const int *xofs, const float2 *xa,
                           const int *yofs, const float2 *yb, int *defcount);
-__global__ void k_lsd_balance(const int *cost, int *perm, int B, int fpw);
 __global__ void k_lsd_maxgrad(const float *ang_all, const double *modgrad_all, double *maxgrad, LsdGeom g);
 __global__ void k_lsd_seedkeys(const float *ang_all, const double *modgrad_all, const double *maxgrad, uint32_t *keys_all, LsdGeom g);
 __global__ void k_lsd_count_used(const float *ang_all, int *out, LsdGeom g);
+// lsd_kernels.hip: region growing -- the serial chain, one wave per frame (the _budget instances are the same kernels with the time budget of
+// plf_line_params.max_ms compiled in: separate instances, the default ones read no clock)
+__global__ void k_lsd_balance(const int *cost, int *perm, int B, int fpw);
 __global__ void k_lsd_regions2(float *ang_all, const double *modgrad_all, const double2 *cs_all, const float2 *cs0_all, uint32_t *rxy_all, LsdRect *rects_all, int *nrect, int *status, LsdGeom g,
                                const uint32_t *seeds_all, int nframes, const int *perm);
 __global__ void k_lsd_regions_lat(float *ang_all, const double *modgrad_all, const double2 *cs_all, const float2 *cs0_all, uint32_t *rxy_all, LsdRect *rects_all, int *nrect, int *status, LsdGeom g,
                                   const uint32_t *seeds_all, int *sink);
-// the speculative schedule: row bands grown by waves of their own, validated in rounds or committed in order
+__global__ void k_lsd_regions2_budget(float *ang_all, const double *modgrad_all, const double2 *cs_all, const float2 *cs0_all, uint32_t *rxy_all, LsdRect *rects_all, int *nrect, int *status,
+                                      LsdGeom g, const uint32_t *seeds_all, int nframes, const int *perm);
+__global__ void k_lsd_regions_lat_budget(float *ang_all, const double *modgrad_all, const double2 *cs_all, const float2 *cs0_all, uint32_t *rxy_all, LsdRect *rects_all, int *nrect, int *status,
+                                         LsdGeom g, const uint32_t *seeds_all, int *sink);
+// lsd_kernels.hip: region growing -- the speculative schedule, row bands grown by waves of their own, validated in rounds or committed in order (and its _budget instances)
 __global__ void k_lsd_spec_fused(float *ang_all, const double *modgrad_all, const double2 *cs_all, const float2 *cs0_all, uint32_t *rxy_all, LsdRect *rects_all, int *nrect, int *status, LsdGeom g,
                                  SpecBufs SB, int *stats, int B);
 __global__ void k_lsd_spec_rows(const float *ang_all, LsdGeom g, SpecBufs SB, int *rowcnt);
@@ -158,17 +178,12 @@ __global__ void k_lsd_spec_prefix(SpecBufs SB, int round);
 __global__ void k_lsd_spec_clear(SpecBufs SB, int *rowcnt, int rounds_state);
 __global__ void k_lsd_spec_validate(float *ang_all, const double *modgrad_all, const double2 *cs_all, const float2 *cs0_all, LsdGeom g, SpecBufs SB, int round);
 __global__ void k_lsd_spec_assemble(LsdRect *rects_all, int *nrect, int *status, LsdGeom g, SpecBufs SB, int last);
-// the same kernels with the time budget of plf_line_params.max_ms compiled in (separate instances: the default ones read no clock)
-__global__ void k_lsd_regions2_budget(float *ang_all, const double *modgrad_all, const double2 *cs_all, const float2 *cs0_all, uint32_t *rxy_all, LsdRect *rects_all, int *nrect, int *status,
-                                      LsdGeom g, const uint32_t *seeds_all, int nframes, const int *perm);
-__global__ void k_lsd_regions_lat_budget(float *ang_all, const double *modgrad_all, const double2 *cs_all, const float2 *cs0_all, uint32_t *rxy_all, LsdRect *rects_all, int *nrect, int *status,
-                                         LsdGeom g, const uint32_t *seeds_all, int *sink);
 __global__ void k_lsd_spec_fused_budget(float *ang_all, const double *modgrad_all, const double2 *cs_all, const float2 *cs0_all, uint32_t *rxy_all, LsdRect *rects_all, int *nrect, int *status,
                                         LsdGeom g, SpecBufs SB, int *stats, int B);
 __global__ void k_lsd_spec_grow_budget(float *ang_all, const double *modgrad_all, const double2 *cs_all, const float2 *cs0_all, LsdGeom g, SpecBufs SB);
 __global__ void k_lsd_spec_commit_budget(float *ang_all, const double *modgrad_all, const double2 *cs_all, const float2 *cs0_all, uint32_t *rxy_all, LsdRect *rects_all, int *nrect, int *status,
                                          LsdGeom g, SpecBufs SB, int *stats);
-// NFA validation
+// lsd_nfa.hip: NFA validation
 __global__ void k_nfa_init(const LsdRect *rects_all, const int *nrect, uint8_t *keep_all, NfaEntry *entries, NfaState *states, int *counters, int *status, LsdGeom g);
 __global__ void k_nfa_clamp(int *counters, int *status, LsdGeom g);
 __global__ void k_nfa_count(const float *ang_all, const NfaEntry *entries, const int *counters, int cidx, int mult, NfaCounts *counts, LsdGeom g);

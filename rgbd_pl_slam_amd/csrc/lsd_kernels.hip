@@ -1,413 +1,27 @@
-// lsd_kernels.hip -- LSD line-segment detector on gfx950, restating what the reference reaches through
-// LineSegment::ExtractLineSegment -> cv::line_descriptor::LSDDetector::detect -> cv::LineSegmentDetector
-// (include/ExtractLineSegment.h:38; OpenCV 3.3 imgproc/lsd.cpp, LSD_REFINE_ADV, default parameters).
+// lsd_kernels.hip -- LSD region growing on gfx950: the seed loop of cv::LineSegmentDetector with region_grow, region2rect, reduce_region_radius and refine
+// (OpenCV 3.3 imgproc/lsd.cpp, LSD_REFINE_ADV; the reference gets there through LineSegment::ExtractLineSegment, include/ExtractLineSegment.h:38).  The per-seed
+// pipeline comes first, then the serial chain (k_lsd_balance, k_lsd_regions2, k_lsd_regions_lat) and the speculative schedule (k_lsd_spec_*), each also as _budget
+// instances; all launched by line_enqueue (line_host.hip).  The stages before and after it are lsd_pre.hip and lsd_nfa.hip; the stage map is in lsd_geom.h.
 //
-// Stage map (B frames per launch):
-//   k_lsd_pre                           GaussianBlur(7x7, sigma 0.75) on the image converted to double, resize(0.8,
-//                                       INTER_LINEAR), ll_angle: 2x2 gradient, modgrad, level-line angle (cv::fastAtan2)
-//   k_lsd_regions                       seed scan + region_grow + region2rect + refine   (ORDER-DEPENDENT, see below)
-//   k_nfa_init / k_nfa_count / k_nfa_math   rect_improve = 5 search stages of (pixel count, NFA math) per rectangle
-//   k_lsd_finalize                      ordered compaction -> segments -> KeyLine fields -> top-N by response
-//
-// The only inherently sequential part of LSD is k_lsd_regions: regions are grown greedily in seed order, every
-// accepted pixel changes the running region angle (float sums + fastAtan2), and `used` marks made by one region
-// (and un-made by refine) decide what later seeds see.  That chain is kept EXACTLY: one wave owns one frame and
-// performs the accept steps in the reference order, while its 64 lanes cooperate on everything that is
-// order-free inside a step (the 3x3 neighbourhood tests, pixel gathers, min/max extents, the rectangle pixel
-// counts).  Floating-point sums whose order matters are accumulated serially in the reference order.
-// The NFA validation does not touch `used`, so it is split off and runs one lane per rectangle.
-// Frames are independent, so a batch keeps 1 wave x B frames busy (the batch is the parallel axis).
-#include "plf_common.h"
-#include "lsd_geom.h"
+// Region growing is the only inherently sequential part of LSD: regions are grown greedily in seed order, every accepted pixel changes the running region angle
+// (float sums + fastAtan2), and the USED marks made by one region (and un-made by refine) decide what later seeds see.  That chain is kept EXACTLY: one wave owns
+// one frame -- or, in the speculative schedule, one band of it, checked afterwards against the true flags -- and performs the accept steps in the reference
+// order, while its 64 lanes cooperate on everything that is order-free inside a step (the 3x3 neighbourhood tests, pixel gathers, min/max extents).
+// Floating-point sums whose order matters are accumulated serially in the reference order.  Frames are independent, so a batch keeps 1 wave x B frames busy
+// (the batch is the parallel axis).
+#include "lsd_dev.h"
 
-#define NOTDEF_F (-1024.0f)
-// issue priority of the THROUGHPUT kernels of the line stream (k_lsd_pre, the NFA kernels): the line stream is the critical path of the large-batch step and its
-// front / tail run beside ORB tiles (priority 2) and matcher waves (0)
-#ifndef PLF_LINE_PRIO
-#define PLF_LINE_PRIO 0
-#endif
-#define PLF_LINE_SETPRIO() do { if (PLF_LINE_PRIO) __builtin_amdgcn_s_setprio(PLF_LINE_PRIO); } while (0)
+// (switches read by the per-seed pipeline, or by both the chain and the speculative schedule)
 #ifndef PLF_SPEC_PF_REFINE
 #define PLF_SPEC_PF_REFINE 1   // (experiment: fetch-ahead in refine's regrowth of the band waves, STG == 0)
 #endif
-#define PI_D 3.1415926535897932384626433832795
-#define M_3_2_PI_D (3 * 3.14159265358979323846 / 2)
-#define M_2__PI_D (2 * 3.14159265358979323846)
-#define DEG2RAD_D (PI_D / 180)
-
-// ------------------------------------------------------------------------------------------------
-// k_lsd_pre: GaussianBlur(7x7, sigma 0.75) of the image converted to double, resize(0.8, INTER_LINEAR) with float
-// coefficients, and ll_angle, fused per 64 x 16 tile of the scaled image; every intermediate lives in LDS
-// (identical operation order to cv::RowFilter / SymmColumnFilter / resize / ll_angle, see oracle/lsd_oracle.c).
-//   row pass   tmp(y, x)  = sum_i k[i] * double(u8(y, refl101(x - 3 + i)))                      i = 0..6, in this order
-//   col pass   blur(y, x) = k[3] * tmp(y, x) + 0.0, then += k[3+i] * (tmp(refl(y+i)) + tmp(refl(y-i)))   i = 1..3
-//   resize     r0 = S0[sx] * a.x + S0[sx+1] * a.y (or S0[sx] * 1.0 for dx >= xmax), same for r1; out = r0 * b.x + r1 * b.y
-//   ll_angle   2x2 gradient, modgrad (double), level-line angle in DEGREES as cv::fastAtan2 returns it (the reference
-//              stores double(deg) * DEG_TO_RADS, recomputed on use), NOTDEF_F where the gradient is too small or on
-//              the last row/column.  cs: cos and sin of the float-rounded angle, the increments region_grow adds to
-//              its sums.  cs0: float(cos(angle)), float(sin(angle)) of the un-rounded angle, the initial sums of a
-//              region seeded here.
-// A tile of 65 x 17 scaled pixels (one more column/row for the gradient) needs at most PRE_SC x PRE_SR blurred source
-// pixels (checked on the host for the actual geometry) and 6 more rows of the row pass.
-// ------------------------------------------------------------------------------------------------
-typedef unsigned long long __attribute__((aligned(1))) plf_u64u;   // 8-byte access at byte alignment (legal on gfx950 global memory)
-typedef uint32_t __attribute__((aligned(1))) plf_u32u_pre;
-// (PRE_TW, PRE_TH, PRE_SC, PRE_SR, PRE_NT: lsd_geom.h -- the host sizes the launch and checks the geometry with the same constants)
-__global__ void __launch_bounds__(PRE_NT) k_lsd_pre(const uint8_t *__restrict__ in, ptrdiff_t pitch, ptrdiff_t fstride, float *__restrict__ ang,
-                                                 double *__restrict__ modgrad, double2 *__restrict__ cs, float2 *__restrict__ cs0, LsdGeom g,
-                                                 LsdTaps t, const int *__restrict__ xofs, const float2 *__restrict__ xa,
-                                                 const int *__restrict__ yofs, const float2 *__restrict__ yb, int *__restrict__ defcount)
-{
-    PLF_LINE_SETPRIO();
-    // LDS: the row-pass tile (22.5 KB; the column pass overwrites it IN PLACE with the blurred tile -- every thread first reads the 14 rows behind its
-    // 8 outputs into registers, one barrier, then writes -- and the list of defined pixels reuses it at the end) + the scaled tile (8.8 KB): 31 KB per
-    // workgroup, 4 resident tiles of 8 waves per CU (a separate 18 KB blurred tile made it 40 KB / 3 tiles)
-    constexpr int PRE_TMP = (PRE_SR + 12) * PRE_SC * 8 >= PRE_TW * PRE_TH * 20 ? (PRE_SR + 12) * PRE_SC : (PRE_TW * PRE_TH * 20 + 7) / 8;
-    __shared__ double s_tmp[PRE_TMP];   // (+6 rows for the row pass, +6 that only keep the column pass's unconditional reads in bounds)
-    __shared__ double s_sc[(PRE_TH + 1) * (PRE_TW + 1)];
-    double *s_blur = s_tmp;   // blurred row r at s_tmp row r (after the column pass)
-    const int f = blockIdx.z, tid = threadIdx.x;
-    const int dx0 = blockIdx.x * PRE_TW, dy0 = blockIdx.y * PRE_TH;
-    const int dx1 = min(dx0 + PRE_TW, g.sw - 1), dy1 = min(dy0 + PRE_TH, g.sh - 1);
-    const int c_lo = xofs[dx0], c_hi = min(xofs[dx1] + 1, g.w - 1);
-    const int r_lo = min(max(yofs[dy0], 0), g.h - 1), r_hi = min(max(yofs[dy1] + 1, 0), g.h - 1);
-    const int nc = c_hi - c_lo + 1, nr = r_hi - r_lo + 1;
-    const uint8_t *img = in + (size_t)f * fstride;
-    // row pass: per output the same products and the same order of additions as cv::RowFilter, k[0] d[j] + k[1] d[j+1] + ... + k[6] d[j+6].
-    // One item = 8 consecutive outputs of one row = one thread ((PRE_SR + 6) rows x 11 groups <= PRE_NT: one round, one index division, one row address): their 14
-    // source bytes are converted once, and since k[q] and k[6 - q] are the same bits (LsdTaps::symmetric) k[q] * d and k[6 - q] * d are the same IEEE product of
-    // the same operands -- written with the four distinct taps the compiler computes each once: 44 products per item instead of 56, none of them different.
-    // (Items of 4 outputs in two rounds, a product per tap and plf_reflect101's loop on every item's row: 2 x 120 instructions for these 8 outputs, now ~150.)
-    if (t.symmetric) {
-        static_assert((PRE_SR + 6) * (PRE_SC / 8) <= PRE_NT && PRE_SC % 8 == 0, "one row-pass item per thread");
-        const int r = tid / (PRE_SC / 8), c = 8 * (tid - r * (PRE_SC / 8));
-        if (r < nr + 6 && c < nc) {
-            const uint8_t *row = img + (size_t)plf_reflect101_near(r_lo - 3 + r, g.h) * pitch;
-            const int x = c_lo + c;
-            double *dst = s_tmp + r * PRE_SC + c;
-            const double k0 = t.k[0], k1 = t.k[1], k2 = t.k[2], k3 = t.k[3];
-            if (g.w >= 16) {
-                unsigned long long w0, w1;   // the 14 source bytes x - 3 .. x + 10: byte q is byte sel(q) of (w0, w1)
-                double d[14];
-                if (x >= 3 && x + 10 < g.w) {   // interior: two unaligned 8-byte loads, x - 3 .. x + 4 and x + 3 .. x + 10
-                    w0 = *(const plf_u64u *)(row + x - 3); w1 = *(const plf_u64u *)(row + x + 3);
-#pragma unroll
-                    for (int q = 0; q < 14; q++) d[q] = (double)(int)(((q < 8 ? w0 : w1) >> (8 * (q < 8 ? q : q - 6))) & 0xFF);
-                } else {
-                    // image border (the first / last groups of a row): the reflected source bytes are picked out of one 16-byte window that lies inside the
-                    // row.  (A per-tap reflected byte load here ran on every wave of the tiles at the left / right image edge, because each of their waves
-                    // holds a border group: a third of the kernel's time, 13.5 -> 9.1 ms per 4096 frames.)
-                    const int base = min(max(x - 3, 0), g.w - 16);
-                    w0 = *(const plf_u64u *)(row + base); w1 = *(const plf_u64u *)(row + base + 8);
-#pragma unroll
-                    for (int q = 0; q < 14; q++) {
-                        const int pq = min(max(plf_reflect101_near(x - 3 + q, g.w) - base, 0), 15);   // (clamped: only for outputs beyond the tile's last column)
-                        d[q] = (double)(int)((((pq & 8) ? w1 : w0) >> (8 * (pq & 7))) & 0xFF);
-                    }
-                }
-#pragma unroll
-                for (int j = 0; j < 8; j++) {
-                    double s_ = k0 * d[j];
-                    s_ += k1 * d[j + 1]; s_ += k2 * d[j + 2]; s_ += k3 * d[j + 3]; s_ += k2 * d[j + 4]; s_ += k1 * d[j + 5]; s_ += k0 * d[j + 6];
-                    dst[j] = s_;
-                }
-            } else {   // images narrower than 16 pixels
-#pragma unroll 1
-                for (int j = 0; j < 8; j++) {
-                    double s_ = t.k[0] * (double)row[plf_reflect101(x + j - 3, g.w)];
-#pragma unroll 1
-                    for (int q = 1; q < 7; q++) s_ += t.k[q] * (double)row[plf_reflect101(x + j - 3 + q, g.w)];
-                    dst[j] = s_;
-                }
-            }
-        }
-    } else {
-        // taps that are not pairwise the same bits: one item = 4 consecutive columns of one row (10 source bytes converted once), a product per tap
-        for (int i = tid; i < (nr + 6) * (PRE_SC / 4); i += PRE_NT) {
-            const int r = i / (PRE_SC / 4), c = 4 * (i - r * (PRE_SC / 4));
-            if (c >= nc) continue;
-            const uint8_t *row = img + (size_t)plf_reflect101(r_lo - 3 + r, g.h) * pitch;
-            const int x = c_lo + c;
-            double o[4];
-            if (x >= 3 && x + 8 < g.w) {   // interior: bytes x-3 .. x+6 from one unaligned 8-byte and one 4-byte load
-                const unsigned long long lo8 = *(const plf_u64u *)(row + x - 3);
-                const uint32_t hi4 = *(const plf_u32u_pre *)(row + x + 5);
-                double d[10];
-    #pragma unroll
-                for (int q = 0; q < 8; q++) d[q] = (double)(int)((lo8 >> (8 * q)) & 0xFF);
-                d[8] = (double)(int)(hi4 & 0xFF); d[9] = (double)(int)((hi4 >> 8) & 0xFF);
-    #pragma unroll
-                for (int j = 0; j < 4; j++) {
-                    double s_ = t.k[0] * d[j];
-    #pragma unroll
-                    for (int q = 1; q < 7; q++) s_ += t.k[q] * d[j + q];
-                    o[j] = s_;
-                }
-            } else if (g.w >= 16) {
-                // image border (the first / last groups of a row): the 10 reflected source bytes are picked out of one 16-byte window that lies inside the
-                // row.  (A per-tap reflected byte load here -- 28 loads, ~450 instructions -- ran on every wave of the tiles at the left / right image edge,
-                // because each of their waves holds a border group: a third of the kernel's time, 13.5 -> 9.1 ms per 4096 frames.)
-                const int base = min(max(x - 3, 0), g.w - 16);
-                const unsigned long long w0 = *(const plf_u64u *)(row + base), w1 = *(const plf_u64u *)(row + base + 8);
-                double d[10];
-    #pragma unroll
-                for (int q = 0; q < 10; q++) {
-                    const int pq = plf_reflect101(x - 3 + q, g.w) - base;
-                    d[q] = (double)(int)((((pq & 8) ? w1 : w0) >> (8 * (pq & 7))) & 0xFF);
-                }
-    #pragma unroll
-                for (int j = 0; j < 4; j++) {
-                    double s_ = t.k[0] * d[j];
-    #pragma unroll
-                    for (int q = 1; q < 7; q++) s_ += t.k[q] * d[j + q];
-                    o[j] = s_;
-                }
-            } else {   // images narrower than 16 pixels
-    #pragma unroll 1
-                for (int j = 0; j < 4; j++) {
-                    double s_ = t.k[0] * (double)row[plf_reflect101(x + j - 3, g.w)];
-    #pragma unroll 1
-                    for (int q = 1; q < 7; q++) s_ += t.k[q] * (double)row[plf_reflect101(x + j - 3 + q, g.w)];
-                    o[j] = s_;
-                }
-            }
-    #pragma unroll
-            for (int j = 0; j < 4; j++) s_tmp[r * PRE_SC + c + j] = o[j];
-        }
-    }
-    __syncthreads();
-    {
-        // column pass, one item = (column c, band of 8 blurred rows): at most 4 bands x 88 columns <= PRE_NT items, so one round
-        static_assert(((PRE_SR + 7) / 8) * PRE_SC <= PRE_NT, "one column-pass item per thread");
-        const int cb = tid / PRE_SC, cc = tid - cb * PRE_SC, rb0 = 8 * cb;
-        const bool item = cc < nc && rb0 < nr;
-        double v[14];
-        if (item) {
-            // (no row tests: the 6 spare rows of s_tmp keep rb0 + 13 inside the array; rows past nr + 6 hold stale values and only feed outputs nobody reads)
-#pragma unroll
-            for (int j = 0; j < 14; j++) v[j] = s_tmp[(rb0 + j) * PRE_SC + cc];
-        }
-        __syncthreads();
-        if (item) {
-#pragma unroll
-            for (int j = 0; j < 8; j++) {
-                double s_ = t.k[3] * v[j + 3] + 0.0;
-#pragma unroll
-                for (int q = 1; q <= 3; q++) s_ += t.k[3 + q] * (v[j + 3 + q] + v[j + 3 - q]);
-                s_blur[(rb0 + j) * PRE_SC + cc] = s_;
-            }
-        }
-    }
-    __syncthreads();
-    const int ncs = dx1 - dx0 + 1, nrs = dy1 - dy0 + 1;
-    {
-        // resize: a lane owns one column of the scaled tile (its source column and coefficients are loaded once), a wave walks rows -- the row's source rows
-        // and coefficients are wave-uniform (scalar loads); per pixel two LDS reads of two doubles and the nine products / sums of cv::resize.
-        // (One item per (row, column) with the four table loads per pixel was 60 instructions per pixel, a sixth of the kernel.)
-        const int wv = __builtin_amdgcn_readfirstlane(tid >> 6), lane = tid & 63;
-        auto px = [&](int rx, int sx, double ax, double ay, bool lin, int ry, int sy, float2 b) {
-            const double *S0 = s_blur + (min(max(sy, 0), g.h - 1) - r_lo) * PRE_SC + sx, *S1 = s_blur + (min(max(sy + 1, 0), g.h - 1) - r_lo) * PRE_SC + sx;
-            double r0, r1;
-            if (lin) {
-                r0 = S0[0] * ax + S0[1] * ay;
-                r1 = S1[0] * ax + S1[1] * ay;
-            } else {
-                r0 = S0[0] * 1.0;
-                r1 = S1[0] * 1.0;
-            }
-            s_sc[ry * (PRE_TW + 1) + rx] = r0 * (double)b.x + r1 * (double)b.y;
-        };
-        if (lane < ncs) {
-            const int dx = dx0 + lane, sx = xofs[dx] - c_lo;
-            const float2 a = xa[dx];
-            const double ax = (double)a.x, ay = (double)a.y;
-            const bool lin = dx < g.xmax;
-            for (int ry = wv; ry < nrs; ry += PRE_NT / 64) px(lane, sx, ax, ay, lin, ry, yofs[dy0 + ry], yb[dy0 + ry]);
-        }
-        if (wv == PRE_NT / 64 - 1 && ncs == PRE_TW + 1 && lane < nrs) {   // the 65th column (the gradient's right neighbour), one lane per row
-            const int dx = dx0 + PRE_TW;
-            const float2 a = xa[dx];
-            px(PRE_TW, xofs[dx] - c_lo, (double)a.x, (double)a.y, dx < g.xmax, lane, yofs[dy0 + lane], yb[dy0 + lane]);
-        }
-    }
-    __syncthreads();
-    // ll_angle for the tile.  Only the 2x2 gradient and its squared norm are computed for every pixel: norm = sqrt(q) <= rho (no level-line angle) is decided
-    // on q itself -- sqrt is correctly rounded and monotone, so sqrt(q) <= rho  <=>  q <= g.rho_q, the largest double whose root does not exceed rho (found
-    // on the host) -- and the pixels with a defined angle (about a quarter) are compacted (wave ballots) into LDS lists, so that the double-precision sqrt,
-    // fastAtan2 and sincos below run on full waves of defined pixels only.  modgrad is written for those pixels alone: nothing reads it elsewhere
-    // (region2rect weighs region points, k_lsd_maxgrad / k_lsd_seedkeys test the angle first).
-    __shared__ int s_ndef;
-    __shared__ float s_angt[PRE_TW * PRE_TH];                    // the tile's level-line angles (NOTDEF_F where there is none): the static singles below
-    __shared__ unsigned long long s_rowbits[PRE_TH];             // static singles of the tile, one word per tile row
-    double *s_q = s_tmp;                                         // the blurred tile is dead after the resize: q, offset inside the frame, (float)gx, (float)-gy
-    int *s_off = reinterpret_cast<int *>(s_tmp + PRE_TW * PRE_TH);
-    float *s_fx = reinterpret_cast<float *>(s_off + PRE_TW * PRE_TH), *s_fy = s_fx + PRE_TW * PRE_TH;
-    if (tid == 0) s_ndef = 0;
-    if (tid < PRE_TH) s_rowbits[tid] = 0ull;
-    __syncthreads();
-    const int tx = tid & 63;
-    float *angf = ang + (size_t)f * g.s_stride;
-#pragma unroll
-    for (int k = 0; k < (PRE_TH + PRE_NT / 64 - 1) / (PRE_NT / 64); k++) {
-        const int ty = __builtin_amdgcn_readfirstlane(tid >> 6) + (PRE_NT / 64) * k;
-        if (PRE_TH % (PRE_NT / 64) != 0 && ty >= PRE_TH) break;
-        const int x = dx0 + tx, y = dy0 + ty;
-        bool def = false;
-        double q = 0.0;
-        float fx = 0.f, fy = 0.f;
-        s_angt[ty * PRE_TW + tx] = NOTDEF_F;
-        if (x < g.sw && y < g.sh) {
-            if (x < g.sw - 1 && y < g.sh - 1) {
-                const double *im = s_sc + ty * (PRE_TW + 1) + tx;
-                const double DA = im[PRE_TW + 2] - im[0];
-                const double BC = im[1] - im[PRE_TW + 1];
-                const double gx = DA + BC, gy = DA - BC;
-                q = (gx * gx + gy * gy) / 4;
-                def = q > g.rho_q;
-                fx = (float)gx; fy = (float)-gy;
-            }
-            if (!def) angf[(unsigned)(y * g.sw + x)] = NOTDEF_F;
-        }
-        const unsigned long long m = __ballot(def);
-        int base = 0;
-        if (plf_lane() == 0 && m) base = atomicAdd(&s_ndef, __popcll(m));
-        base = __builtin_amdgcn_readfirstlane(base);
-        if (def) {
-            const int e = base + __popcll(m & ((1ull << plf_lane()) - 1ull));
-            s_q[e] = q; s_off[e] = ty * PRE_TW + tx; s_fx[e] = fx; s_fy[e] = fy;   // (the position inside the tile: the frame offset follows from it)
-        }
-    }
-    __syncthreads();
-    const int ndef = s_ndef;
-    // pixels with a level-line angle = the length of the frame's region-growing chain to within the few pixels refine releases (every one of them ends up USED):
-    // the cost by which k_lsd_balance deals the frames of a large batch to the waves of k_lsd_regions2
-    if (defcount && tid == 0 && ndef) atomicAdd(&defcount[f], ndef);
-    double *mgf = modgrad + (size_t)f * g.s_stride;
-    double2 *csf = cs + (size_t)f * g.s_stride;
-    float2 *cs0f = cs0 + (size_t)f * g.s_stride;
-    for (int i = tid; i < ndef; i += PRE_NT) {
-        const int loc = s_off[i];
-        const unsigned o = (unsigned)((dy0 + loc / PRE_TW) * g.sw + dx0 + loc % PRE_TW);   // (32-bit offsets from the frame's scalar base pointers)
-        mgf[o] = sqrt(s_q[i]);
-        const float deg = plf_fast_atan2_1div(s_fx[i], s_fy[i]);
-        angf[o] = deg;
-        s_angt[loc] = deg;
-        double cf, sf;
-        float c0, s0;
-        plf_lsd_cs(deg, &cf, &sf, &c0, &s0);   // cs: cos / sin of the FLOAT-rounded angle; cs0: float cos / sin of the un-rounded one (plf_math.h)
-        csf[o] = make_double2(cf, sf);
-        cs0f[o] = make_float2(c0, s0);
-    }
-    // Static singles (LsdGeom::sgl; see singles_run in the region-growing section): one BIT per pixel, set iff the pixel has an angle and none of its 8
-    // neighbours can pass the first alignment test of a region seeded there -- no neighbour's angle is within the tolerance + 0.001 degrees of the pixel's
-    // (circular difference in single precision: a superset of the reference's double test).  Pixels on the rim of this tile (neighbours outside: unknown, 11 % of
-    // the pixels) never get the bit.  Interior pixels read their neighbours from the tile of angles without bounds tests; the bits of a tile row are collected
-    // in one 64-bit LDS word and written as (up to) two dwords -- a byte per pixel, stored from the compacted lanes, cost the kernel 1.5 ms per 8192 natural
-    // frames in partial-line writes alone.
-#ifndef PLF_PRE_NOSGL
-    if (g.sgl) {
-        __syncthreads();
-        const float tol = (float)(g.prec * (180.0 / PI_D)) + 1.0e-3f;
-        for (int i = tid; i < ndef; i += PRE_NT) {
-            const int loc = s_off[i], ty = loc / PRE_TW, tx = loc % PRE_TW;
-            if (tx > 0 && tx < PRE_TW - 1 && ty > 0 && ty < PRE_TH - 1) {
-                const float a = s_angt[loc];
-                const float *nb = s_angt + loc;
-                float best = 1.0e9f;
-#pragma unroll
-                for (int k = 0; k < 8; k++) {
-                    const int off = (k < 3 ? k - 1 - PRE_TW : k == 3 ? -1 : k == 4 ? 1 : k - 6 + PRE_TW);
-                    const float b = nb[off];
-                    const float d = fabsf(a - b), e = 360.f - d;
-                    const float m = d < e ? d : e;
-                    best = (b >= 0.f && m < best) ? m : best;
-                }
-                if (!(best < tol)) atomicOr(&s_rowbits[ty], 1ull << tx);
-            }
-        }
-        __syncthreads();
-        if (tid < min(PRE_TH, g.sh - dy0)) {
-            // (row tid of the tile = 64 bits at pixel index (dy0 + tid) * sw + dx0 of the frame's bitmap)
-            const unsigned long long bits = s_rowbits[tid];
-            uint32_t *bmf = g.sgl + (size_t)f * (g.s_stride >> 5);
-            const unsigned idx = (unsigned)((dy0 + tid) * g.sw + dx0);
-            if ((g.sw & 31) == 0) {   // the words lie inside the row and belong to this tile alone: plain stores, zero words included (nothing clears the map)
-                bmf[idx >> 5] = (uint32_t)bits;
-                if (dx0 + 32 < g.sw) bmf[(idx >> 5) + 1] = (uint32_t)(bits >> 32);
-            } else if (bits) {        // any width: the host cleared the map, the row's bits are OR-ed into up to three words
-                const unsigned o = idx & 31u;
-                atomicOr(&bmf[idx >> 5], (uint32_t)(bits << o));
-                const unsigned long long hi = o ? bits >> (32 - o) : bits >> 32;
-                if ((uint32_t)hi) atomicOr(&bmf[(idx >> 5) + 1], (uint32_t)hi);
-                if (o && (uint32_t)(hi >> 32)) atomicOr(&bmf[(idx >> 5) + 2], (uint32_t)(hi >> 32));
-            }
-        }
-    }
+#ifndef PLF_LSD_SINGLES
+#define PLF_LSD_SINGLES 1   // static singles, see singles_run (0: every seed takes the pipeline -- the A/B switch, tools/ab.sh)
 #endif
-}
-
-// ------------------------------------------------------------------------------------------------
-// Published LSD seed order (seed_order = 1; every OpenCV release except 3.0-3.3): pixels sorted by gradient-magnitude
-// bin, strongest bin first, raster order inside a bin (a stable counting sort upstream).  The key packs
-// (1023 - bin) << 20 | pixel, so an ascending sort of the keys of a frame is exactly that order.
-// bin = int(modgrad * (1023 / max_grad)), max_grad over the pixels with a defined angle (oracle/lsd_oracle.c).
-// ------------------------------------------------------------------------------------------------
-__global__ void __launch_bounds__(256) k_lsd_maxgrad(const float *__restrict__ ang_all, const double *__restrict__ modgrad_all,
-                                                     double *__restrict__ maxgrad, LsdGeom g)
-{
-    __shared__ double red[256];
-    const int f = blockIdx.x, t = threadIdx.x, NP = g.sw * g.sh;
-    const float *ang = ang_all + (size_t)f * g.s_stride;
-    const double *mg = modgrad_all + (size_t)f * g.s_stride;
-    double m = -1.0;
-    for (int a = t; a < NP; a += 256)
-        if (ang[a] != NOTDEF_F && mg[a] > m) m = mg[a];
-    red[t] = m;
-    __syncthreads();
-    for (int o = 128; o > 0; o >>= 1) {
-        if (t < o && red[t + o] > red[t]) red[t] = red[t + o];
-        __syncthreads();
-    }
-    if (t == 0) maxgrad[f] = red[0];
-}
-
-__global__ void __launch_bounds__(256) k_lsd_seedkeys(const float *__restrict__ ang_all, const double *__restrict__ modgrad_all, const double *__restrict__ maxgrad,
-                                                      uint32_t *__restrict__ keys_all, LsdGeom g)
-{
-    const int a = blockIdx.x * 256 + threadIdx.x, f = blockIdx.y, NP = g.sw * g.sh;
-    if (a >= NP) return;
-    const double mx = maxgrad[f];
-    const double bin_coef = (mx > 0) ? 1023.0 / mx : 0.0;
-    const int x = a % g.sw, y = a / g.sw;
-    int b = 0;   // pixels without a level-line angle (the last row / column among them) never seed and have no modgrad: parked in the weakest bin
-    if (x < g.sw - 1 && y < g.sh - 1 && ang_all[(size_t)f * g.s_stride + a] != NOTDEF_F) {
-        b = (int)(modgrad_all[(size_t)f * g.s_stride + a] * bin_coef);
-        if (b > 1023) b = 1023;
-    }
-    keys_all[(size_t)f * g.s_stride + a] = ((uint32_t)(1023 - b) << 20) | (uint32_t)a;
-}
-
-// diagnostics (plf_line_chain_lengths): pixels of a frame that region growing left marked USED (sign bit of the angle word of a defined pixel) = the accept
-// steps of the frame's chain minus what refine / reduce_region_radius released again.  Counted after the fact so that the chain kernel carries no counter.
-__global__ void __launch_bounds__(256) k_lsd_count_used(const float *__restrict__ ang_all, int *__restrict__ out, LsdGeom g)
-{
-    __shared__ int red[256];
-    const int f = blockIdx.x, t = threadIdx.x, NP = g.sw * g.sh;
-    const uint32_t *ang = reinterpret_cast<const uint32_t *>(ang_all) + (size_t)f * g.s_stride;
-    int c = 0;
-    for (int a = t; a < NP; a += 256) { const uint32_t w = ang[a]; c += (w >= 0x80000000u && w != __float_as_uint(NOTDEF_F)) ? 1 : 0; }
-    red[t] = c;
-    __syncthreads();
-    for (int o = 128; o > 0; o >>= 1) { if (t < o) red[t] += red[t + o]; __syncthreads(); }
-    if (t == 0) out[f] = red[0];
-}
 
 // ------------------------------------------------------------------------------------------------
 // region growing (one wave per frame)
 // ------------------------------------------------------------------------------------------------
-// LDS pointers carry their address space in the type: a pointer that may be LDS or global would be lowered to FLAT
-// accesses, whose `s_waitcnt vmcnt(0)` also drains the outstanding neighbourhood loads.
-#define LDS_PTR(T) __attribute__((address_space(3))) T *
 // The USED flag of a pixel is the SIGN BIT of its entry in the frame's angle map (angles are in [0, 360), NOTDEF is
 // -1024): a pixel is a candidate iff its word is < 0x80000000.  The map lives in HBM/L2, not LDS, so that a
 // workgroup needs only a few KB of LDS and a CU hosts many frames at once -- the kernel is a chain of dependent
@@ -436,7 +50,7 @@ struct RegCtx {
 };
 
 #ifdef PLF_LSD_TIMING
-__device__ long long g_lsd_t[24];
+extern __device__ long long g_lsd_t[24];   // (defined beside plf_lsd_timing_dump)
 #define TIC(v) const long long v = clock64()
 #define TOC(slot, v) do { if (blockIdx.x == 0 && threadIdx.x == 0) g_lsd_t[slot] += clock64() - (v); } while (0)
 #ifdef PLF_LSD_TIMING_NOCNT
@@ -457,7 +71,6 @@ __device__ long long g_lsd_t[24];
 #define CNT(slot, k)
 #define TOCB(slot, v)
 #endif
-#define CBAR() asm volatile("" ::: "memory")   // single-wave kernel: LDS ops stay in program order; only the compiler must not reorder
 
 // (bitmap mode returns the same word the flag-in-sign-bit mode would hold: every caller is unchanged)
 __device__ __forceinline__ uint32_t ang_load(const RegCtx &C, int a)
@@ -496,37 +109,6 @@ __device__ __forceinline__ void rxy_put(RegCtx &C, int i, uint32_t v)
     if (i < C.rcap) C.rxy_l[i] = v;
     else C.rxy_g[i] = v;
 }
-
-__device__ __forceinline__ double shfl_d(double v, int src)
-{
-    int lo = __double2loint(v), hi = __double2hiint(v);
-    lo = __shfl(lo, src, 64); hi = __shfl(hi, src, 64);
-    return __hiloint2double(hi, lo);
-}
-// broadcast from a wave-uniform lane (v_readlane: no LDS crossbar round trip)
-__device__ __forceinline__ double readlane_d(double v, int src)
-{
-    const int lo = __builtin_amdgcn_readlane(__double2loint(v), src), hi = __builtin_amdgcn_readlane(__double2hiint(v), src);
-    return __hiloint2double(hi, lo);
-}
-
-
-// Wave-wide min / max by DPP (round 5): row_shr 1, 2, 4, 8 inside the rows of 16 lanes, row_bcast:15 and row_bcast:31 across them -- lane 63 ends up with the
-// value over all 64 lanes and is broadcast with v_readlane.  __shfl_xor butterflies compile to ds_bpermute_b32 (~60 cycles each, six dependent levels: the four
-// double extents of region2rect cost a lone band wave ~800 cycles per call, the bounding box of a seed's record ~600); min and max are order-free, so the result
-// is the same bit for bit.  A lane without a source in a step keeps its own value (old = the value itself: op(v, v) = v).
-template <int CTRL, int ROWMASK> __device__ __forceinline__ int dpp_mov_i(int v) { return __builtin_amdgcn_update_dpp(v, v, CTRL, ROWMASK, 0xf, false); }
-template <int CTRL, int ROWMASK> __device__ __forceinline__ double dpp_mov_d(double v)
-{
-    return __hiloint2double(dpp_mov_i<CTRL, ROWMASK>(__double2hiint(v)), dpp_mov_i<CTRL, ROWMASK>(__double2loint(v)));
-}
-#define PLF_DPP_REDUCE(v, OP, MOV)                                                                            \
-    v = OP(v, MOV<0x111, 0xf>(v)); v = OP(v, MOV<0x112, 0xf>(v)); v = OP(v, MOV<0x114, 0xf>(v)); v = OP(v, MOV<0x118, 0xf>(v)); \
-    v = OP(v, MOV<0x142, 0xa>(v)); v = OP(v, MOV<0x143, 0xc>(v));
-__device__ __forceinline__ int wave_min_i(int v) { PLF_DPP_REDUCE(v, min, dpp_mov_i) return __builtin_amdgcn_readlane(v, 63); }
-__device__ __forceinline__ int wave_max_i(int v) { PLF_DPP_REDUCE(v, max, dpp_mov_i) return __builtin_amdgcn_readlane(v, 63); }
-__device__ __forceinline__ double wave_min_d(double v) { PLF_DPP_REDUCE(v, fmin, dpp_mov_d) return readlane_d(v, 63); }
-__device__ __forceinline__ double wave_max_d(double v) { PLF_DPP_REDUCE(v, fmax, dpp_mov_d) return readlane_d(v, 63); }
 
 // (GrowTh, grow_thresholds: plf_math.h)
 
@@ -1087,9 +669,6 @@ __device__ __forceinline__ unsigned long long singles_run(unsigned long long mas
     const unsigned long long below = ns ? ((ns & (0ull - ns)) - 1ull) : ~0ull;
     return mask & smask & below;
 }
-#ifndef PLF_LSD_SINGLES
-#define PLF_LSD_SINGLES 1   // (0: every seed takes the pipeline -- the A/B switch, tools/ab.sh)
-#endif
 
 // LDS of one wave of the large-batch region kernel: the first 1280 words of the region list (rcap <= 1279 + the mailbox word) and 1 KB for the parked seed chunk
 // (PLF_LSD_WAVE_LIST / PLF_LSD_WAVE_LDS: lsd_geom.h, shared with the host)
@@ -2816,6 +2395,7 @@ __global__ void __launch_bounds__(64) k_lsd_spec_assemble(LsdRect *__restrict__ 
 }
 
 #ifdef PLF_LSD_TIMING
+__device__ long long g_lsd_t[24];
 extern "C" void plf_lsd_timing_dump()
 {
     long long t[24];
@@ -2828,866 +2408,3 @@ extern "C" void plf_lsd_timing_dump()
     printf("[lsd timing, frame 0 of the large-batch kernel] static singles marked without the pipeline %lld\n", t[23]);
 }
 #endif
-
-// ------------------------------------------------------------------------------------------------
-// NFA validation (one wave per rectangle)
-// ------------------------------------------------------------------------------------------------
-// (log_gamma_d, log_gamma_int, nfa_d, nfa_head / nfa_tail: plf_math.h)
-
-// NFA values of small rectangles, tabulated: rect_improve asks for nfa(n, k, p) tens of millions of times per large batch (9,600 values per VGA frame), nearly
-// always with a pixel count n of a few dozen to a few hundred and always with p = 1/8 * 2^-j, j = 0..10 (region2rect's p, halved by the two precision stages).  The
-// table holds nfa_d's result for every n < NFA_TAB_N, k <= n and those eleven p, once per scaled-image size (LOG_NT enters the loop's exit test, so the values
-// depend on it).  It is filled on the HOST with the same nfa_d compiled against the host's libm -- the oracle's -- and uploaded (line_host.hip, plf_nfa_table_host):
-// the device library's exp / log / pow differ from glibc's in the last bit (tests/test_gpu_math.py), the host's do not.  Likewise the log_gamma table.
-
-// true (and v) if (n, k, p) is tabulated
-__device__ __forceinline__ bool nfa_lookup(const double *__restrict__ tab, int n, int k, double p, double &v)
-{
-    const long long bits = __double_as_longlong(p);
-    const int j = 1023 - 3 - (int)(bits >> 52);   // p = 2^-(3 + j) exactly <=> mantissa 0, sign 0
-    if ((bits & 0xFFFFFFFFFFFFFll) != 0 || j < 0 || j >= NFA_TAB_P || n < 0 || n >= NFA_TAB_N || k < 0 || k > n) return false;
-    v = tab[(size_t)j * NFA_TAB_ROW + n * (n + 1) / 2 + k];
-    return true;
-}
-
-struct EdgePt { int x, y, taken; };
-
-// ------------------------------------------------------------------------------------------------
-// NFA validation = rect_improve (imgproc/lsd.cpp), restructured for the GPU without changing a decision:
-//   * the pixel COUNTING of a rectangle (rect_nfa's scan-line walk) is wave-parallel: upstream's left/right x
-//     walk adds integer-valued steps (its slopes are integer divisions), so the span of row y has a closed form
-//     and every lane takes a row; the counts for up to 6 angle precisions of the same geometry come from one pass;
-//   * the NFA MATH (log-gamma, binomial tail; fp64 transcendentals) is lane-parallel: one lane per rectangle;
-//   * rect_improve's 5 search stages stay sequential (stage s+1 starts from the best rectangle of stage s); inside
-//     a stage the 5 candidate rectangles do not depend on the comparisons, so they are counted together and the
-//     "keep it if better" chain is replayed in order by the lane that owns the rectangle.
-// Work lists are global (all frames of the batch) and compacted with atomics; order is irrelevant because every
-// result is written to its rectangle's own slot.
-// ------------------------------------------------------------------------------------------------
-#define NFA_U 4   // gathers in flight per lane in rect_count's column loop
-// pixel count of one rectangle by a group of 16 lanes (4 rectangles per wave: most candidate rectangles span
-// only a few rows, so a full wave per rectangle would idle)
-// NP = 6: the counts for rec.prec and the five halved precisions of the same geometry (stages 0 and 4); NP = 1: rec.prec only (the candidate
-// rectangles of stages 1..3 -- most of the pixel visits; the five unused comparisons per pixel were 37 % of the loop body)
-__device__ __forceinline__ int div_small(int a, int b);
-
-// scan-line description of a rectangle: everything rect_count's row walk needs (all integers)
-struct RectScan { int mnx, y_lo, y_hi, lfy, rty, fl, sl, fr, sr; };
-
-__device__ __forceinline__ void rect_scan_setup(const LsdRect &rec, int H, RectScan &S)
-{
-    const double half_width = rec.width / 2.0;
-    const double dyhw = rec.dy * half_width, dxhw = rec.dx * half_width;
-    // the four corners, kept in registers (no indexed array: that would live in scratch memory)
-    int px0 = (int)(rec.x1 - dyhw), py0 = (int)(rec.y1 + dxhw);
-    int px1 = (int)(rec.x2 - dyhw), py1 = (int)(rec.y2 + dxhw);
-    int px2 = (int)(rec.x2 + dyhw), py2 = (int)(rec.y2 - dxhw);
-    int px3 = (int)(rec.x1 + dyhw), py3 = (int)(rec.y1 - dxhw);
-    // std::sort with AsmallerB_XoverY is a total order on (x, y): a sorting network yields the same sequence
-#define PLF_CSWAP(xa, ya, xb, yb) { const bool sw = (xa > xb) || (xa == xb && ya > yb); const int tx = sw ? xb : xa, ty = sw ? yb : ya; \
-                                    xb = sw ? xa : xb; yb = sw ? ya : yb; xa = tx; ya = ty; }
-    PLF_CSWAP(px0, py0, px1, py1) PLF_CSWAP(px2, py2, px3, py3) PLF_CSWAP(px0, py0, px2, py2) PLF_CSWAP(px1, py1, px3, py3) PLF_CSWAP(px1, py1, px2, py2)
-#undef PLF_CSWAP
-#define PLF_SELX(i) ((i) == 0 ? px0 : (i) == 1 ? px1 : (i) == 2 ? px2 : px3)
-#define PLF_SELY(i) ((i) == 0 ? py0 : (i) == 1 ? py1 : (i) == 2 ? py2 : py3)
-    int imin = 0, imax = 0;   // first minimum / first maximum of y in sorted order (strict comparisons)
-    {
-        int ymin = py0, ymax = py0;
-        if (ymin > py1) { imin = 1; ymin = py1; }
-        if (ymin > py2) { imin = 2; ymin = py2; }
-        if (ymin > py3) { imin = 3; ymin = py3; }
-        if (ymax < py1) { imax = 1; ymax = py1; }
-        if (ymax < py2) { imax = 2; ymax = py2; }
-        if (ymax < py3) { imax = 3; ymax = py3; }
-    }
-    // only `min` is marked taken before the next picks (upstream); the list is sorted by x, so the leftmost of the
-    // rest is the lowest free index, the rightmost is the later of the remaining two unless their x are equal
-    const int il = (imin == 0) ? 1 : 0;
-    int ra = -1, rb = -1;
-    for (int i = 0; i < 4; ++i) if (i != imin && i != il) { if (ra < 0) ra = i; else rb = i; }
-    const int ir = (PLF_SELX(ra) < PLF_SELX(rb)) ? rb : ra;
-    const int it = (ir == ra) ? rb : ra;
-    EdgePt mn, mx, lf, rt, tl;
-    mn.x = PLF_SELX(imin); mn.y = PLF_SELY(imin); mx.x = PLF_SELX(imax); mx.y = PLF_SELY(imax);
-    lf.x = PLF_SELX(il); lf.y = PLF_SELY(il); rt.x = PLF_SELX(ir); rt.y = PLF_SELY(ir); tl.x = PLF_SELX(it); tl.y = PLF_SELY(it);
-#undef PLF_SELX
-#undef PLF_SELY
-    // upstream: integer divisions, and `tailp->p.x` where p.y was meant
-    S.fl = (mn.y != lf.y) ? div_small(mn.x - lf.x, mn.y - lf.y) : 0;
-    S.sl = (lf.y != tl.x) ? div_small(lf.x - tl.x, lf.y - tl.x) : 0;
-    S.fr = (mn.y != rt.y) ? div_small(mn.x - rt.x, mn.y - rt.y) : 0;
-    S.sr = (rt.y != tl.x) ? div_small(rt.x - tl.x, rt.y - tl.x) : 0;
-    // rows outside the image are skipped BEFORE the step update (upstream `continue`): the walk starts at y_lo.
-    S.mnx = mn.x; S.lfy = lf.y; S.rty = rt.y;
-    S.y_lo = max(mn.y, 0); S.y_hi = min(mx.y, H - 1);
-}
-
-// span of row y (y_lo <= y <= y_hi).  After visiting row y' the walk adds (y' >= lf.y ? slstep : flstep); all terms are integers, so the span of
-// row y is exact in closed form.
-__device__ __forceinline__ void rect_span(const RectScan &S, int y, int W, int &xl, int &xr)
-{
-    // (32-bit: slopes and row counts are below 2^15 for any image the handle accepts -- line_configure checks -- so the products stay below 2^30 and the 24-bit
-    // multiplier's result is the full product; upstream's own arithmetic is int)
-    const int al = max(0, min(y, S.lfy) - S.y_lo), bl = (y - S.y_lo) - al;
-    const int ar = max(0, min(y, S.rty) - S.y_lo), br = (y - S.y_lo) - ar;
-    const int left = S.mnx + __mul24(S.fl, al) + __mul24(S.sl, bl), right = S.mnx + __mul24(S.fr, ar) + __mul24(S.sr, br);
-    xl = max(left, 0); xr = min(right, W - 1);
-}
-
-// truncating integer division (C semantics) of operands below 2^23 in magnitude, b != 0: the float quotient estimate is within 1 of the truth, fixed up exactly
-// with the remainder (the compiler's general 32-bit division is ~35 instructions; rect_scan_setup has four)
-__device__ __forceinline__ int div_small(int a, int b)
-{
-    const unsigned ua = (unsigned)abs(a), ub = (unsigned)abs(b);
-    unsigned q = (unsigned)((float)ua * __builtin_amdgcn_rcpf((float)ub));
-    int r = (int)ua - (int)(q * ub);
-    if (r < 0) { q--; r += (int)ub; }
-    if (r >= (int)ub) { q++; }
-    return ((a ^ b) < 0) ? -(int)q : (int)q;
-}
-
-// sum over the 16 lanes of a DPP row (= one rectangle's group), result in every lane: four rotate-and-add steps, one instruction each (ds_bpermute + address
-// arithmetic before)
-__device__ __forceinline__ int row16_sum(int v)
-{
-    v += __builtin_amdgcn_update_dpp(0, v, 0x128, 0xF, 0xF, false);   // row_ror:8
-    v += __builtin_amdgcn_update_dpp(0, v, 0x124, 0xF, 0xF, false);   // row_ror:4
-    v += __builtin_amdgcn_update_dpp(0, v, 0x122, 0xF, 0xF, false);   // row_ror:2
-    v += __builtin_amdgcn_update_dpp(0, v, 0x121, 0xF, 0xF, false);   // row_ror:1
-    return v;
-}
-
-// |level-line angle - theta| folded as upstream's isAligned does
-__device__ __forceinline__ double rect_ntheta(float dw, double theta)
-{
-    const double a = (double)fabsf(dw) * DEG2RAD_D;   // the sign bit is k_lsd_regions' USED flag
-    double n_theta = theta - a;
-    if (n_theta < 0) n_theta = -n_theta;
-    if (n_theta > M_3_2_PI_D) {
-        n_theta -= M_2__PI_D;
-        if (n_theta < 0) n_theta = -n_theta;
-    }
-    return n_theta;
-}
-
-template <int NP, int G = 16>
-__device__ void rect_count(const float *__restrict__ ang, int W, int H, const LsdRect &rec, NfaCounts &out)
-{
-    const int lane = plf_lane() & (G - 1);   // G lanes per rectangle: 16 (four rectangles per wave, large batches) or the whole wave (k_nfa_fused)
-    RectScan S;
-    rect_scan_setup(rec, H, S);
-    const int y_lo = S.y_lo, y_hi = S.y_hi;
-    double precs[NP];
-    precs[0] = rec.prec;
-    if (NP > 1) {
-        double pp = rec.p;
-#pragma unroll
-        for (int k = 1; k < NP; k++) { pp /= 2; precs[k] = pp * PI_D; }
-    }
-    int total = 0, alg[NP];
-#pragma unroll
-    for (int k = 0; k < NP; k++) alg[k] = 0;
-    // 16 lanes = ry_n rows x rx_n interleaved columns: rectangles along the x axis have few, long rows
-    int ry_n = G;
-    while (ry_n > 1 && ry_n > y_hi - y_lo + 1) ry_n >>= 1;
-    const int rx_n = G / ry_n, ry = lane & (ry_n - 1), rx = lane / ry_n;
-    for (int y = y_lo + ry; y <= y_hi; y += ry_n) {
-        int xl, xr;
-        rect_span(S, y, W, xl, xr);
-        const float *row = ang + (size_t)y * W;
-        // the angle words of a row sit in HBM (thousands of frames in flight: no cache holds them) and the kernel is bound by that latency: NFA_U gathers
-        // in flight per lane instead of 1, and 16 waves per SIMD-quad slot (line_host.hip) -- 15.9 -> 7.9 ms per 4096 frames for the five stages
-        for (int x = xl + rx; x <= xr; x += NFA_U * rx_n) {
-            float dwv[NFA_U];
-#pragma unroll
-            for (int q = 0; q < NFA_U; q++) dwv[q] = (x + q * rx_n <= xr) ? row[x + q * rx_n] : NOTDEF_F;
-#pragma unroll
-            for (int q = 0; q < NFA_U; q++) {
-                if (x + q * rx_n > xr) continue;
-                ++total;
-                const float dw = dwv[q];
-                if (dw == NOTDEF_F) continue;
-                const double n_theta = rect_ntheta(dw, rec.theta);
-#pragma unroll
-                for (int k = 0; k < NP; k++) if (n_theta <= precs[k]) ++alg[k];
-            }
-        }
-
-    }
-    if (G == 16) {
-        total = row16_sum(total);
-#pragma unroll
-        for (int k = 0; k < NP; k++) alg[k] = row16_sum(alg[k]);
-    } else {
-#pragma unroll
-        for (int o = G / 2; o > 0; o >>= 1) {  // butterfly inside the group
-            total += __shfl_xor(total, o, 64);
-#pragma unroll
-            for (int k = 0; k < NP; k++) alg[k] += __shfl_xor(alg[k], o, 64);
-        }
-    }
-    out.total = total;
-#pragma unroll
-    for (int k = 0; k < 6; k++) out.alg[k] = k < NP ? alg[k < NP ? k : 0] : 0;
-}
-
-// The five candidate rectangles of one width stage (1..3) of rect_improve, counted in ONE pass by a group of 16 lanes.  They share theta and the precision and
-// cover nearly the same pixels, so (i) lane c < 5 does candidate c's scan-line set-up (corners, ordering, the four integer slopes -- two thirds of the instructions
-// of a rect_count call on the small rectangles that make up most of a frame) while the others idle instead of the whole group doing it five times, (ii) every
-// pixel of the union of the spans is fetched and its angle folded once, then tested against each candidate's span.  Per candidate the counted set is exactly
-// rect_count<1>'s: the pixels of rows y_lo..y_hi inside [xl, xr] of rect_span.  par: 5 x 12 ints of LDS owned by the group.
-__device__ void rect_count5(const float *__restrict__ ang, int W, int H, const LsdRect &cand, bool valid, double theta, double prec, int *par, int (&total)[5],
-                            int (&alg)[5])
-{
-    const int lane = plf_lane() & 15;
-    RectScan S;
-    rect_scan_setup(cand, H, S);
-    const bool mine = lane < 5 && valid;
-    if (lane < 5) {
-        int *P = par + lane * 12;
-        P[0] = S.mnx; P[1] = mine ? S.y_lo : 1; P[2] = mine ? S.y_hi : 0; P[3] = S.lfy; P[4] = S.rty; P[5] = S.fl; P[6] = S.sl; P[7] = S.fr; P[8] = S.sr;
-    }
-    int y_lo = mine ? S.y_lo : (1 << 30), y_hi = mine ? S.y_hi : -(1 << 30);
-#pragma unroll
-    for (int o = 8; o > 0; o >>= 1) { y_lo = min(y_lo, __shfl_xor(y_lo, o, 64)); y_hi = max(y_hi, __shfl_xor(y_hi, o, 64)); }
-    CBAR();
-#pragma unroll
-    for (int c = 0; c < 5; c++) total[c] = alg[c] = 0;
-    int ry_n = 16;
-    while (ry_n > 1 && ry_n > y_hi - y_lo + 1) ry_n >>= 1;
-    const int rx_n = 16 / ry_n, ry = lane & (ry_n - 1), rx = lane / ry_n;
-    for (int y = y_lo + ry; y <= y_hi; y += ry_n) {
-        int xl[5], xr[5], uxl = 1 << 30, uxr = -1;   // (a row none of the candidates has pixels in: an empty loop below, without overflowing uxl + rx)
-#pragma unroll
-        for (int c = 0; c < 5; c++) {
-            const int *P = par + c * 12;
-            RectScan Sc;
-            Sc.mnx = P[0]; Sc.y_lo = P[1]; Sc.y_hi = P[2]; Sc.lfy = P[3]; Sc.rty = P[4]; Sc.fl = P[5]; Sc.sl = P[6]; Sc.fr = P[7]; Sc.sr = P[8];
-            rect_span(Sc, y, W, xl[c], xr[c]);
-            if (y < Sc.y_lo || y > Sc.y_hi) { xl[c] = 1; xr[c] = 0; }
-            if (xl[c] <= xr[c]) { uxl = min(uxl, xl[c]); uxr = max(uxr, xr[c]); }
-        }
-        const float *row = ang + (size_t)y * W;
-        for (int x = uxl + rx; x <= uxr; x += NFA_U * rx_n) {
-            float dwv[NFA_U];
-#pragma unroll
-            for (int q = 0; q < NFA_U; q++) dwv[q] = (x + q * rx_n <= uxr) ? row[x + q * rx_n] : NOTDEF_F;
-#pragma unroll
-            for (int q = 0; q < NFA_U; q++) {
-                const int xq = x + q * rx_n;
-                if (xq > uxr) continue;
-                const float dw = dwv[q];
-                const bool al = dw != NOTDEF_F && rect_ntheta(dw, theta) <= prec;
-#pragma unroll
-                for (int c = 0; c < 5; c++) {
-                    const bool in = xq >= xl[c] && xq <= xr[c];
-                    total[c] += in ? 1 : 0;
-                    alg[c] += (in && al) ? 1 : 0;
-                }
-            }
-        }
-    }
-    CBAR();
-#pragma unroll
-    for (int c = 0; c < 5; c++) { total[c] = row16_sum(total[c]); alg[c] = row16_sum(alg[c]); }
-}
-
-__device__ __forceinline__ void emit_segment(LsdRect rec, float4 *seg)
-{
-    rec.x1 += 0.5; rec.y1 += 0.5; rec.x2 += 0.5; rec.y2 += 0.5;
-    rec.x1 /= 0.8; rec.y1 /= 0.8; rec.x2 /= 0.8; rec.y2 /= 0.8;
-    *seg = make_float4((float)rec.x1, (float)rec.y1, (float)rec.x2, (float)rec.y2);
-}
-
-// one lane per rectangle of every frame: queue it for the first count
-__global__ void __launch_bounds__(256) k_nfa_init(const LsdRect *__restrict__ rects_all, const int *__restrict__ nrect,
-                                                  uint8_t *__restrict__ keep_all, NfaEntry *__restrict__ entries, NfaState *__restrict__ states,
-                                                  int *__restrict__ counters, int *__restrict__ status, LsdGeom g)
-{
-    const int f = blockIdx.y, n = nrect[f];
-    for (int i = blockIdx.x * 256 + threadIdx.x; i < n; i += gridDim.x * 256) {
-        keep_all[(size_t)f * g.rect_cap + i] = 0;
-        const int q = atomicAdd(&counters[0], 1);
-        if (q >= g.nfa_pool) { atomicOr(status, 1); continue; }   // the batch holds more rectangles than the pooled stage buffers (k_nfa_clamp trims the count)
-        NfaEntry e;
-        e.r = rects_all[(size_t)f * g.rect_cap + i]; e.frame = f; e.nprec = 6; e.pad0 = e.pad1 = 0;
-        entries[q] = e;
-        NfaState st;
-        st.rec = e.r; st.log_nfa = -1; st.frame = f; st.rect = i;
-        states[q] = st;
-    }
-}
-
-__global__ void k_nfa_clamp(int *__restrict__ counters, int *__restrict__ status, LsdGeom g)
-{
-    if (counters[0] > g.nfa_pool) { counters[0] = g.nfa_pool; atomicOr(status, 1); }
-}
-
-// persistent waves: entry e -> counts[e];  n = counters[cidx] * mult.  k_nfa_count: stages 0 and 4 (entries carry nprec 6 or 0), k_nfa_count1:
-// stages 1..3 (nprec 1 or 0)
-template <int NP>
-__device__ __forceinline__ void nfa_count_body(const float *__restrict__ ang_all, const NfaEntry *__restrict__ entries, const int *__restrict__ counters,
-                                               int cidx, int mult, NfaCounts *__restrict__ counts, const LsdGeom &g)
-{
-    const int n = counters[cidx] * mult;
-    const int grp = threadIdx.x >> 4;
-    for (int e0 = blockIdx.x * 4; e0 < n; e0 += gridDim.x * 4) {
-        const int e = e0 + grp;
-        if (e >= n) continue;     // (no wave-wide barrier below: groups are independent)
-        const NfaEntry en = entries[e];
-        if (en.nprec == 0) continue;
-        NfaCounts c;
-        if (en.nprec == NP) rect_count<NP>(ang_all + (size_t)en.frame * g.s_stride, g.sw, g.sh, en.r, c);
-        else if (NP == 1) rect_count<6>(ang_all + (size_t)en.frame * g.s_stride, g.sw, g.sh, en.r, c);   // (not produced by k_nfa_math; kept for safety)
-        else rect_count<1>(ang_all + (size_t)en.frame * g.s_stride, g.sw, g.sh, en.r, c);
-        if ((threadIdx.x & 15) == 0) counts[e] = c;
-    }
-}
-__global__ void __launch_bounds__(64) k_nfa_count(const float *__restrict__ ang_all, const NfaEntry *__restrict__ entries,
-                                                  const int *__restrict__ counters, int cidx, int mult, NfaCounts *__restrict__ counts, LsdGeom g)
-{
-    nfa_count_body<6>(ang_all, entries, counters, cidx, mult, counts, g);
-}
-__global__ void __launch_bounds__(64) k_nfa_count1(const float *__restrict__ ang_all, const NfaEntry *__restrict__ entries,
-                                                   const int *__restrict__ counters, int cidx, int mult, NfaCounts *__restrict__ counts, LsdGeom g)
-{
-    nfa_count_body<1>(ang_all, entries, counters, cidx, mult, counts, g);
-}
-
-// the same with a whole wave per rectangle: what is left for the staged kernels after k_nfa_small are the rectangles of 512 pixels and more (16 lanes would walk
-// 32+ pixels each, one dependent gather after the other)
-template <int NP>
-__device__ __forceinline__ void nfa_count_wave_body(const float *__restrict__ ang_all, const NfaEntry *__restrict__ entries, const int *__restrict__ counters,
-                                                    int cidx, int mult, NfaCounts *__restrict__ counts, const LsdGeom &g)
-{
-    const int n = counters[cidx] * mult;
-    for (int e = blockIdx.x; e < n; e += gridDim.x) {
-        const NfaEntry en = entries[e];
-        if (en.nprec == 0) continue;
-        NfaCounts c;
-        if (en.nprec == NP) rect_count<NP, 64>(ang_all + (size_t)en.frame * g.s_stride, g.sw, g.sh, en.r, c);
-        else if (NP == 1) rect_count<6, 64>(ang_all + (size_t)en.frame * g.s_stride, g.sw, g.sh, en.r, c);
-        else rect_count<1, 64>(ang_all + (size_t)en.frame * g.s_stride, g.sw, g.sh, en.r, c);
-        if (threadIdx.x == 0) counts[e] = c;
-    }
-}
-__global__ void __launch_bounds__(64) k_nfa_count_w(const float *__restrict__ ang_all, const NfaEntry *__restrict__ entries,
-                                                    const int *__restrict__ counters, int cidx, int mult, NfaCounts *__restrict__ counts, LsdGeom g)
-{
-    PLF_LINE_SETPRIO();
-    nfa_count_wave_body<6>(ang_all, entries, counters, cidx, mult, counts, g);
-}
-__global__ void __launch_bounds__(64) k_nfa_count1_w(const float *__restrict__ ang_all, const NfaEntry *__restrict__ entries,
-                                                     const int *__restrict__ counters, int cidx, int mult, NfaCounts *__restrict__ counts, LsdGeom g)
-{
-    PLF_LINE_SETPRIO();
-    nfa_count_wave_body<1>(ang_all, entries, counters, cidx, mult, counts, g);
-}
-
-__device__ __forceinline__ void nfa_finish(const NfaState &st, float4 *__restrict__ seg_all, uint8_t *__restrict__ keep_all, const LsdGeom &g)
-{
-    keep_all[(size_t)st.frame * g.rect_cap + st.rect] = 1;
-    emit_segment(st.rec, &seg_all[(size_t)st.frame * g.rect_cap + st.rect]);
-}
-
-// NFA value of every counted candidate, one lane per (rectangle, candidate): the fp64-transcendental part is
-// spread over as many lanes as there are candidates so that no lane evaluates more than one binomial tail.
-// stage 0 / 4: item = rectangle * 6 + k (k-th precision of the same geometry); stages 1..3: item = entry index.
-// The length of the binomial-tail loop varies from 1 to thousands of iterations between items (it runs from k + 1
-// to about n / 2), so a block first orders its chunk of items by the predicted loop length (LDS counting sort on
-// half-octave buckets): the 64 lanes of a wave then run loops of similar length instead of idling behind the
-// longest one.  The order only decides which lane evaluates which item.
-#define EV_T 256
-#define EV_PER 8
-#define EV_CHUNK (EV_T * EV_PER)
-__device__ __forceinline__ bool nfa_item(int stage, bool multi, int it, const NfaEntry *__restrict__ entries, const NfaCounts *__restrict__ counts,
-                                         int &n, int &k, double &p)
-{
-    if (multi) {
-        const int e = it / 6, q = it - e * 6;
-        if (entries[e].nprec != 6 || (stage == 4 && q == 0)) return false;
-        double pp = entries[e].r.p;
-        for (int j = 0; j < q; j++) pp /= 2;
-        n = counts[e].total; k = counts[e].alg[q]; p = pp;   // (indexed straight from memory: no by-value struct in scratch)
-        return true;
-    }
-    if (entries[it].nprec == 0) return false;
-    n = counts[it].total; k = counts[it].alg[0]; p = entries[it].r.p;
-    return true;
-}
-
-__global__ void __launch_bounds__(EV_T) k_nfa_eval(int stage, const double *__restrict__ lgam, const double *__restrict__ tab, const NfaCounts *__restrict__ counts,
-                                                   const NfaEntry *__restrict__ entries, const int *__restrict__ counters,
-                                                   double *__restrict__ vals, LsdGeom g)
-{
-    PLF_LINE_SETPRIO();
-    __shared__ uint16_t order[EV_CHUNK];
-    __shared__ int hist[32];
-    const bool multi = (stage == 0 || stage == 4);
-    const int total = counters[stage] * (multi ? 6 : 5), t = threadIdx.x;
-    // items per thread: EV_PER when the grid is full; fewer when there is little work (few frames in flight), so that it spreads over more blocks
-    // and no thread evaluates several binomial tails back to back
-    const int per = min(EV_PER, max(1, (total + (int)gridDim.x * EV_T - 1) / ((int)gridDim.x * EV_T))), chunk = per * EV_T;
-    for (int c0 = blockIdx.x * chunk; c0 < total; c0 += gridDim.x * chunk) {
-        if (t < 32) hist[t] = 0;
-        __syncthreads();
-        int bkt[EV_PER], rnk[EV_PER];
-#pragma unroll
-        for (int q = 0; q < EV_PER; q++) {
-            const int it = c0 + q * EV_T + t;
-            bkt[q] = -1; rnk[q] = 0;
-            if (q < per && it < total) {
-                int n = 0, k = 0;
-                double p;
-                int b = 0;
-                double tv;
-                if (nfa_item(stage, multi, it, entries, counts, n, k, p) && n != 0 && k != 0 && n != k && !(tab && nfa_lookup(tab, n, k, p, tv))) {
-                    const int L = max(1, (n + 1) / 2 - k);
-                    const int lz = 31 - __clz(L);
-                    b = min(31, 1 + 2 * lz + (lz > 0 ? ((L >> (lz - 1)) & 1) : 0));
-                }
-                bkt[q] = b;
-                rnk[q] = atomicAdd(&hist[b], 1);
-            }
-        }
-        __syncthreads();
-        if (t == 0) {   // longest loops first
-            int run = 0;
-            for (int b = 31; b >= 0; b--) { const int v = hist[b]; hist[b] = run; run += v; }
-        }
-        __syncthreads();
-#pragma unroll
-        for (int q = 0; q < EV_PER; q++)
-            if (bkt[q] >= 0) order[hist[bkt[q]] + rnk[q]] = (uint16_t)(q * EV_T + t);
-        __syncthreads();
-        const int cnt = min(chunk, total - c0);
-        for (int i = t; i < cnt; i += EV_T) {
-            const int it = c0 + order[i];
-            int n = 0, k = 0;
-            double p = 0.0, v = -1.0e300;
-            if (nfa_item(stage, multi, it, entries, counts, n, k, p) && !(tab && nfa_lookup(tab, n, k, p, v))) v = nfa_d(lgam, g.log_nt, n, k, p);
-            vals[it] = v;
-        }
-        __syncthreads();
-    }
-}
-
-// stage: 0 = first evaluation + "finer precision" loop, 1..3 = the three width loops, 4 = final precision loop.
-// Reads the NFA values of the previous eval pass, replays the "keep if better" chain in the reference order,
-// finishes meaningful rectangles and queues the next stage's candidate rectangles for the others.
-__global__ void __launch_bounds__(64) k_nfa_math(int stage, const double *__restrict__ vals, const NfaEntry *__restrict__ entries,
-                                                 const NfaState *__restrict__ st_in, NfaState *__restrict__ st_out,
-                                                 NfaEntry *__restrict__ ent_out, int *__restrict__ counters, float4 *__restrict__ seg_all,
-                                                 uint8_t *__restrict__ keep_all, LsdGeom g)
-{
-    PLF_LINE_SETPRIO();
-    const int n = counters[stage];
-    const double LOG_EPS = 0.0, delta = 0.5, delta_2 = delta / 2.0;
-    for (int i = blockIdx.x * 64 + threadIdx.x; i < n; i += gridDim.x * 64) {
-        NfaState st = st_in[i];
-        if (stage == 0 || stage == 4) {
-            const NfaEntry en = entries[i];
-            if (stage == 0) {
-                st.log_nfa = vals[6 * i];
-                if (st.log_nfa > LOG_EPS) { nfa_finish(st, seg_all, keep_all, g); continue; }
-            }
-            if (en.nprec == 6) {
-                LsdRect r = st.rec;
-                for (int k = 1; k <= 5; ++k) {
-                    r.p /= 2;
-                    r.prec = r.p * PI_D;
-                    const double v = vals[6 * i + k];
-                    if (v > st.log_nfa) { st.log_nfa = v; st.rec = r; }
-                }
-            }
-            if (st.log_nfa > LOG_EPS) { nfa_finish(st, seg_all, keep_all, g); continue; }
-            if (stage == 4) continue;  // not meaningful
-        } else {
-            for (int k = 0; k < 5; ++k) {
-                const NfaEntry en = entries[5 * i + k];
-                if (en.nprec == 0) continue;
-                const double v = vals[5 * i + k];
-                if (v > st.log_nfa) { st.rec = en.r; st.log_nfa = v; }
-            }
-            if (st.log_nfa > LOG_EPS) { nfa_finish(st, seg_all, keep_all, g); continue; }
-        }
-        // queue the next stage
-        const int q = atomicAdd(&counters[stage + 1], 1);
-        st_out[q] = st;
-        LsdRect r = st.rec;
-        if (stage <= 2) {
-            // stage 0 -> "reduce width", 1 -> "reduce one side", 2 -> "reduce the other side"
-            for (int k = 0; k < 5; ++k) {
-                NfaEntry e;
-                e.frame = st.frame; e.pad0 = e.pad1 = 0; e.nprec = 0;
-                if ((r.width - delta) >= 0.5) {
-                    if (stage == 1) { r.x1 += -r.dy * delta_2; r.y1 += r.dx * delta_2; r.x2 += -r.dy * delta_2; r.y2 += r.dx * delta_2; }
-                    if (stage == 2) { r.x1 -= -r.dy * delta_2; r.y1 -= r.dx * delta_2; r.x2 -= -r.dy * delta_2; r.y2 -= r.dx * delta_2; }
-                    r.width -= delta;
-                    e.nprec = 1;
-                }
-                e.r = r;
-                ent_out[5 * q + k] = e;
-            }
-        } else {  // stage 3 -> final "finer precision" loop (upstream keeps the width test here too)
-            NfaEntry e;
-            e.r = r; e.frame = st.frame; e.pad0 = e.pad1 = 0;
-            e.nprec = ((r.width - delta) >= 0.5) ? 6 : 0;
-            ent_out[q] = e;
-        }
-    }
-}
-
-// ------------------------------------------------------------------------------------------------
-// rect_improve of one SMALL rectangle by a group of 16 lanes, all five stages in one launch (large batches).  Two thirds of a frame's ~550 rectangles are small
-// regions that fail the first test and walk through all five stages (22 pixel counts, 21 NFA values each) only to be rejected; with the staged kernels above that is
-// 17 grid-wide launches whose eval / math steps mostly move 112-byte work-list entries around.  Here every NFA value is one load from the NFA table and the
-// "keep it if better" chain stays in registers (the same chain as k_nfa_math, the same rect_count).  A rectangle with a candidate the table does not hold (512 pixels
-// or more) is handed, untouched, to the staged kernels through their stage-0 work list, exactly as k_nfa_init would have queued it.
-// ------------------------------------------------------------------------------------------------
-#ifndef PLF_NFA_SMALL_WPE
-#define PLF_NFA_SMALL_WPE 0
-#endif
-#if PLF_NFA_SMALL_WPE > 0
-#define PLF_NFA_SMALL_OCC __attribute__((amdgpu_waves_per_eu(PLF_NFA_SMALL_WPE, PLF_NFA_SMALL_WPE)))
-#else
-#define PLF_NFA_SMALL_OCC
-#endif
-// stages LO..HI of one rectangle by its group of 16 lanes (all lanes of the group return the same state)
-template <int LO, int HI>
-__device__ __forceinline__ void nfa_small_stages(const float *__restrict__ ang, const double *__restrict__ tab, const LsdGeom &g, int *par, int grp, int lane16,
-                                                 LsdRect &rec, double &log_nfa, bool &keep, bool &defer, bool &fin)
-{
-    const double LOG_EPS = 0.0, delta = 0.5, delta_2 = delta / 2.0;
-    NfaCounts c;
-    for (int stage = LO; stage <= HI && !fin; stage++) {
-        if (stage == 0 || stage == 4) {
-            if (stage == 4 && !((rec.width - delta) >= 0.5)) break;   // (nprec 0 in k_nfa_math: nothing to evaluate, not meaningful)
-            rect_count<6, 16>(ang, g.sw, g.sh, rec, c);
-            LsdRect r = rec;
-#pragma unroll
-            for (int k = 0; k < 6; k++) {
-                if (k > 0) { r.p /= 2; r.prec = r.p * PI_D; }
-                if (stage == 4 && k == 0) continue;
-                double v;
-                if (!nfa_lookup(tab, c.total, c.alg[k], r.p, v)) { defer = fin = true; break; }
-                if (stage == 0 && k == 0) {
-                    log_nfa = v;
-                    if (v > LOG_EPS) { keep = fin = true; break; }
-                } else if (v > log_nfa) { log_nfa = v; rec.p = r.p; rec.prec = r.prec; }
-            }
-        } else {
-            // 1: reduce the width, 2: reduce one side, 3: reduce the other side -- five candidates, each derived from the previous one: lane c of the group
-            // builds candidate c by the same c + 1 steps (lanes 5..15 idle along with candidate 4), then one pass counts all five
-            LsdRect r = rec;
-            bool valid = true;
-            const int myc = min(lane16, 4);
-            for (int k = 0; k <= 4; k++) {
-                if (k > myc) break;
-                if (!((r.width - delta) >= 0.5)) { valid = false; break; }   // (every later candidate fails the same test)
-                if (stage == 2) { r.x1 += -r.dy * delta_2; r.y1 += r.dx * delta_2; r.x2 += -r.dy * delta_2; r.y2 += r.dx * delta_2; }
-                if (stage == 3) { r.x1 -= -r.dy * delta_2; r.y1 -= r.dx * delta_2; r.x2 -= -r.dy * delta_2; r.y2 -= r.dx * delta_2; }
-                r.width -= delta;
-            }
-            const int nvalid = __popcll((__ballot(valid && lane16 < 5) >> (16 * grp)) & 31ull);   // (monotone: candidates 0 .. nvalid - 1)
-            if (nvalid > 0) {
-                int total[5], alg[5];
-                rect_count5(ang, g.sw, g.sh, r, valid, rec.theta, rec.prec, par, total, alg);
-                int best = -1;
-#pragma unroll
-                for (int k = 0; k < 5; k++) {
-                    if (k >= nvalid || fin) continue;
-                    double v;
-                    if (!nfa_lookup(tab, total[k], alg[k], rec.p, v)) { defer = fin = true; continue; }
-                    if (v > log_nfa) { log_nfa = v; best = k; }
-                }
-                if (best >= 0 && !defer) {
-                    const int src = (threadIdx.x & 48) + best;
-                    rec.x1 = shfl_d(r.x1, src); rec.y1 = shfl_d(r.y1, src); rec.x2 = shfl_d(r.x2, src); rec.y2 = shfl_d(r.y2, src); rec.width = shfl_d(r.width, src);
-                }
-            }
-        }
-        if (!fin && log_nfa > LOG_EPS) keep = fin = true;
-    }
-}
-
-// what a group's first lane does when its rectangle is decided: keep flag and segment, or the hand-over to the staged kernels (the rectangle as found)
-__device__ __forceinline__ void nfa_small_finish(int f, int ri, const LsdRect &rec, bool keep, bool defer, const LsdRect *__restrict__ rects_all, uint8_t *__restrict__ keep_all,
-                                                 float4 *__restrict__ seg_all, NfaEntry *__restrict__ entries, NfaState *__restrict__ states, int *__restrict__ counters,
-                                                 int *__restrict__ status, const LsdGeom &g)
-{
-    const size_t o = (size_t)f * g.rect_cap + ri;
-    keep_all[o] = keep && !defer ? 1 : 0;
-    if (defer) {
-        const int q = atomicAdd(&counters[0], 1);
-        if (q >= g.nfa_pool) { atomicOr(status, 1); return; }
-        NfaEntry e;
-        e.r = rects_all[o]; e.frame = f; e.nprec = 6; e.pad0 = e.pad1 = 0;
-        entries[q] = e;
-        NfaState st;
-        st.rec = e.r; st.log_nfa = -1; st.frame = f; st.rect = ri;
-        states[q] = st;
-    } else if (keep) emit_segment(rec, &seg_all[o]);
-}
-
-// surv != null (large batches): the rectangles that are not decided by stage 0 -- two thirds -- are queued per FRAME (surv[f * scap ..], fcnt[f]) for
-// k_nfa_small2 instead of walking through stages 1-4 here: the four groups of a wave then always have work (a wave of this kernel lasted as long as its longest
-// rectangle: 30 % of the group slots idled behind rectangles that stage 0 had already decided).  A full list is no error: the group carries on here.  (One counter
-// per frame, not per XCD: 350 k atomics on one address cost more than the stages they were to save.)
-__global__ void PLF_NFA_SMALL_OCC __launch_bounds__(64) k_nfa_small(const float *__restrict__ ang_all, const double *__restrict__ tab, const LsdRect *__restrict__ rects_all,
-                                                  const int *__restrict__ nrect, uint8_t *__restrict__ keep_all, float4 *__restrict__ seg_all,
-                                                  NfaEntry *__restrict__ entries, NfaState *__restrict__ states, int *__restrict__ counters,
-                                                  int *__restrict__ status, LsdGeom g, int nframes, NfaState *__restrict__ surv, int *__restrict__ fcnt, int scap)
-{
-    PLF_LINE_SETPRIO();
-    // grid (8 * slots, ceil(B / 8)): workgroups go to the 8 XCDs round-robin in dispatch order (x fastest), so XCD x works through frame 8 * blockIdx.y + x and the
-    // angle words of a frame are pulled into ONE L2 (k_orient_brief's order)
-    const int f = 8 * (int)blockIdx.y + ((int)blockIdx.x & 7), slot = (int)blockIdx.x >> 3, nslots = (int)gridDim.x >> 3;
-    if (f >= nframes) return;
-    __shared__ int s_par[4][5 * 12];
-    const int n_r = nrect[f], grp = threadIdx.x >> 4, lane16 = threadIdx.x & 15;
-    const float *ang = ang_all + (size_t)f * g.s_stride;
-    for (int i0 = slot * 4; i0 < n_r; i0 += nslots * 4) {
-        const int ri = i0 + grp;
-        if (ri >= n_r) continue;   // (groups are independent: rect_count's butterflies stay inside the 16 lanes)
-        LsdRect rec = rects_all[(size_t)f * g.rect_cap + ri];
-        double log_nfa = -1;
-        bool keep = false, defer = false, fin = false;
-        nfa_small_stages<0, 0>(ang, tab, g, &s_par[grp][0], grp, lane16, rec, log_nfa, keep, defer, fin);
-        if (!fin) {
-            int q = -1;
-            if (surv) {
-                if (lane16 == 0) q = atomicAdd(&fcnt[f], 1);
-                q = __shfl(q, threadIdx.x & 48, 64);
-            }
-            if (q >= 0 && q < scap) {
-                if (lane16 == 0) {
-                    NfaState st;
-                    st.rec = rec; st.log_nfa = log_nfa; st.frame = f; st.rect = ri;
-                    surv[(size_t)f * scap + q] = st;
-                }
-                continue;
-            }
-            nfa_small_stages<1, 4>(ang, tab, g, &s_par[grp][0], grp, lane16, rec, log_nfa, keep, defer, fin);
-        }
-        if (lane16 == 0) nfa_small_finish(f, ri, rec, keep, defer, rects_all, keep_all, seg_all, entries, states, counters, status, g);
-    }
-}
-
-// stages 1-4 of the rectangles k_nfa_small queued, same (frame, slot) grid: XCD x works through the frames 8 * blockIdx.y + x
-__global__ void PLF_NFA_SMALL_OCC __launch_bounds__(64) k_nfa_small2(const float *__restrict__ ang_all, const double *__restrict__ tab, const LsdRect *__restrict__ rects_all,
-                                                   uint8_t *__restrict__ keep_all, float4 *__restrict__ seg_all, NfaEntry *__restrict__ entries,
-                                                   NfaState *__restrict__ states, int *__restrict__ counters, int *__restrict__ status, LsdGeom g, int nframes,
-                                                   const NfaState *__restrict__ surv, const int *__restrict__ fcnt, int scap)
-{
-    PLF_LINE_SETPRIO();
-    const int f = 8 * (int)blockIdx.y + ((int)blockIdx.x & 7), slot = (int)blockIdx.x >> 3, nslots = (int)gridDim.x >> 3;
-    if (f >= nframes) return;
-    __shared__ int s_par[4][5 * 12];
-    const int n = min(fcnt[f], scap), grp = threadIdx.x >> 4, lane16 = threadIdx.x & 15;
-    const float *ang = ang_all + (size_t)f * g.s_stride;
-    for (int i0 = slot * 4; i0 < n; i0 += nslots * 4) {
-        const int i = i0 + grp;
-        if (i >= n) continue;
-        const NfaState st = surv[(size_t)f * scap + i];
-        LsdRect rec = st.rec;
-        double log_nfa = st.log_nfa;
-        bool keep = false, defer = false, fin = false;
-        nfa_small_stages<1, 4>(ang, tab, g, &s_par[grp][0], grp, lane16, rec, log_nfa, keep, defer, fin);
-        if (lane16 == 0) nfa_small_finish(f, st.rect, rec, keep, defer, rects_all, keep_all, seg_all, entries, states, counters, status, g);
-    }
-}
-
-// ------------------------------------------------------------------------------------------------
-// rect_improve of ONE rectangle by ONE wave, all five stages in one launch (few frames in flight).  The staged kernels above put a grid-wide barrier after
-// every count / eval / math step, so a stage lasts as long as its slowest rectangle: with one frame in flight the 17 launches took 1.2-2.4 ms, most of it the
-// binomial tails of a few rectangles per stage.  Here a rectangle's chain only waits for itself: count with the whole wave (rect_count<NP, 64>), the up to six
-// NFA values of a step in six lanes, the "keep if better" chain replayed exactly as k_nfa_math does.  Same device functions, same operations, same results.
-// ------------------------------------------------------------------------------------------------
-__device__ __forceinline__ double nfa_bcast(double v, int src) { return shfl_d(v, src); }
-
-// nfa_d in three pieces, so that the long exit-free part of the binomial tail can be shared by the wave.  A rectangle of n pixels needs about n / 2 - k tail
-// iterations, each `term *= ((n - i + 1) / i) * p_term; bin_tail += term`; for the large, sparse rectangles that go through all five stages that is 10^4
-// iterations per NFA value, and the fp64 division -- 14 of the 17 instructions of an iteration -- does not depend on the running product at all.  So the up to six
-// chains of a step (lanes 0..5) run in lock step and ALL 64 lanes compute the divisions of the next 512 iterations of every chain into LDS first; the chain lanes
-// then only multiply and add.  Every operation and its order inside a chain are those of nfa_d (the division is the same IEEE operation whichever lane does it).
-#define NFA_COOP_BLK 512
-
-// all 64 lanes; `it` of a lane that runs no chain has live == false.  tab: NFA_COOP_BLK doubles per chain lane (lanes 0..5)
-__device__ __forceinline__ void nfa_coop(NfaIt &it, LDS_PTR(double) tab, double LOG_NT)
-{
-    const int lane = plf_lane();
-    int done_j = 0;                                                   // iterations of the exit-free part already taken (the same for every chain: lock step)
-    int len = it.live ? it.iend - it.i : 0;
-    for (;;) {
-        int maxlen = len;
-#pragma unroll
-        for (int o = 4; o > 0; o >>= 1) maxlen = max(maxlen, __shfl_xor(maxlen, o, 64));   // (chains live in lanes 0..5)
-        maxlen = __builtin_amdgcn_readfirstlane(maxlen);
-        if (done_j >= maxlen) break;
-        // divisions of the next block of every chain
-        for (int c = 0; c < 6; c++) {
-            const int len_c = __builtin_amdgcn_readlane(len, c);
-            if (len_c <= done_j) continue;
-            const int n_c = __builtin_amdgcn_readlane(it.n, c), i_c = __builtin_amdgcn_readlane(it.i, c);   // (it.i: first iteration of the chain's exit-free part)
-            const int cnt = min(NFA_COOP_BLK, len_c - done_j);
-            for (int j = lane; j < cnt; j += 64) {
-                const int i = i_c + done_j + j;
-                tab[c * NFA_COOP_BLK + j] = (double)(n_c - i + 1) / (double)i;
-            }
-        }
-        CBAR();
-        if (lane < 6 && len > done_j) {
-            const int cnt = min(NFA_COOP_BLK, len - done_j);
-            LDS_PTR(double) tb = tab + lane * NFA_COOP_BLK;
-            double term = it.term, bin_tail = it.bin_tail, lastm = 2.0;
-            const double p_term = it.p_term;
-            int j = 0;
-            for (; j + 4 <= cnt; j += 4) {
-                const double m0 = tb[j] * p_term, m1 = tb[j + 1] * p_term, m2 = tb[j + 2] * p_term, m3 = tb[j + 3] * p_term;
-                term *= m0; bin_tail += term;
-                term *= m1; bin_tail += term;
-                term *= m2; bin_tail += term;
-                term *= m3; bin_tail += term;
-                lastm = m3;
-            }
-            for (; j < cnt; j++) { const double m0 = tb[j] * p_term; term *= m0; bin_tail += term; lastm = m0; }
-            it.term = term; it.bin_tail = bin_tail;
-            if (NFA_DEAD_TAIL(lastm, term, bin_tail)) {   // (nfa_d's early exit, checked once per block)
-                it.live = false; it.val = -log10(bin_tail) - LOG_NT; len = 0;
-            }
-        }
-        CBAR();
-        done_j += NFA_COOP_BLK;
-    }
-}
-
-// wave-uniform condition as a scalar: the compiler cannot see that the NFA values are the same in every lane and would turn `if (c) { rect = r; }` into 24 selects
-// (v_cndmask_b32_e32 back to back: 17-40 cycles each, profiles/r03_valu_issue.json) instead of a branch over 24 moves
-__device__ __forceinline__ bool uni(bool c) { return __builtin_amdgcn_readfirstlane((int)c) != 0; }
-
-// (st: the rectangle as found, log_nfa -1; keep_all of its slot is already 0)
-__device__ __forceinline__ NfaIt nfa_head_tab(const double *__restrict__ lgam, const double *__restrict__ nfatab, double LOG_NT, int n, int k, double p)
-{
-    double v;
-    if (nfatab && nfa_lookup(nfatab, n, k, p, v)) {   // (the host-filled table: nfa_d against glibc, i.e. the oracle's value)
-        NfaIt it;
-        it.live = false; it.term = it.bin_tail = it.p_term = 0.0; it.i = it.iend = 0; it.n = n; it.val = v;
-        return it;
-    }
-    return nfa_head(lgam, LOG_NT, n, k, p);
-}
-
-__device__ __forceinline__ void nfa_fused_rect(const float *__restrict__ ang, const double *__restrict__ lgam, const double *__restrict__ nfatab, LDS_PTR(double) tab, NfaState &st,
-                                               uint8_t *__restrict__ keep_all, float4 *__restrict__ seg_all, const LsdGeom &g)
-{
-    const int lane = threadIdx.x;
-    const double LOG_EPS = 0.0, delta = 0.5, delta_2 = delta / 2.0;
-    {
-        bool done = false;
-        // ---- stage 0: the rectangle as found, at its precision and the five halved ones
-        {
-            NfaCounts c;
-            rect_count<6, 64>(ang, g.sw, g.sh, st.rec, c);
-            double v = -1.0e300;
-            {
-                NfaIt it; it.live = false; it.n = 0; it.i = it.iend = 0; it.val = v;
-                if (lane < 6) {
-                    double pp = st.rec.p;
-                    for (int j = 0; j < lane; j++) pp /= 2;
-                    it = nfa_head_tab(lgam, nfatab, g.log_nt, c.total, c.alg[lane < 6 ? lane : 0], pp);
-                }
-                nfa_coop(it, tab, g.log_nt);
-                if (lane < 6) v = nfa_tail(it, g.log_nt);
-            }
-            st.log_nfa = nfa_bcast(v, 0);
-            if (uni(st.log_nfa > LOG_EPS)) done = true;
-            else {
-                LsdRect r = st.rec;
-                for (int k = 1; k <= 5; ++k) {
-                    r.p /= 2;
-                    r.prec = r.p * PI_D;
-                    const double vk = nfa_bcast(v, k);
-                    if (uni(vk > st.log_nfa)) { st.log_nfa = vk; st.rec = r; }
-                }
-                if (uni(st.log_nfa > LOG_EPS)) done = true;
-            }
-        }
-        // ---- stages 1..3: five progressively narrower / shifted candidates each
-        for (int stage = 0; stage <= 2 && !done; stage++) {
-            // (the candidates are a progressive sequence: generated once for the counts, once more for the pick -- cheaper than holding five rectangles)
-            int tot = 0, al = 0, non = 0;     // lane k keeps the counts of candidate k; non: candidates that exist (the width test fails for good once it fails)
-            {
-                LsdRect r = st.rec;
-                for (int k = 0; k < 5; ++k) {
-                    if (!((r.width - delta) >= 0.5)) break;
-                    if (stage == 1) { r.x1 += -r.dy * delta_2; r.y1 += r.dx * delta_2; r.x2 += -r.dy * delta_2; r.y2 += r.dx * delta_2; }
-                    if (stage == 2) { r.x1 -= -r.dy * delta_2; r.y1 -= r.dx * delta_2; r.x2 -= -r.dy * delta_2; r.y2 -= r.dx * delta_2; }
-                    r.width -= delta;
-                    NfaCounts c;
-                    rect_count<1, 64>(ang, g.sw, g.sh, r, c);
-                    if (lane == k) { tot = c.total; al = c.alg[0]; }
-                    non = k + 1;
-                }
-            }
-            double v = -1.0e300;
-            {
-                NfaIt it; it.live = false; it.n = 0; it.i = it.iend = 0; it.val = v;
-                if (lane < non) it = nfa_head_tab(lgam, nfatab, g.log_nt, tot, al, st.rec.p);
-                nfa_coop(it, tab, g.log_nt);
-                if (lane < non) v = nfa_tail(it, g.log_nt);
-            }
-            {
-                LsdRect r = st.rec;
-                for (int k = 0; k < non; ++k) {
-                    if (stage == 1) { r.x1 += -r.dy * delta_2; r.y1 += r.dx * delta_2; r.x2 += -r.dy * delta_2; r.y2 += r.dx * delta_2; }
-                    if (stage == 2) { r.x1 -= -r.dy * delta_2; r.y1 -= r.dx * delta_2; r.x2 -= -r.dy * delta_2; r.y2 -= r.dx * delta_2; }
-                    r.width -= delta;
-                    const double vk = nfa_bcast(v, k);
-                    if (uni(vk > st.log_nfa)) { st.rec = r; st.log_nfa = vk; }
-                }
-            }
-            if (uni(st.log_nfa > LOG_EPS)) done = true;
-        }
-        // ---- stage 4: finer precisions of the rectangle the width searches ended with
-        if (!done && (st.rec.width - delta) >= 0.5) {
-            NfaCounts c;
-            rect_count<6, 64>(ang, g.sw, g.sh, st.rec, c);
-            double v = -1.0e300;
-            {
-                NfaIt it; it.live = false; it.n = 0; it.i = it.iend = 0; it.val = v;
-                if (lane >= 1 && lane < 6) {
-                    double pp = st.rec.p;
-                    for (int j = 0; j < lane; j++) pp /= 2;
-                    it = nfa_head_tab(lgam, nfatab, g.log_nt, c.total, c.alg[lane < 6 ? lane : 0], pp);
-                }
-                nfa_coop(it, tab, g.log_nt);
-                if (lane >= 1 && lane < 6) v = nfa_tail(it, g.log_nt);
-            }
-            LsdRect r = st.rec;
-            for (int k = 1; k <= 5; ++k) {
-                r.p /= 2;
-                r.prec = r.p * PI_D;
-                const double vk = nfa_bcast(v, k);
-                if (uni(vk > st.log_nfa)) { st.log_nfa = vk; st.rec = r; }
-            }
-            if (uni(st.log_nfa > LOG_EPS)) done = true;
-        }
-        if (done && lane == 0) nfa_finish(st, seg_all, keep_all, g);
-    }
-}
-
-__global__ void __launch_bounds__(64) k_nfa_fused(const float *__restrict__ ang_all, const double *__restrict__ lgam, const double *__restrict__ nfatab, const LsdRect *__restrict__ rects_all,
-                                                  const int *__restrict__ nrect, uint8_t *__restrict__ keep_all, float4 *__restrict__ seg_all, LsdGeom g)
-{
-    __shared__ double tab_s[6 * NFA_COOP_BLK];
-    LDS_PTR(double) tab = (LDS_PTR(double))tab_s;
-    const int f = blockIdx.y, lane = threadIdx.x, n_r = nrect[f];
-    const float *ang = ang_all + (size_t)f * g.s_stride;
-    for (int ri = blockIdx.x; ri < n_r; ri += gridDim.x) {
-        NfaState st;
-        st.rec = rects_all[(size_t)f * g.rect_cap + ri]; st.log_nfa = -1; st.frame = f; st.rect = ri;
-        if (lane == 0) keep_all[(size_t)f * g.rect_cap + ri] = 0;
-        nfa_fused_rect(ang, lgam, nfatab, tab, st, keep_all, seg_all, g);
-    }
-}

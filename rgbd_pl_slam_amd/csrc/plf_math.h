@@ -278,7 +278,7 @@ PLF_MATH_CALL double nfa_d(const double *__restrict__ lgam, double LOG_NT, int n
     return -log10(bin_tail) - LOG_NT;
 }
 
-// nfa_d in pieces for the wave-cooperative kernels (lsd_kernels.hip, nfa_coop): nfa_head stops where nfa_d's exit-free blocks end (it.i .. it.iend: the
+// nfa_d in pieces for the wave-cooperative kernels (lsd_nfa.hip, nfa_coop): nfa_head stops where nfa_d's exit-free blocks end (it.i .. it.iend: the
 // iterations nfa_coop shares out), nfa_tail finishes a chain from it.iend.  nfa_head, then the exit-free iterations in order, then nfa_tail is nfa_d's chain.
 struct NfaIt { double term, bin_tail, p_term, val; int i, n, iend; bool live; };
 

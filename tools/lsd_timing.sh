@@ -1,7 +1,7 @@
 #!/bin/bash
-# rebuild lsd_kernels with -DPLF_LSD_TIMING into a scratch library and print the per-section cycle counts (frame 0)
+# rebuild the line extractor (lsd_*.hip) with -DPLF_LSD_TIMING into a scratch library, where tools/lsd_timing*.py look for it (PLF_TIMING_LIB); they print the
+# per-section cycle counts (frame 0).  PLF_TIMING_EXTRA: further flags for the same files, e.g. -DPLF_LSD_TIMING_NOCNT (cycles without the counters' global
+# read-modify-writes) or -DPLF_TIMING_BAND=5 (which band wave is timed)
 set -e
-cd "$(dirname "$0")/../rgbd_pl_slam_amd/csrc"
-FLAGS="--offload-arch=gfx950 -O3 -std=c++17 -fPIC -ffp-contract=off -fno-fast-math -fgpu-rdc -w"
-mkdir -p /tmp/plft && for f in orb_kernels orb_front orb_octree orb_host line_kernels line_host match_kernels match_host frame_kernels batch_host api_misc; do /opt/rocm/bin/hipcc $FLAGS -c $f.hip -o /tmp/plft/$f.o & done; /opt/rocm/bin/hipcc $FLAGS -DPLF_LSD_TIMING $PLF_TIMING_EXTRA -c lsd_kernels.hip -o /tmp/plft/lsd_kernels.o; wait
-/opt/rocm/bin/hipcc --offload-arch=gfx950 -fgpu-rdc --hip-link -shared -fPIC -o /tmp/plft/libplf_hip.so /tmp/plft/*.o
+bash "$(dirname "$0")/variant_build.sh" timing "lsd_*.hip=-DPLF_LSD_TIMING $PLF_TIMING_EXTRA"
+mkdir -p /tmp/plft && cp "$(dirname "$0")/scratch/libplf_timing.so" /tmp/plft/libplf_hip.so

@@ -1,5 +1,5 @@
 """Per-round anatomy of the validation rounds (few frames in flight): python tools/round_log.py <polygons|natural|photo> [B=1] [calls=4]   (photo: PHOTO=k picks the photograph, 6 = gravel)
-Needs a -DPLF_ROUND_LOG library:  bash tools/variant_build.sh rl lsd_kernels.hip=-DPLF_ROUND_LOG line_host.hip=-DPLF_ROUND_LOG
+Needs a -DPLF_ROUND_LOG library:  bash tools/variant_build.sh rl 'lsd_*.hip=-DPLF_ROUND_LOG' line_host.hip=-DPLF_ROUND_LOG
                                   PLF_LIB_PATH=tools/scratch/libplf_rl.so PLF_LSD_ROUND_LOG=1 python tools/round_log.py natural 1"""
 import sys, os, ctypes as C
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
