@@ -225,7 +225,10 @@ enum {
     PLF_MATH_LGAMMA = 8,      /* LSD log_gamma, evaluated on the device (double) */
     PLF_MATH_LGAMMA_TABLE = 9, /* the log_gamma table the line handles upload, entries 1 .. 65535 (double) */
     PLF_MATH_NFA_TABLE = 10,  /* the NFA table the line handles upload for LOG_NT = params[0] (double) */
-    PLF_MATH_NFA = 11         /* LSD nfa on the device, sampled (n, k, p); params: LOG_NT, log2 of the largest n / 512 (double) */
+    PLF_MATH_NFA = 11,        /* LSD nfa on the device, sampled (n, k, p); params: LOG_NT, log2 of the largest n / 512 (double) */
+    PLF_MATH_DSQRT = 12,      /* double sqrt of sampled finite non-negative doubles (double): the pose routine's exactness rests on it */
+    PLF_MATH_DDIV = 13,       /* double division of sampled finite doubles (double) */
+    PLF_MATH_SINCOS_D = 14    /* plf_sincos_d of 2^20 log-spaced angles of [1e-5, 2 pi] (double2: sin, cos) */
 };
 int plf_debug_math(int32_t op, const double *params, int64_t first, int64_t n, void *out_dev, int32_t device, void *stream);
 
@@ -1223,6 +1226,57 @@ int plf_local_gather(const int32_t *local_item, const int32_t *n_local_item, int
 int plf_local_visible(const int32_t *local_item, const int32_t *n_local_item, const uint8_t *seen, int32_t n_rows, int32_t item_stride,
                       uint8_t *in_view, int32_t *n_to_match, int32_t *visible, const int32_t *frame_row_start, const int32_t *frame_row_item,
                       const uint8_t *item_bad, int32_t n_items, int32_t device, void *stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * Pose optimisation: Optimizer::PoseOptimization(Frame*) (so@0xaef50), the motion-only refinement Tracking runs in TrackReferenceKeyFrame,
+ * TrackWithMotionModel, TrackLocalMap and three times in Relocalization, for n_frames frames in ONE launch -- one wave per frame, the four
+ * rounds of g2o's Levenberg-Marquardt inside, nothing read back.  Points only: the binary exports no PoseOptimizationWithLine (the header
+ * declares it with a "todo", and lineEdge.h leaves its Jacobian uninitialised), so line edges are not part of this call.
+ *
+ * The definition is tests/poseref.py: the routine restated from the g2o sources the reference ships, in IEEE double operations without FMA;
+ * the device writes the bits of that file.  Against the binary it is the same algorithm, accumulation order and constants, but the
+ * association inside Eigen's LDLT / quaternion code and the last bit of libm's sin / cos (here plf_sincos_d, csrc/plf_math.h) are fixed by
+ * that file, not measured -- PARITY UNPINNED.
+ *
+ * Per frame f: key point i < N (N = n_device[f] clamped to [0, kp_stride], or n_host) with match_of_kp[f, i] >= 0 is one edge -- mono when
+ * uright < 0, else stereo -- observing world_pos row match_of_kp[f, i]; information inv_level_sigma2[octave] (octave clamped to the table).
+ * Fewer than 3 edges: pose_out = pose_in, n_inliers = 0, status PLF_POSE_EARLY, no flag written.  Otherwise the outlier flag of every
+ * matched key point is written (no other entry of `outlier` is touched), n_inliers = edges - outliers of the last round, and status has
+ * PLF_POSE_NONFINITE when an entry of pose_out is not finite (NaN / Inf inputs, a singular start pose); nothing faults on such input.
+ * A NaN entry of pose_out or frustum_out has unspecified sign and payload (IEEE leaves them to the implementation: the device's default NaN and a host's differ).
+ * frustum_out (optional): Rcw, tcw and Ow = -Rcw^T tcw of pose_out as Frame::UpdatePoseMatrices forms them in float -- what plf_frustum_* reads.
+ * Every array is DEVICE memory except pose_in (pose_mem: PLF_MEM_HOST or PLF_MEM_DEVICE) and cam; asynchronous on `stream`;
+ * PLF_E_BADARG (NULL arrays, n_frames < 0, kp_stride < 1, pos_stride < 0, nlevels < 1, n_host outside [0, kp_stride] without n_device)
+ * is returned before any device work.
+ * ---------------------------------------------------------------------------------------------- */
+enum { PLF_POSE_EARLY = 1, PLF_POSE_NONFINITE = 2 };
+typedef struct { float Tcw[12]; } plf_pose34;            /* rows of [Rcw | tcw] */
+typedef struct {
+    int32_t n_frames, kp_stride, pos_stride;
+    const plf_keypoint *keys_un;                          /* n_frames x kp_stride */
+    const float *uright;                                  /* n_frames x kp_stride */
+    const int32_t *n_device;                              /* N per frame, or NULL: n_host for every frame */
+    int32_t n_host;
+    const int32_t *match_of_kp;                           /* n_frames x kp_stride; >= 0: row of world_pos; < 0: none */
+    const float *world_pos;                               /* frame f reads world_pos + f * pos_stride * 3; pos_stride 0 = one shared array */
+    const float *inv_level_sigma2;
+    int32_t nlevels;
+} plf_pose_view;
+int plf_pose_optimize(const plf_pose_view *v, const plf_camera *cam, const plf_pose34 *pose_in, int32_t pose_mem, plf_pose34 *pose_out,
+                      plf_frustum_pose *frustum_out, uint8_t *outlier, int32_t *n_inliers, int32_t *status, int32_t device, void *stream);
+
+/* The caller's statements right after PoseOptimization, one elementwise kernel.  For every matched key point (row = match_of_kp[f, i] >= 0;
+ * its map id = row_id[f * id_stride + row] when row_id is given -- the local_item of plf_local_items -- else the row itself):
+ *   PLF_POSE_COMMIT_DISCARD (TrackWithMotionModel, TrackReferenceKeyFrame): an outlier gets match_of_kp = -1; n_out[f] = the remaining
+ *     matches whose point has n_obs[id] > 0 (nmatchesMap).  n_obs is required.
+ *   PLF_POSE_COMMIT_FOUND (TrackLocalMap): found[id] += 1 per inlier match (MapPoint::IncreaseFound, integer atomics: a point matched from
+ *     two frames is raised twice) -- the array plf_map_point_culling reads; n_out[f] = the inlier matches with n_obs[id] > 0
+ *     (mnMatchesInliers; n_obs NULL = mbOnlyTracking: every inlier match counts).  match_of_kp is not written.
+ * An id outside [0, n_points) is counted nowhere.  `outlier` is read only.  Device memory, asynchronous, PLF_E_BADARG before any device work. */
+enum { PLF_POSE_COMMIT_DISCARD = 0, PLF_POSE_COMMIT_FOUND = 1 };
+int plf_pose_commit(int32_t mode, int32_t *match_of_kp, const uint8_t *outlier, const int32_t *n_device, int32_t n_host, int32_t n_frames,
+                    int32_t kp_stride, const int32_t *row_id, int32_t id_stride, const int32_t *n_obs, int32_t n_points, int32_t *found,
+                    int32_t *n_out, int32_t device, void *stream);
 
 #ifdef __cplusplus
 }

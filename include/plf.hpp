@@ -1637,6 +1637,60 @@ LocalMapResult<KeyFrameT, MapPointT> UpdateLocalMap(FrameT &mCurrentFrame, std::
     for (int i = 0; i < h_n[0]; i++) { mvpLocalMapPoints.push_back(pts[h_item[i]]); out.seen.push_back(h_seen[i]); }
     return out;
 }
+// Optimizer::PoseOptimization(Frame*) (so@0xaef50), the reference's signature over its own Frame / MapPoint: the matched key points of ONE frame go to the
+// device as a plf_pose_view, plf_pose_optimize refines mTcw, and the frame gets what the reference's body leaves in it -- mvbOutlier of every matched key
+// point, SetPose(the refined Tcw) -- and the call returns nInitialCorrespondences - nBad.  Points only, as the binary (the header's
+// PoseOptimizationWithLine has no body anywhere).  With fewer than 3 matches: returns 0, frame untouched.  For ONE frame the adapter uploads and waits; a
+// tracker with its frames resident calls plf_pose_optimize on all of them at once and reads nothing back.  fx, fy, cx, cy are static members of Frame in
+// the reference, mbf an ordinary one: read as pFrame->fx etc.
+struct Optimizer {
+    template <class FrameT> static int PoseOptimization(FrameT *pFrame, int device = 0)
+    {
+        const int N = pFrame->N;
+        if (N <= 0) return 0;
+        std::vector<plf_keypoint> keys(N);
+        std::vector<float> uright(N, -1.0f), pos;
+        std::vector<int32_t> match(N, -1);
+        std::vector<uint8_t> flags(N, 0);
+        int nInitialCorrespondences = 0;
+        for (int i = 0; i < N; i++) {
+            const cv::KeyPoint &kp = pFrame->mvKeysUn[i];
+            keys[i] = plf_keypoint{kp.pt.x, kp.pt.y, kp.size, kp.angle, kp.response, kp.octave, kp.class_id};
+            uright[i] = pFrame->mvuRight[i];
+            flags[i] = pFrame->mvbOutlier[i] ? 1 : 0;
+            auto *pMP = pFrame->mvpMapPoints[i];
+            if (!pMP) continue;
+            const cv::Mat Xw = pMP->GetWorldPos();
+            match[i] = nInitialCorrespondences++;
+            for (int k = 0; k < 3; k++) pos.push_back(Xw.template at<float>(k));
+        }
+        if (nInitialCorrespondences < 3) return 0;
+        plf_pose34 pin, pout;
+        for (int r = 0; r < 3; r++)
+            for (int c = 0; c < 4; c++) pin.Tcw[4 * r + c] = pFrame->mTcw.template at<float>(r, c);
+        const std::vector<float> sigma2(pFrame->mvInvLevelSigma2.begin(), pFrame->mvInvLevelSigma2.end());
+        plf::DeviceArray<plf_keypoint> dkeys(keys, device);
+        plf::DeviceArray<float> dur(uright, device), dpos(pos, device), dsig(sigma2, device);
+        plf::DeviceArray<int32_t> dmatch(match, device), dn(1, device), dst(1, device);
+        plf::DeviceArray<uint8_t> dflags(flags, device);
+        plf::DeviceArray<plf_pose34> dout(1, device);
+        plf_pose_view v = {};
+        v.n_frames = 1; v.kp_stride = N; v.pos_stride = 0; v.keys_un = dkeys.get(); v.uright = dur.get(); v.n_host = N; v.match_of_kp = dmatch.get();
+        v.world_pos = dpos.get(); v.inv_level_sigma2 = dsig.get(); v.nlevels = (int32_t)sigma2.size();
+        plf_camera cam = {};
+        cam.fx = pFrame->fx; cam.fy = pFrame->fy; cam.cx = pFrame->cx; cam.cy = pFrame->cy; cam.bf = pFrame->mbf;
+        plf::check(plf_pose_optimize(&v, &cam, &pin, PLF_MEM_HOST, dout.get(), nullptr, dflags.get(), dn.get(), dst.get(), device, nullptr), "PoseOptimization");
+        pout = dout.download()[0];                            // a NULL-stream download waits for the device first
+        flags = dflags.download();
+        for (int i = 0; i < N; i++)
+            if (match[i] >= 0) pFrame->mvbOutlier[i] = flags[i] != 0;
+        cv::Mat Tcw(4, 4, CV_32F);
+        for (int r = 0; r < 4; r++)
+            for (int c = 0; c < 4; c++) Tcw.template at<float>(r, c) = r < 3 ? pout.Tcw[4 * r + c] : (c == 3 ? 1.0f : 0.0f);
+        pFrame->SetPose(Tcw);
+        return dn.download()[0];
+    }
+};
 }  // namespace ORB_SLAM2_PLF
 #endif
 #endif

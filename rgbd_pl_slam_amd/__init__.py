@@ -16,3 +16,5 @@ from . import culling  # noqa: F401
 from .culling import keyframe_culling, map_point_culling, CullMap  # noqa: F401
 from . import localmap  # noqa: F401
 from .localmap import local_keyframes, local_items, local_gather, local_visible, update_local_map, children_csr, LocalMap  # noqa: F401
+from . import pose  # noqa: F401
+from .pose import pose_optimization, pose_commit, PoseResult  # noqa: F401

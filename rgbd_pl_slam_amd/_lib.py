@@ -305,3 +305,25 @@ def localmap_prototypes(l):
     l.plf_local_gather.argtypes = [P, P, I, I, C.POINTER(LocalMapSrc), C.POINTER(LocalMapDst), I, P]
     l.plf_local_visible.argtypes = [P, P, P, I, I, P, P, P, P, P, P, I, I, P]
     return l
+
+
+# ---- pose optimisation (include/plf.h, "Pose optimisation")
+POSE_EARLY, POSE_NONFINITE = 1, 2
+POSE_COMMIT_DISCARD, POSE_COMMIT_FOUND = 0, 1
+
+
+class Camera(C.Structure):
+    _fields_ = [(n, C.c_float) for n in ("fx", "fy", "cx", "cy", "k1", "k2", "p1", "p2", "k3", "bf")]
+
+
+class PoseView(C.Structure):
+    _fields_ = [("n_frames", C.c_int32), ("kp_stride", C.c_int32), ("pos_stride", C.c_int32), ("keys_un", C.c_void_p), ("uright", C.c_void_p),
+                ("n_device", C.c_void_p), ("n_host", C.c_int32), ("match_of_kp", C.c_void_p), ("world_pos", C.c_void_p),
+                ("inv_level_sigma2", C.c_void_p), ("nlevels", C.c_int32)]
+
+
+def pose_prototypes(l):
+    P, I = C.c_void_p, C.c_int32
+    l.plf_pose_optimize.argtypes = [C.POINTER(PoseView), C.POINTER(Camera), P, I, P, P, P, P, P, I, P]
+    l.plf_pose_commit.argtypes = [I, P, P, P, I, I, I, P, I, P, I, P, P, I, P]
+    return l

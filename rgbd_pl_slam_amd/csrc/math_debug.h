@@ -20,6 +20,8 @@ PLF_MATH int64_t plf_math_domain(int op)
         case PLF_MATH_LGAMMA_TABLE: return LGAM_N - 1;             // the table entries 1 .. LGAM_N - 1
         case PLF_MATH_NFA_TABLE: return (int64_t)NFA_TAB_P * NFA_TAB_ROW;
         case PLF_MATH_NFA: return 1ll << 40;
+        case PLF_MATH_DSQRT: case PLF_MATH_DDIV: return 1ll << 40;  // sampled operands
+        case PLF_MATH_SINCOS_D: return 1ll << 20;                   // log-spaced angles of [1e-5, 2 pi]
         default: return -1;
     }
 }
@@ -44,6 +46,26 @@ PLF_MATH void plf_nfa_sample(int64_t i, int nshift, int *n, int *k, double *p)
     double q = 0.125;
     for (int t = 0; t < jp; t++) q /= 2;
     *p = q;
+}
+
+// operand j of sample i of PLF_MATH_DSQRT / PLF_MATH_DDIV: 64 pseudo-random bits as a double, an all-ones exponent (Inf / NaN) cut to a finite one
+PLF_MATH double plf_double_sample(int64_t i, int j)
+{
+    uint64_t u = plf_splitmix64(2 * (uint64_t)i + (uint64_t)j);
+    if (((u >> 52) & 0x7ff) == 0x7ff) u &= ~(1ull << 62);
+    double d;
+    __builtin_memcpy(&d, &u, 8);
+    return d;
+}
+// angle i of PLF_MATH_SINCOS_D: the double whose bit pattern lies i equal steps above that of 1e-5, the last one just below that of 2 pi -- log-spaced up to the
+// mantissa, and computed without a libm call, so that the test forms the very same angles with integer arithmetic
+PLF_MATH double plf_angle_sample(int64_t i)
+{
+    const uint64_t lo = 0x3EE4F8B588E368F1ull, hi = 0x401921FB54442D18ull;   // 1e-5, 2 pi
+    const uint64_t u = lo + (uint64_t)i * ((hi - lo) / ((1ull << 20) - 1));
+    double d;
+    __builtin_memcpy(&d, &u, 8);
+    return d;
 }
 
 // tab: PLF_MATH_LGAMMA_TABLE, PLF_MATH_NFA: the log_gamma table as the line handles upload it; PLF_MATH_NFA_TABLE: the NFA table of log_nt, likewise
@@ -97,6 +119,15 @@ PLF_MATH void plf_math_eval(int op, float log_scale, int nlevels, int64_t i, voi
             break;
         case PLF_MATH_NFA_TABLE:
             ((double *)out)[j] = tab[i];
+            break;
+        case PLF_MATH_DSQRT:
+            ((double *)out)[j] = sqrt(fabs(plf_double_sample(i, 0)));
+            break;
+        case PLF_MATH_DDIV:
+            ((double *)out)[j] = plf_double_sample(i, 0) / plf_double_sample(i, 1);
+            break;
+        case PLF_MATH_SINCOS_D:
+            plf_sincos_d(plf_angle_sample(i), (double *)out + 2 * j, (double *)out + 2 * j + 1);
             break;
         case PLF_MATH_NFA: {
             int n, k;

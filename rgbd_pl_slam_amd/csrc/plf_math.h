@@ -109,6 +109,54 @@ PLF_MATH void plf_sincosf_glibc(float y, float *sinp, float *cosp)
     if (n & 1) { *sinp = cv; *cosp = sv; } else { *sinp = sv; *cosp = cv; }
 }
 
+// sin and cos of a double angle as ONE explicit sequence of IEEE double operations (no FMA, no libm call), so that the device (pose_kernels.hip:
+// the update angle of SE3Quat::exp), the host loop (tools/pose_cpu.cpp) and the definition (tests/poseref.py, through tests/cpp/pose_mathhost.cpp)
+// share the bits.  Valid on [0, 7); the pose routine calls it on [1e-5, ...), below that the exp map takes its series branch.  Reduction
+// to |r| <= pi / 4 by the nearest multiple k of pi / 2 held as hi + lo (theta - hi is exact by Sterbenz, the subtraction of lo leaves a tail that
+// the kernels take), then the two fdlibm kernels (k_sin.c / k_cos.c, Sun Microsystems 1993, freely usable), each below 1 ulp.  Against glibc's
+// sin / cos: within 1 ulp on 10^6 log-spaced angles of [1e-5, 2 pi] (tests/test_pose_ref.py).
+PLF_MATH double plf_hi_word_d(double hi32_of, int sub)   // the double whose high word is that of |x| minus `sub`, low word zero
+{
+    uint64_t u;
+    __builtin_memcpy(&u, &hi32_of, 8);
+    u = (uint64_t)(((uint32_t)(u >> 32) & 0x7fffffffu) - (uint32_t)sub) << 32;
+    double r;
+    __builtin_memcpy(&r, &u, 8);
+    return r;
+}
+PLF_MATH void plf_sincos_d(double theta, double *sinp, double *cosp)
+{
+    if (!(theta >= 0.0 && theta < 7.0)) { *sinp = *cosp = (double)__uint_as_float(0x7FC00000u); return; }   // outside the domain (or NaN): NaN, on every side
+    const int k = (int)(theta * 0x1.45f306dc9c883p-1 + 0.5);   // nearest multiple of pi / 2
+    const double hi = k == 1 ? 0x1.921fb54442d18p+0 : k == 2 ? 0x1.921fb54442d18p+1 : k == 3 ? 0x1.2d97c7f3321d2p+2 : k == 4 ? 0x1.921fb54442d18p+2 : 0.0;
+    const double lo = k == 1 ? 0x1.1a62633145c07p-54 : k == 2 ? 0x1.1a62633145c07p-53 : k == 3 ? 0x1.a79394c9e8a0ap-53 : k == 4 ? 0x1.1a62633145c07p-52 : 0.0;
+    const double t = theta - hi;
+    const double x = t - lo;
+    const double y = (t - x) - lo;                             // the tail of the reduced argument
+    const double z = x * x;
+    // k_sin
+    const double S1 = -1.66666666666666324348e-01, S2 = 8.33333333332248946124e-03, S3 = -1.98412698298579493134e-04, S4 = 2.75573137070700676789e-06,
+                 S5 = -2.50507602534068634195e-08, S6 = 1.58969099521155010221e-10;
+    const double v = z * x;
+    const double rs = S2 + z * (S3 + z * (S4 + z * (S5 + z * S6)));
+    const double s = x - ((z * (0.5 * y - v * rs) - y) - v * S1);
+    // k_cos
+    const double C1 = 4.16666666666666019037e-02, C2 = -1.38888888888741095749e-03, C3 = 2.48015872894767294178e-05, C4 = -2.75573143513906633035e-07,
+                 C5 = 2.08757232129817482790e-09, C6 = -1.13596475577881948265e-11;
+    const double rc = z * (C1 + z * (C2 + z * (C3 + z * (C4 + z * (C5 + z * C6)))));
+    const double ax = fabs(x);
+    double c;
+    if (ax < 0x1.33333p-2) c = 1.0 - (0.5 * z - (z * rc - x * y));
+    else {
+        const double qx = ax > 0.78125 ? 0.28125 : plf_hi_word_d(x, 0x00200000);
+        const double hz = 0.5 * z - qx, a = 1.0 - qx;
+        c = a - (hz - (z * rc - x * y));
+    }
+    const int q = k & 3;
+    *sinp = q == 0 ? s : q == 1 ? c : q == 2 ? -s : -c;
+    *cosp = q == 0 ? c : q == 1 ? -s : q == 2 ? -c : s;
+}
+
 // Thresholds of the cheap alignment pre-test of region_grow (lsd_kernels.hip): t1 <= tan(prec - delta), t2 >= tan(prec + delta), delta = 0.05 degrees.
 // The pre-test only sorts candidates into "surely aligned", "surely not" and "border" (decided by the reference's own test), so ANY t1 below and
 // t2 above those tangents is sound: single-precision tanf with a 1e-4 relative safety factor (its error is ~1e-7; the band is ~2.5e-3 wide) keeps
