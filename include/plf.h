@@ -1278,6 +1278,123 @@ int plf_pose_commit(int32_t mode, int32_t *match_of_kp, const uint8_t *outlier, 
                     int32_t kp_stride, const int32_t *row_id, int32_t id_stride, const int32_t *n_obs, int32_t n_points, int32_t *found,
                     int32_t *n_out, int32_t device, void *stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * Tracking tail -- the statements of void Tracking::Track() (so@0x4f2f0) after plf_pose_commit, which produce what the NEXT frame's first
+ * matcher reads: bool Tracking::NeedNewKeyFrame() (so@0x49750), the point half of void Tracking::CreateNewKeyFrame() (so@0x4e040) and of
+ * void Tracking::UpdateLastFrame() (so@0x4e570), the motion model and the two match clean-ups.  Any number of frames per call.  Points only:
+ * CreateNewKeyFrame calls no MapLine constructor, and the binary has no CreateNewMapLines / UpdateLocalLines.
+ *
+ * The definition is tests/trackref.py, one float32 operation per statement.  Fixed by the binary: the control flow, the constants, the order of
+ * the float multiplies.  Fixed by this project's restatement of cv::gemm's small-matrix float path (each entry a float sum of the products from
+ * the left, then + C; as oracle/match_oracle.c holds it for Rcw * p + tcw), not by executed OpenCV code: the bits of mRwc * x3Dc + mOw and of
+ * the 4x4 products -- PARITY UNPINNED.
+ *
+ * Common to the calls: frame f's arrays start at f * kp_stride; N = n_device[f] clamped to [0, kp_stride], or n_host.  The point behind key
+ * point i: row = match_of_kp[f, i] (< 0: none); its map id = row_id[f * id_stride + row] when row_id is given (a row >= id_stride: none), else
+ * the row; an id outside [0, n_points) is "no point" everywhere here.  Observations() is n_obs[id].
+ * Stateless; every array is DEVICE memory; asynchronous on `stream`; nothing is read back; no scratch is needed.  PLF_E_BADARG (a NULL required
+ * array, negative sizes, strides < 1, n_host outside [0, kp_stride] without n_device, a mode outside its enum) is returned before any device
+ * work.  NaN / Inf values and out-of-range ids fault nowhere.
+ *
+ * plf_track_close_points -- the loop CreateNewKeyFrame (so@0x4e0fd-0x4e400) and UpdateLastFrame (so@0x4e938-0x4ecc8) share:
+ *  1. the entries are the pairs (z, i), i < N, z = depth[f, i], with z > 0 (vucomiss + jbe, so@0x4e171 / 0x4e9b1: a NaN or -0.0 is no entry),
+ *     ordered by std::sort on pair<float,int> (so@0x4e1ca): by z, equal z by i.
+ *  2. they are walked in order, nPoints = 1, 2, ... counting EVERY visited entry (mov %ebp,%ecx in both branches, so@0x4e257 / 0x4e344).
+ *  3. an entry is created when it has no point (so@0x4e2b6) or Observations() < 1 (jle, so@0x4e259).
+ *  4. AFTER the entry is handled: z > th_depth && nPoints > min_points (cmp $0x64; jg, so@0x4e275 / 0x4eb60) ends the walk.  The ending entry
+ *     itself is still created, so up to min_points + 1 far entries are (as upstream ORB-SLAM2 does).
+ *  5. a created entry's position is Frame::UnprojectStereo(i) (so@0xf6dc0): x = ((u - cx) * z) * invfx (so@0xf6e5c-0xf6e6b), y = ((v - cy) * z)
+ *     * invfy (so@0xf6eaf-0xf6f1c), invfx = 1.0f / fx; then mRwc * (x, y, z) + mOw with mRwc = Rcw^T and mOw of the frame's plf_frustum_pose.
+ *  The binary differs from upstream in UpdateLastFrame's guard: it returns for mnLastKeyFrameId == mLastFrame.mnId or a monocular sensor only
+ *  (so@0x4e8cc-0x4e8e2) -- there is no mbOnlyTracking test, temporal points are made in SLAM mode too.  The guard is the caller's.
+ *  min_points = INT32_MAX disables the cut: every entry is walked, which is the SET Tracking::StereoInitialization (so@0x4b680) creates
+ *  (it walks by index, not by depth).
+ *  Outputs: new_kp[f, k] = key point of the k-th created entry, new_pos[f, k, 0..3) its position, for k < new_stride; n_new[f] the TRUE count,
+ *  n_walked[f] the entries visited, status[f] = PLF_TRACK_OVERFLOW when n_new[f] > new_stride.  Entries from min(n_new, new_stride) on are
+ *  not written.  mode PLF_TRACK_CLOSE_KEYFRAME: match_of_kp[f, new_kp] = id_base[f] + k, in place (mCurrentFrame.mvpMapPoints[i] = pNewMP);
+ *  the caller appends new_pos to the resident map.  mode PLF_TRACK_CLOSE_LASTFRAME: has_mappoint[f, i] = 1, world_pos[f, i] = position,
+ *  obs_positive[f, i] = 0 in the arrays behind a plf_lastframe_view (each n_frames x kp_stride), the temporal points
+ *  plf_match_project_lastframe reads.  Both apply to the entries below new_stride only.
+ *  One launch; kp_stride <= 1024: one wave per frame, <= 16384: one workgroup of 256 (128 KB of LDS at most); larger: PLF_E_BADARG.
+ *  The entries are packed as (bits(z) << 32) | i -- a positive float's bits order as an unsigned integer --, compacted into LDS, padded to a
+ *  power of two and sorted by a bitonic network; the cut is a count, the created entries are emitted in order by a scan.
+ * ---------------------------------------------------------------------------------------------- */
+enum { PLF_TRACK_OVERFLOW = 1, PLF_TRACK_NONFINITE = 1 };
+enum { PLF_TRACK_CLOSE_LIST = 0, PLF_TRACK_CLOSE_KEYFRAME = 1, PLF_TRACK_CLOSE_LASTFRAME = 2 };
+typedef struct {
+    int32_t n_frames, kp_stride;
+    const plf_keypoint *keys_un;                          /* n_frames x kp_stride (close_points only) */
+    const float *depth;                                   /* n_frames x kp_stride: mvDepth, the kp_depth of plf_frame_tail */
+    const int32_t *match_of_kp;                           /* n_frames x kp_stride */
+    const int32_t *n_device;                              /* N per frame, or NULL: n_host for every frame */
+    int32_t n_host;
+    const int32_t *row_id;                                /* optional, n_frames x id_stride */
+    int32_t id_stride;
+    const int32_t *n_obs;                                 /* n_points */
+    int32_t n_points;
+    const plf_frustum_pose *pose;                         /* n_frames (close_points only): the frustum_out of plf_pose_optimize */
+} plf_track_view;
+typedef struct { float th_depth; int32_t min_points, mode, new_stride; } plf_track_close_params;   /* min_points: 100 in the binary */
+typedef struct { uint8_t *has_mappoint; float *world_pos; uint8_t *obs_positive; } plf_track_lastframe_out;
+/* id_base: n_frames, PLF_TRACK_CLOSE_KEYFRAME only (then v->match_of_kp is written); last: PLF_TRACK_CLOSE_LASTFRAME only */
+int plf_track_close_points(const plf_track_view *v, const plf_camera *cam, const plf_track_close_params *p, const int32_t *id_base,
+                           const plf_track_lastframe_out *last, int32_t *new_kp, float *new_pos, int32_t *n_new, int32_t *n_walked,
+                           int32_t *status, int32_t device, void *stream);
+
+/* Tracking::NeedNewKeyFrame, from the binary (NOT upstream's current form: there is no nTrackedClose < 100 / nNonTrackedClose > 70 test and
+ * mvbOutlier is not read):
+ *   mbOnlyTracking (so@0x4976e), isStopped() || stopRequested() (so@0x497aa-0x497c4): no.
+ *   mnId < mnLastRelocFrameId + mMaxFrames && nKFs > mMaxFrames (so@0x497d5-0x497fc; the sums are 32-bit, the ids compare as 64-bit unsigned): no.
+ *   nMinObs = nKFs >= 3 ? 3 : 2 (so@0x4980b); nRefMatches = mpReferenceKF->TrackedMapPoints(nMinObs) (so@0x98280: non-null, not isBad(),
+ *     Observations() >= nMinObs): here the row ref_kf of kf_row_start / kf_row_item (the rows plf_local_items reads) with item_bad and n_obs;
+ *     a ref_kf outside [0, n_kf) counts 0.
+ *   the loop so@0x49860-0x498be: for z = mvDepth[i] with z > 0 && z < mThDepth: nTotal++, and nMap++ when the key point has a point with
+ *     Observations() > 0.  ratioMap = (float)nMap / (float)max(1, nTotal) (so@0x498c0-0x498e4); a monocular sensor takes 1.
+ *   thRefRatio = 0.75f, 0.4f when nKFs <= 1, 0.9f monocular (so@0x498ee, 0x49a40, 0x4996a); thMapRatio = 0.35f, 0.20f when mnMatchesInliers > 300
+ *     (so@0x49904-0x49913).
+ *   c1a = mnId >= mnLastKeyFrameId + mMaxFrames; c1b = mnId >= mnLastKeyFrameId + mMinFrames && AcceptKeyFrames() (so@0x499c2-0x499ee);
+ *   c1c = not monocular && (mnMatchesInliers < nRefMatches * 0.25 [double] || ratioMap < 0.3f) (so@0x49920-0x4994c);
+ *   c2 = (mnMatchesInliers < nRefMatches * thRefRatio [float] || ratioMap < thMapRatio) && mnMatchesInliers > 15 (so@0x49993-0x499bc).
+ *   (c1a || c1b || c1c) && c2: AcceptKeyFrames() ? yes : InterruptBA(), and KeyframesInQueue() < 3 for a non-monocular sensor (so@0x49a50-0x49aa5).
+ * decision[f]: 0 = no, 1 = insert, 2 = the conditions hold but the mapper is busy -- InterruptBA() and the queue test are thread state and
+ * follow on the host.  counts[f, 0..3) = nTotal, nMap, nRefMatches.  n_inliers (optional, n_frames: the n_out of plf_pose_commit) replaces
+ * state[f].n_matches_inliers.  v->keys_un and v->pose are not read.  One wave per frame. */
+enum { PLF_TRACK_ONLY_TRACKING = 1, PLF_TRACK_MAPPER_STOPPED = 2, PLF_TRACK_MAPPER_IDLE = 4, PLF_TRACK_MONO = 8 };
+typedef struct {
+    int64_t frame_id;                                     /* mCurrentFrame.mnId */
+    int32_t ref_kf;                                       /* slot of mpReferenceKF */
+    int32_t n_matches_inliers;
+    uint32_t last_kf_id, last_reloc_frame_id;             /* mnLastKeyFrameId, mnLastRelocFrameId */
+    int32_t min_frames, max_frames, n_kfs;
+    int32_t flags;                                        /* PLF_TRACK_ONLY_TRACKING | _MAPPER_STOPPED (isStopped || stopRequested) | _MAPPER_IDLE (AcceptKeyFrames) | _MONO */
+} plf_track_kf_state;
+typedef struct { const int32_t *kf_row_start, *kf_row_item; int32_t n_kf; const uint8_t *item_bad; } plf_track_kf_view;   /* item_bad optional */
+int plf_track_need_keyframe(const plf_track_view *v, const plf_track_kf_view *kf, const plf_track_kf_state *state, const int32_t *n_inliers,
+                            float th_depth, int32_t *counts, int32_t *decision, int32_t device, void *stream);
+
+/* The motion model, one thread per frame, every product a 4x4 on the small-matrix float path (poses carry the row 0 0 0 1).  flags:
+ *   PLF_TRACK_MOTION_VELOCITY: velocity[f] (16 floats) = Tcw_cur * LastTwc, LastTwc = eye with GetRotationInverse() (Rcw^T) and
+ *     GetCameraCenter() (Ow) of last_frustum[f] copied in (so@0x4f42f-0x4f860).
+ *   PLF_TRACK_MOTION_LASTPOSE: last_out[f] = tlr[f] * tref[f] (UpdateLastFrame's SetPose, so@0x4e670-0x4e763), last_frustum_out optional.
+ *   PLF_TRACK_MOTION_PREDICT: pose_pred[f] = velocity[f] * Tcw_last (so@0x4edd2-0x4ee71), frustum_pred optional; Tcw_last = last_out[f] when
+ *     PLF_TRACK_MOTION_LASTPOSE is set, else last[f]; velocity is the one just written under PLF_TRACK_MOTION_VELOCITY, else read.
+ * status[f] = PLF_TRACK_NONFINITE when a written pose or velocity entry is not finite.  A flag's arrays may be NULL when it is not set. */
+enum { PLF_TRACK_MOTION_VELOCITY = 1, PLF_TRACK_MOTION_PREDICT = 2, PLF_TRACK_MOTION_LASTPOSE = 4 };
+int plf_track_motion(int32_t flags, int32_t n_frames, const plf_pose34 *cur, const plf_frustum_pose *last_frustum, float *velocity,
+                     const plf_pose34 *last, const plf_pose34 *tlr, const plf_pose34 *tref, plf_pose34 *last_out,
+                     plf_frustum_pose *last_frustum_out, plf_pose34 *pose_pred, plf_frustum_pose *frustum_pred, int32_t *status,
+                     int32_t device, void *stream);
+
+/* The match clean-ups of Track(), one elementwise kernel, in place:
+ *   PLF_TRACK_CLEAN_VO ("Clean VO matches", so@0x4f8a0-0x4f927): a matched key point whose point has Observations() < 1 (or is no point of
+ *     the map) gets match_of_kp = -1 and outlier = 0.  n_obs is required.
+ *   PLF_TRACK_CLEAN_OUTLIERS (after the key-frame decision, so@0x4fd99-0x4fde9): a matched key point with outlier != 0 gets match_of_kp = -1;
+ *     the flag stays. */
+enum { PLF_TRACK_CLEAN_VO = 0, PLF_TRACK_CLEAN_OUTLIERS = 1 };
+int plf_track_clean(int32_t mode, int32_t *match_of_kp, uint8_t *outlier, const int32_t *n_device, int32_t n_host, int32_t n_frames,
+                    int32_t kp_stride, const int32_t *row_id, int32_t id_stride, const int32_t *n_obs, int32_t n_points, int32_t device,
+                    void *stream);
+
 #ifdef __cplusplus
 }
 #endif

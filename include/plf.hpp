@@ -702,6 +702,50 @@ private:
     int n_rows_, kf_stride_, item_stride_, device_;
 };
 
+// The tail of Tracking::Track() over arrays the caller keeps on the device (include/plf.h, "Tracking tail"), stateless, any number of frames per call;
+// every call only enqueues on `stream`.  Names follow the reference's members; points only, as the binary.
+struct Tracking {
+    // bool Tracking::NeedNewKeyFrame() (so@0x49750): counts (n_frames x 3: nTotal, nMap, nRefMatches) and decision (0 no, 1 insert, 2 the mapper is busy)
+    static void NeedNewKeyFrame(const plf_track_view &v, const plf_track_kf_view &kf, const plf_track_kf_state *state_dev, const int32_t *mnMatchesInliers_dev,
+                                float mThDepth, int32_t *counts_dev, int32_t *decision_dev, int device = 0, void *stream = nullptr)
+    {
+        check(plf_track_need_keyframe(&v, &kf, state_dev, mnMatchesInliers_dev, mThDepth, counts_dev, decision_dev, device, stream), "Tracking::NeedNewKeyFrame");
+    }
+    // the point loop of void Tracking::CreateNewKeyFrame() (so@0x4e040): mvpMapPoints[new_kp] = id_base + k in place (v.match_of_kp is written)
+    static void CreateNewKeyFrame(const plf_track_view &v, const plf_camera &cam, float mThDepth, const int32_t *id_base_dev, int new_stride, int32_t *new_kp_dev,
+                                  float *new_pos_dev, int32_t *n_new_dev, int32_t *n_walked_dev, int32_t *status_dev, int device = 0, void *stream = nullptr,
+                                  int min_points = 100)
+    {
+        const plf_track_close_params p = {mThDepth, min_points, id_base_dev ? PLF_TRACK_CLOSE_KEYFRAME : PLF_TRACK_CLOSE_LIST, new_stride};
+        check(plf_track_close_points(&v, &cam, &p, id_base_dev, nullptr, new_kp_dev, new_pos_dev, n_new_dev, n_walked_dev, status_dev, device, stream),
+              "Tracking::CreateNewKeyFrame");
+    }
+    // the temporal points of void Tracking::UpdateLastFrame() (so@0x4e570) into the arrays behind a plf_lastframe_view
+    static void UpdateLastFrame(const plf_track_view &v, const plf_camera &cam, float mThDepth, const plf_track_lastframe_out &last, int new_stride, int32_t *new_kp_dev,
+                                float *new_pos_dev, int32_t *n_new_dev, int32_t *n_walked_dev, int32_t *status_dev, int device = 0, void *stream = nullptr,
+                                int min_points = 100)
+    {
+        const plf_track_close_params p = {mThDepth, min_points, PLF_TRACK_CLOSE_LASTFRAME, new_stride};
+        check(plf_track_close_points(&v, &cam, &p, nullptr, &last, new_kp_dev, new_pos_dev, n_new_dev, n_walked_dev, status_dev, device, stream),
+              "Tracking::UpdateLastFrame");
+    }
+    // mVelocity = mCurrentFrame.mTcw * LastTwc, SetPose(Tlr * pRef->GetPose()), SetPose(mVelocity * mLastFrame.mTcw): the products `flags` names
+    static void MotionModel(int flags, int n_frames, const plf_pose34 *cur, const plf_frustum_pose *last_frustum, float *mVelocity, const plf_pose34 *last,
+                            const plf_pose34 *Tlr, const plf_pose34 *Tref, plf_pose34 *last_out, plf_frustum_pose *last_frustum_out, plf_pose34 *pose_pred,
+                            plf_frustum_pose *frustum_pred, int32_t *status_dev, int device = 0, void *stream = nullptr)
+    {
+        check(plf_track_motion(flags, n_frames, cur, last_frustum, mVelocity, last, Tlr, Tref, last_out, last_frustum_out, pose_pred, frustum_pred, status_dev, device,
+                               stream), "Tracking::MotionModel");
+    }
+    // "Clean VO matches" (PLF_TRACK_CLEAN_VO) and the outlier matches nulled after the key-frame decision (PLF_TRACK_CLEAN_OUTLIERS)
+    static void CleanMatches(int mode, int32_t *mvpMapPoints_dev, uint8_t *mvbOutlier_dev, const int32_t *n_dev, int n_host, int n_frames, int kp_stride,
+                             const int32_t *row_id, int id_stride, const int32_t *n_obs, int n_points, int device = 0, void *stream = nullptr)
+    {
+        check(plf_track_clean(mode, mvpMapPoints_dev, mvbOutlier_dev, n_dev, n_host, n_frames, kp_stride, row_id, id_stride, n_obs, n_points, device, stream),
+              "Tracking::CleanMatches");
+    }
+};
+
 }  // namespace plf
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -1689,6 +1733,114 @@ struct Optimizer {
             for (int c = 0; c < 4; c++) Tcw.template at<float>(r, c) = r < 3 ? pout.Tcw[4 * r + c] : (c == 3 ? 1.0f : 0.0f);
         pFrame->SetPose(Tcw);
         return dn.download()[0];
+    }
+};
+
+// Tracking::NeedNewKeyFrame (so@0x49750) and the point loops of Tracking::CreateNewKeyFrame (so@0x4e040) / Tracking::UpdateLastFrame (so@0x4e570) over the
+// reference's own Tracking / Frame / KeyFrame / MapPoint.  Single-frame: each uploads, waits and writes back; a tracker with its frames resident calls the
+// plf_track_* entry points on all of them at once and reads nothing back.  The MapPoints are made on the host, by the caller's `make(x3D, i)`, in the
+// device's order (the order of the reference's walk), so that ids (MapPoint::nNextId) come out as the reference's.
+struct Tracking {
+    template <class TrackingT> static bool NeedNewKeyFrame(TrackingT *t, int device = 0)
+    {
+        auto &F = t->mCurrentFrame;
+        const int N = std::max(F.N, 1);
+        std::vector<float> depth(N, 0.0f);
+        std::vector<int32_t> match(N, -1), n_obs, row_start(2, 0), row_item;
+        std::vector<uint8_t> bad;
+        std::unordered_map<const void *, int32_t> ids;
+        auto id_of = [&](auto *pMP) {
+            auto it = ids.find(pMP);
+            if (it != ids.end()) return it->second;
+            const int32_t id = (int32_t)n_obs.size();
+            ids.emplace(pMP, id);
+            n_obs.push_back(pMP->Observations());
+            bad.push_back(pMP->isBad() ? 1 : 0);
+            return id;
+        };
+        for (int i = 0; i < F.N; i++) {
+            depth[i] = F.mvDepth[i];
+            if (F.mvpMapPoints[i]) match[i] = id_of(F.mvpMapPoints[i]);
+        }
+        if (t->mpReferenceKF)
+            for (auto *pMP : t->mpReferenceKF->GetMapPointMatches()) row_item.push_back(pMP ? id_of(pMP) : -1);
+        row_start[1] = (int32_t)row_item.size();
+        if (row_item.empty()) row_item.push_back(-1);
+        if (n_obs.empty()) { n_obs.push_back(0); bad.push_back(0); }
+        plf_track_kf_state s = {};
+        s.frame_id = (int64_t)F.mnId; s.ref_kf = t->mpReferenceKF ? 0 : -1; s.n_matches_inliers = t->mnMatchesInliers;
+        s.last_kf_id = (uint32_t)t->mnLastKeyFrameId; s.last_reloc_frame_id = (uint32_t)t->mnLastRelocFrameId;
+        s.min_frames = t->mMinFrames; s.max_frames = t->mMaxFrames; s.n_kfs = (int32_t)t->mpMap->KeyFramesInMap();
+        const bool stopped = t->mpLocalMapper->isStopped() || t->mpLocalMapper->stopRequested();
+        const bool idle = t->mpLocalMapper->AcceptKeyFrames();
+        s.flags = (t->mbOnlyTracking ? PLF_TRACK_ONLY_TRACKING : 0) | (stopped ? PLF_TRACK_MAPPER_STOPPED : 0) | (idle ? PLF_TRACK_MAPPER_IDLE : 0) |
+                  (t->mSensor == 0 ? PLF_TRACK_MONO : 0);
+        plf::DeviceArray<float> ddepth(depth, device);
+        plf::DeviceArray<int32_t> dmatch(match, device), dobs(n_obs, device), dstart(row_start, device), ditem(row_item, device), dcounts(3, device), ddec(1, device);
+        plf::DeviceArray<uint8_t> dbad(bad, device);
+        plf::DeviceArray<plf_track_kf_state> dstate(std::vector<plf_track_kf_state>(1, s), device);
+        plf_track_view v = {};
+        v.n_frames = 1; v.kp_stride = N; v.depth = ddepth.get(); v.match_of_kp = dmatch.get(); v.n_host = F.N > 0 ? F.N : 0; v.n_obs = dobs.get();
+        v.n_points = (int32_t)n_obs.size();
+        const plf_track_kf_view kf = {dstart.get(), ditem.get(), 1, dbad.get()};
+        plf::Tracking::NeedNewKeyFrame(v, kf, dstate.get(), nullptr, t->mThDepth, dcounts.get(), ddec.get(), device);
+        const int decision = ddec.download()[0];                 // a NULL-stream download waits for the device first
+        if (decision != 2) return decision == 1;
+        t->mpLocalMapper->InterruptBA();                         // thread state: the host's (so@0x49a50-0x49aa5)
+        return t->mSensor != 0 && t->mpLocalMapper->KeyframesInQueue() < 3;
+    }
+
+    // the loop of CreateNewKeyFrame after UpdatePoseMatrices: F.mvpMapPoints[i] = make(x3D, i) for the created key points, in order; returns their number
+    template <class FrameT, class Make> static int CreateNewKeyFrame(FrameT &F, float mThDepth, Make make, int device = 0, int min_points = 100)
+    {
+        return ClosePoints(F, mThDepth, make, device, min_points);
+    }
+    // the loop of UpdateLastFrame over mLastFrame (the guard and SetPose(Tlr * pRef->GetPose()) are the caller's; make() also keeps mlpTemporalPoints)
+    template <class FrameT, class Make> static int UpdateLastFrame(FrameT &F, float mThDepth, Make make, int device = 0, int min_points = 100)
+    {
+        return ClosePoints(F, mThDepth, make, device, min_points);
+    }
+
+private:
+    template <class FrameT, class Make> static int ClosePoints(FrameT &F, float mThDepth, Make make, int device, int min_points)
+    {
+        const int N = F.N;
+        if (N <= 0) return 0;
+        if (N > 16384) throw std::invalid_argument("Tracking: more than 16384 key points");
+        std::vector<plf_keypoint> keys(N);
+        std::vector<float> depth(N);
+        std::vector<int32_t> match(N, -1), n_obs(N, 0);
+        for (int i = 0; i < N; i++) {
+            const cv::KeyPoint &kp = F.mvKeysUn[i];
+            keys[i] = plf_keypoint{kp.pt.x, kp.pt.y, kp.size, kp.angle, kp.response, kp.octave, kp.class_id};
+            depth[i] = F.mvDepth[i];
+            if (F.mvpMapPoints[i]) { match[i] = i; n_obs[i] = F.mvpMapPoints[i]->Observations(); }
+        }
+        plf_frustum_pose fp = {};
+        const cv::Mat Rwc = F.GetRotationInverse(), Ow = F.GetCameraCenter();
+        for (int r = 0; r < 3; r++) {
+            for (int c = 0; c < 3; c++) fp.Rcw[3 * r + c] = Rwc.template at<float>(c, r);
+            fp.Ow[r] = Ow.template at<float>(r);
+        }
+        plf_camera cam = {};
+        cam.fx = F.fx; cam.fy = F.fy; cam.cx = F.cx; cam.cy = F.cy; cam.bf = F.mbf;
+        plf::DeviceArray<plf_keypoint> dkeys(keys, device);
+        plf::DeviceArray<float> ddepth(depth, device), dpos((size_t)N * 3, device);
+        plf::DeviceArray<int32_t> dmatch(match, device), dobs(n_obs, device), dkp(N, device), dn(3, device);
+        plf::DeviceArray<plf_frustum_pose> dfp(std::vector<plf_frustum_pose>(1, fp), device);
+        plf_track_view v = {};
+        v.n_frames = 1; v.kp_stride = N; v.keys_un = dkeys.get(); v.depth = ddepth.get(); v.match_of_kp = dmatch.get(); v.n_host = N; v.n_obs = dobs.get();
+        v.n_points = N; v.pose = dfp.get();
+        plf::Tracking::CreateNewKeyFrame(v, cam, mThDepth, nullptr, N, dkp.get(), dpos.get(), dn.get(), dn.get() + 1, dn.get() + 2, device, nullptr, min_points);
+        const int n_new = dn.download()[0];                      // a NULL-stream download waits for the device first
+        const std::vector<int32_t> kp = dkp.download();
+        const std::vector<float> pos = dpos.download();
+        for (int k = 0; k < n_new; k++) {
+            cv::Mat x3D(3, 1, CV_32F);
+            for (int r = 0; r < 3; r++) x3D.template at<float>(r, 0) = pos[3 * (size_t)k + r];
+            F.mvpMapPoints[kp[k]] = make(x3D, kp[k]);
+        }
+        return n_new;
     }
 };
 }  // namespace ORB_SLAM2_PLF

@@ -18,3 +18,5 @@ from . import localmap  # noqa: F401
 from .localmap import local_keyframes, local_items, local_gather, local_visible, update_local_map, children_csr, LocalMap  # noqa: F401
 from . import pose  # noqa: F401
 from .pose import pose_optimization, pose_commit, PoseResult  # noqa: F401
+from . import track  # noqa: F401
+from .track import close_points, need_new_keyframe, motion_model, clean_matches, kf_state  # noqa: F401

@@ -327,3 +327,41 @@ def pose_prototypes(l):
     l.plf_pose_optimize.argtypes = [C.POINTER(PoseView), C.POINTER(Camera), P, I, P, P, P, P, P, I, P]
     l.plf_pose_commit.argtypes = [I, P, P, P, I, I, I, P, I, P, I, P, P, I, P]
     return l
+
+
+# ---- tracking tail (include/plf.h, "Tracking tail")
+TRACK_OVERFLOW, TRACK_NONFINITE = 1, 1
+TRACK_CLOSE_LIST, TRACK_CLOSE_KEYFRAME, TRACK_CLOSE_LASTFRAME = 0, 1, 2
+TRACK_ONLY_TRACKING, TRACK_MAPPER_STOPPED, TRACK_MAPPER_IDLE, TRACK_MONO = 1, 2, 4, 8
+TRACK_MOTION_VELOCITY, TRACK_MOTION_PREDICT, TRACK_MOTION_LASTPOSE = 1, 2, 4
+TRACK_CLEAN_VO, TRACK_CLEAN_OUTLIERS = 0, 1
+TRACK_KF_STATE_DTYPE = np.dtype([("frame_id", "<i8"), ("ref_kf", "<i4"), ("n_matches_inliers", "<i4"), ("last_kf_id", "<u4"),
+                                 ("last_reloc_frame_id", "<u4"), ("min_frames", "<i4"), ("max_frames", "<i4"), ("n_kfs", "<i4"), ("flags", "<i4")])
+
+
+class TrackView(C.Structure):
+    _fields_ = [("n_frames", C.c_int32), ("kp_stride", C.c_int32), ("keys_un", C.c_void_p), ("depth", C.c_void_p), ("match_of_kp", C.c_void_p),
+                ("n_device", C.c_void_p), ("n_host", C.c_int32), ("row_id", C.c_void_p), ("id_stride", C.c_int32), ("n_obs", C.c_void_p),
+                ("n_points", C.c_int32), ("pose", C.c_void_p)]
+
+
+class TrackCloseParams(C.Structure):
+    _fields_ = [("th_depth", C.c_float), ("min_points", C.c_int32), ("mode", C.c_int32), ("new_stride", C.c_int32)]
+
+
+class TrackLastFrameOut(C.Structure):
+    _fields_ = [("has_mappoint", C.c_void_p), ("world_pos", C.c_void_p), ("obs_positive", C.c_void_p)]
+
+
+class TrackKfView(C.Structure):
+    _fields_ = [("kf_row_start", C.c_void_p), ("kf_row_item", C.c_void_p), ("n_kf", C.c_int32), ("item_bad", C.c_void_p)]
+
+
+def track_prototypes(l):
+    P, I = C.c_void_p, C.c_int32
+    l.plf_track_close_points.argtypes = [C.POINTER(TrackView), C.POINTER(Camera), C.POINTER(TrackCloseParams), P, C.POINTER(TrackLastFrameOut),
+                                         P, P, P, P, P, I, P]
+    l.plf_track_need_keyframe.argtypes = [C.POINTER(TrackView), C.POINTER(TrackKfView), P, P, C.c_float, P, P, I, P]
+    l.plf_track_motion.argtypes = [I, I, P, P, P, P, P, P, P, P, P, P, P, I, P]
+    l.plf_track_clean.argtypes = [I, P, P, P, I, I, I, P, I, P, I, I, P]
+    return l
