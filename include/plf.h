@@ -1395,6 +1395,104 @@ int plf_track_clean(int32_t mode, int32_t *match_of_kp, uint8_t *outlier, const 
                     int32_t kp_stride, const int32_t *row_id, int32_t id_stride, const int32_t *n_obs, int32_t n_points, int32_t device,
                     void *stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * New map points -- the loop body of void LocalMapping::CreateNewMapPoints() include/LocalMapping.h (so@0x5ce60) between the match list
+ * plf_match_triangulation writes and the new points plf_map_distinctive_descriptors / plf_map_update_normal_depth read.  Any number of jobs per
+ * call; a job is one (current keyframe, neighbour keyframe) pair over the keyframes resident as the map stages keep them.  Points only: the
+ * binary exports no CreateNewMapLines.
+ *
+ * The definition is tests/triref.py, one float32 / float64 operation per statement.  From the binary, per pair (i1, i2 = match12[i1]):
+ *  1. xn = ((u - cx) * invfx, (v - cy) * invfy, 1) (so@0x5d9b6-0x5d9db, 0x5e15b-0x5e1f9; invfx = 1.0f / fx, a stored float), ray = Rwc * xn for both
+ *     key points (so@0x5e8da, 0x5e9cc), cosParallaxRays = (float)(ray1.dot(ray2) / (cv::norm(ray1) * cv::norm(ray2))), the quotient in double
+ *     (so@0x5eae4-0x5eb99).
+ *  2. cosParallaxStereo = cosParallaxRays + 1 (so@0x5eb9d) and both stereo cosines start there.  bStereo1 = mvuRight[i1] >= 0 (a NaN is not):
+ *     cosParallaxStereo1 = cosf(2 * atan2f(0.5f * mb, mvDepth[i1])) (so@0x5ebb2-0x5ebf5); ELSE bStereo2: the same of keyframe 2
+ *     (so@0x611b0-0x61205) -- as upstream, the second is only taken when the first key point is monocular.  cosParallaxStereo = the second when it is
+ *     smaller than the first, else the first (vminss, so@0x5ec0e).
+ *  3. cosParallaxRays < cosParallaxStereo && cosParallaxRays > 0 && (bStereo1 || bStereo2 || (double)cosParallaxRays < 0.9998 [double, so@0x126698])
+ *     (so@0x5ec62-0x5ecde): the linear triangulation.  A (4x4 CV_32F) = xn1.x * Tcw1.row(2) - Tcw1.row(0), xn1.y * Tcw1.row(2) - Tcw1.row(1), and the
+ *     same of keyframe 2; cv::SVD::compute(A, w, u, vt, MODIFY_A | FULL_UV) (so@0x5fe0c); x3D = vt.row(3); x3D[3] == 0: the pair is left
+ *     (so@0x5ffb1; a NaN is not zero); x3D = x3D.rowRange(0, 3) / x3D[3] (so@0x60039).
+ *     Else bStereo1 && cosParallaxStereo1 < cosParallaxStereo2: KeyFrame::UnprojectStereo(i1) of keyframe 1 (so@0x61146, body so@0x9a9b0: as
+ *     Frame::UnprojectStereo above); else bStereo2 && cosParallaxStereo2 < cosParallaxStereo1: of keyframe 2 (so@0x61162); else the pair is left.
+ *  4. z1 = (float)(tcw1[2] + Rcw1.row(2).dot(x3D)) [double sum] <= 0: left (so@0x6032e); z2 likewise (so@0x604ce).  A NaN passes.
+ *  5. x1, y1 as z1; invz1 = 1.0f / z1 (vdivss, so@0x606cd); u1 = fmaf(fx * x1, invz1, cx), v1 = fmaf(fy * y1, invz1, cy) -- THE BINARY FUSES these and
+ *     the sums below (vfmadd213ss so@0x60702, 0x6070f; upstream's source has plain mul / add) --; errX1 = u1 - kp1.x, errY1 = v1 - kp1.y.  Monocular
+ *     key point: (double)fmaf(errX1, errX1, errY1 * errY1) > 5.991 * (double)sigma2 (so@0x61e43-0x61e66): left.  Stereo: u1_r = fmaf(-invz1, mbf, u1)
+ *     (vfnmadd132ss so@0x6072b), errX1_r = u1_r - mvuRight[i1], (double)fmaf(errX1_r, errX1_r, fmaf(errX1, errX1, errY1 * errY1)) > 7.8 * (double)sigma2
+ *     (so@0x6073c-0x60760): left.  sigma2 = mvLevelSigma2[kp.octave].  Then the same in keyframe 2 (so@0x6095c-0x609f1).  mbf is the current
+ *     keyframe's for both.
+ *  6. dist1 = (float)cv::norm(x3D - Ow1), dist2 likewise (so@0x60a1d-0x60ca6); dist1 == 0 || dist2 == 0: left (so@0x60cb2-0x60ccc).
+ *     ratioDist = dist2 / dist1, ratioOctave = mvScaleFactors[kp1.octave] / mvScaleFactors[kp2.octave], ratioFactor = 1.5f * mfScaleFactor
+ *     (so@0x5d241-0x5d250); ratioOctave > ratioDist * ratioFactor || ratioDist > ratioOctave * ratioFactor: left (so@0x60d1d-0x60d2f).
+ *  7. new MapPoint(x3D, ...) (so@0x622c9).
+ * Before the pairs: baseline = (float)cv::norm(Ow2 - Ow1); pKF2->mb > baseline skips the neighbour (so@0x5d400-0x5d438; a non-monocular sensor;
+ * the monocular ComputeSceneMedianDepth test, so@0x62042, is out of scope).  nn of GetBestCovisibilityKeyFrames is 10 for a non-monocular sensor.
+ * The binary agrees with upstream ORB-SLAM2 in control flow and constants; it DIFFERS in the fused operations of step 5.
+ * DEVIATION: KeyFrame::UnprojectStereo returns an empty matrix for mvDepth <= 0, on which the reference's next statement throws; here such a pair
+ * is left with PLF_TRI_NO_BRANCH.  A key-point octave outside [0, nlevels) is clamped to it (the reference reads out of bounds).
+ * The OpenCV 3.3 routines behind the PLT are not in the snapshot; restated [UPSTREAM] and PARITY UNPINNED, as at plf_map_update_normal_depth:
+ *  - a - b on CV_32F: one float subtraction per element; cv::norm: a double sum of squares in element order, a double square root;
+ *    cv::Mat::dot on CV_32F: a double sum of double products in element order; Mat / double: x * (float)(1.0 / w) + 0.0f.
+ *  - cv::gemm's small-matrix float path for Rwc * xn (a float sum of the products from the left, as the tracking tail has it).
+ *  - s * row - row (MatOp_AddEx to cv::addWeighted): (a * s + b * -1.0f) + 0.0f per element, in float.
+ *  - cv::SVD::compute on 4x4 CV_32F as OpenCV 3.3's JacobiSVDImpl_<float>: one-sided Jacobi on the transposed copy, squared row norms and the
+ *    products p in double, pairs i < j skipped for |p| <= 2 FLT_EPSILON sqrt(a b), gamma = hypot(2 p, a - b), c and s narrowed to float, rows of At
+ *    and Vt rotated in float without FMA, at most 30 sweeps, norms recomputed, selection sort in descending order.  Whether the binary's OpenCV ran
+ *    its SIMD partial sums or LAPACK here cannot be known: the association inside the SVD is fixed by tests/triref.py.
+ *  - hypot: glibc 2.35's algorithm without FMA (a square root and one correction step), restated in plf_math.h; sqrt is correctly rounded.
+ * atan2f and cosf are glibc's float routines restated operation by operation (plf_math.h), bit-equal to glibc 2.35 (tests/test_tri_ref.py).
+ *
+ * Keyframe slot s: kf_keys[s] (mvKeysUn), kf_uright[s] (mvuRight), kf_depth[s] (mvDepth), kf_n[s] key points, kf_pose[s].  Job j: slots
+ * job_kf1[j] (the current keyframe) and job_kf2[j]; match12 + j * kp_stride: the array plf_match_triangulation wrote (< 0: no pair); i1 runs over
+ * [0, min(kf_n[kf1], kp_stride)).  Outputs of job j at j * new_stride: new_i1 / new_i2 / new_pos[.., 0..3) of the k-th created point, in ascending
+ * i1 -- the order of vMatchedPairs and of the reference's new MapPoint calls --, for k < new_stride; n_new[j] the TRUE count; status[j] a mask of
+ * PLF_TRI_OVERFLOW (n_new > new_stride), PLF_TRI_SKIPPED_BASELINE, PLF_TRI_BAD_SLOT (a slot outside [0, n_kf)); a skipped job writes n_new = 0 and
+ * its status only.  reason[j * kp_stride + i1] (uint8): PLF_TRI_* below in the low four bits, one value per exit of the loop, and in
+ * bits 4-5 the branch that gave the position (0 when none was reached).
+ * Optional marks (marks may be NULL, and each table in it), applied to the entries k < new_stride only: kf_has_mp[kf1][i1] = kf_has_mp[kf2][i2] = 1 in
+ * the has_mp arrays plf_match_triangulation reads, so that the next neighbour's search, enqueued behind this call, sees what AddMapPoint would have
+ * done; kf_mappoints[kf1][i1] = kf_mappoints[kf2][i2] = id_base[j] + k (the keyframes' mvpMapPoints rows).
+ * A row of match12 names each i2 at most once, as SearchForTriangulation leaves it (vbMatched2); were one named twice, its mappoints mark would be either pair's.
+ * Every job is judged on the state at entry; jobs of one call do not see each other's marks, and the CALLER sees to it that the jobs of one call
+ * do not name the same key point twice (two jobs with one current keyframe would).  The reference's neighbour loop of one keyframe is ten
+ * (plf_match_triangulation, plf_triangulate_points) pairs enqueued in order; a caller with many new keyframes puts neighbour r of all into call r.
+ * Stateless; every array is DEVICE memory (the structs themselves are host); asynchronous on `stream`; nothing is read back; no scratch.
+ * PLF_E_BADARG before any device work: a NULL required array, negative sizes, strides < 1, nlevels < 1, kf_mappoints without id_base.  NaN / Inf
+ * values, slots out of range and match12 entries >= kf_n[kf2] fault nowhere.
+ * One launch, one workgroup of 256 per job, the key points in chunks of 256: every lane classifies its pair, the pairs of the SVD branch are
+ * compacted into LDS and solved on dense lanes, the created entries are numbered by a ballot inside the wave and a scan across waves and chunks.
+ * ---------------------------------------------------------------------------------------------- */
+enum { PLF_TRI_OVERFLOW = 1, PLF_TRI_SKIPPED_BASELINE = 2, PLF_TRI_BAD_SLOT = 4 };
+enum { PLF_TRI_NO_PAIR = 1, PLF_TRI_CREATED = 2, PLF_TRI_NO_BRANCH = 3, PLF_TRI_W_ZERO = 4, PLF_TRI_Z1 = 5, PLF_TRI_Z2 = 6, PLF_TRI_REPROJ1 = 7,
+       PLF_TRI_REPROJ2 = 8, PLF_TRI_ZERO_DIST = 9, PLF_TRI_SCALE = 10, PLF_TRI_BAD_I2 = 11,
+       PLF_TRI_BRANCH_SVD = 0x10, PLF_TRI_BRANCH_KF1 = 0x20, PLF_TRI_BRANCH_KF2 = 0x30, PLF_TRI_BRANCH_MASK = 0x30 };
+typedef struct {
+    int32_t n_kf;
+    const plf_keypoint *const *kf_keys;                   /* n_kf device pointers (plf_map_geom_view.kf_keys) */
+    const float *const *kf_uright;                        /* n_kf device pointers */
+    const float *const *kf_depth;                         /* n_kf device pointers */
+    const int32_t *kf_n;                                  /* n_kf */
+    const plf_frustum_pose *kf_pose;                      /* n_kf: Rcw, tcw, Ow */
+    const float *scale_factors, *level_sigma2;            /* nlevels each: mvScaleFactors, mvLevelSigma2 */
+    int32_t nlevels;
+    float scale_factor;                                   /* mfScaleFactor */
+    float mb, mbf;
+} plf_triangulate_view;
+typedef struct {
+    int32_t n_jobs, kp_stride, new_stride;
+    const int32_t *job_kf1, *job_kf2;                     /* n_jobs */
+    const int32_t *match12;                               /* n_jobs x kp_stride */
+} plf_triangulate_jobs;
+typedef struct {
+    uint8_t *const *kf_has_mp;                            /* optional: n_kf device pointers */
+    int32_t *const *kf_mappoints;                         /* optional: n_kf device pointers */
+    const int32_t *id_base;                               /* n_jobs, with kf_mappoints */
+} plf_triangulate_marks;
+int plf_triangulate_points(const plf_triangulate_view *v, const plf_camera *cam, const plf_triangulate_jobs *jobs, const plf_triangulate_marks *marks,
+                           int32_t *new_i1, int32_t *new_i2, float *new_pos, int32_t *n_new, int32_t *status, uint8_t *reason, int32_t device,
+                           void *stream);
+
 #ifdef __cplusplus
 }
 #endif

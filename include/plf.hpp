@@ -746,6 +746,22 @@ struct Tracking {
     }
 };
 
+// The loop body of void LocalMapping::CreateNewMapPoints() (so@0x5ce60) over keyframes the caller keeps on the device (include/plf.h, "New map points"),
+// stateless, any number of (current keyframe, neighbour) jobs per call; the call only enqueues on `stream`.  match12 is what
+// ORBmatcher::SearchForTriangulation wrote; with `marks` the next neighbour's search, enqueued behind this call, sees the new points.
+struct Triangulator {
+    static void CreateNewMapPoints(const plf_triangulate_view &keyframes, const plf_camera &cam, const plf_triangulate_jobs &jobs, const plf_triangulate_marks *marks,
+                                   int32_t *new_i1_dev, int32_t *new_i2_dev, float *new_pos_dev, int32_t *n_new_dev, int32_t *status_dev, uint8_t *reason_dev,
+                                   int device = 0, void *stream = nullptr)
+    {
+        check(plf_triangulate_points(&keyframes, &cam, &jobs, marks, new_i1_dev, new_i2_dev, new_pos_dev, n_new_dev, status_dev, reason_dev, device, stream),
+              "LocalMapping::CreateNewMapPoints");
+    }
+    // one pair's outcome from its reason byte
+    static bool Created(uint8_t reason) { return (reason & 15) == PLF_TRI_CREATED; }
+    static int Branch(uint8_t reason) { return reason & PLF_TRI_BRANCH_MASK; }
+};
+
 }  // namespace plf
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -1841,6 +1857,147 @@ private:
             F.mvpMapPoints[kp[k]] = make(x3D, kp[k]);
         }
         return n_new;
+    }
+};
+
+// void LocalMapping::CreateNewMapPoints() (so@0x5ce60) over the reference's own KeyFrame / MapPoint, in the reference's order: GetBestCovisibilityKeyFrames(nn),
+// and per neighbour the caller's ComputeF12, plf_match_triangulation and plf_triangulate_points (which holds the baseline test) with the has_mp marks on, so that
+// neighbour r + 1 is searched over what neighbour r's pairs created; then, on the host and in the order of the reference's `new MapPoint` calls (neighbour by
+// neighbour, ascending idx1), make(x3D, pKF1, pKF2, idx1, idx2), which does new MapPoint / AddObservation x2 / AddMapPoint x2 / ComputeDistinctiveDescriptors /
+// UpdateNormalAndDepth / mpMap->AddMapPoint / mlpRecentAddedMapPoints.push_back and so hands out MapPoint::nNextId as the reference would.  No ids cross the
+// device: they are given after the last neighbour.  computeF12(pKF1, pKF2) returns the 3x3 CV_32F matrix.  Single-keyframe form: it uploads the keyframes, and
+// waits after each call because the matcher handle enqueues on a stream of its own; a mapper with its keyframes resident passes one stream to both calls and
+// waits once.  The monocular CheckNewKeyFrames() exit and ComputeSceneMedianDepth test are thread state and out of scope: RGB-D and stereo only.
+struct LocalMapping {
+    template <class KeyFrameT, class ComputeF12, class Make>
+    static int CreateNewMapPoints(KeyFrameT *mpCurrentKeyFrame, ComputeF12 computeF12, Make make, int device = 0, int nn = 10)
+    {
+        const std::vector<KeyFrameT *> vpNeighKFs = mpCurrentKeyFrame->GetBestCovisibilityKeyFrames(nn);
+        if (vpNeighKFs.empty()) return 0;
+        std::vector<KeyFrameT *> kfs(1, mpCurrentKeyFrame);
+        kfs.insert(kfs.end(), vpNeighKFs.begin(), vpNeighKFs.end());
+        const int K = (int)kfs.size(), J = K - 1;
+        struct Dev {
+            plf::DeviceArray<plf_keypoint> keys;
+            plf::DeviceArray<float> uright, depth;
+            plf::DeviceArray<uint8_t> desc, has_mp;
+            plf::DeviceArray<uint32_t> node_id;
+            plf::DeviceArray<int32_t> node_start, feat;
+            int n = 0, nodes = 0;
+        };
+        std::vector<Dev> d(K);
+        std::vector<plf_frustum_pose> poses(K);
+        std::vector<const plf_keypoint *> t_keys(K);
+        std::vector<const float *> t_ur(K), t_depth(K);
+        std::vector<uint8_t *> t_has(K);
+        std::vector<int32_t> t_n(K);
+        int max_n = 1;
+        for (int s = 0; s < K; s++) {
+            KeyFrameT *kf = kfs[s];
+            const int N = kf->N;
+            const size_t cap = (size_t)std::max(N, 1);
+            std::vector<plf_keypoint> keys(cap);
+            std::vector<float> ur(cap, -1.0f), dep(cap, -1.0f);
+            std::vector<uint8_t> desc(cap * 32, 0), has(cap, 0);
+            for (int i = 0; i < N; i++) {
+                const cv::KeyPoint &kp = kf->mvKeysUn[i];
+                keys[i] = plf_keypoint{kp.pt.x, kp.pt.y, kp.size, kp.angle, kp.response, kp.octave, kp.class_id};
+                ur[i] = kf->mvuRight[i];
+                dep[i] = kf->mvDepth[i];
+                has[i] = kf->GetMapPoint(i) ? 1 : 0;
+                std::memcpy(&desc[(size_t)i * 32], kf->mDescriptors.data + (size_t)i * kf->mDescriptors.step, 32);
+            }
+            std::vector<uint32_t> node_id;
+            std::vector<int32_t> node_start(1, 0), feat;
+            for (const auto &node : kf->mFeatVec) {
+                node_id.push_back((uint32_t)node.first);
+                for (unsigned int f : node.second) feat.push_back((int32_t)f);
+                node_start.push_back((int32_t)feat.size());
+            }
+            d[s].n = N; d[s].nodes = (int)node_id.size();
+            if (node_id.empty()) node_id.push_back(0);
+            if (feat.empty()) feat.push_back(0);
+            d[s].keys.reset(cap, device); d[s].keys.upload(keys.data(), cap);
+            d[s].uright.reset(cap, device); d[s].uright.upload(ur.data(), cap);
+            d[s].depth.reset(cap, device); d[s].depth.upload(dep.data(), cap);
+            d[s].desc.reset(cap * 32, device); d[s].desc.upload(desc.data(), cap * 32);
+            d[s].has_mp.reset(cap, device); d[s].has_mp.upload(has.data(), cap);
+            d[s].node_id.reset(node_id.size(), device); d[s].node_id.upload(node_id.data(), node_id.size());
+            d[s].node_start.reset(node_start.size(), device); d[s].node_start.upload(node_start.data(), node_start.size());
+            d[s].feat.reset(feat.size(), device); d[s].feat.upload(feat.data(), feat.size());
+            const cv::Mat Rcw = kf->GetRotation(), tcw = kf->GetTranslation(), Ow = kf->GetCameraCenter();
+            for (int r = 0; r < 3; r++) {
+                for (int c = 0; c < 3; c++) poses[s].Rcw[3 * r + c] = Rcw.template at<float>(r, c);
+                poses[s].tcw[r] = tcw.template at<float>(r, 0);
+                poses[s].Ow[r] = Ow.template at<float>(r, 0);
+            }
+            t_keys[s] = d[s].keys.get(); t_ur[s] = d[s].uright.get(); t_depth[s] = d[s].depth.get(); t_has[s] = d[s].has_mp.get(); t_n[s] = N;
+            max_n = std::max(max_n, N);
+        }
+        KeyFrameT *cur = mpCurrentKeyFrame;
+        const int N1 = std::max(cur->N, 1);
+        const std::vector<float> sf(cur->mvScaleFactors.begin(), cur->mvScaleFactors.end()), sg(cur->mvLevelSigma2.begin(), cur->mvLevelSigma2.end());
+        plf::DeviceArray<float> d_sf(sf, device), d_sg(sg, device);
+        plf::DeviceArray<const plf_keypoint *> d_keys(t_keys, device);
+        plf::DeviceArray<const float *> d_ur(t_ur, device), d_depth(t_depth, device);
+        plf::DeviceArray<uint8_t *> d_has(t_has, device);
+        plf::DeviceArray<int32_t> d_n(t_n, device), d_match((size_t)J * N1, device), d_cnt(1, device), d_i1((size_t)J * N1, device), d_i2((size_t)J * N1, device),
+            d_nnew(J, device), d_status(J, device);
+        plf::DeviceArray<plf_frustum_pose> d_pose(poses, device);
+        plf::DeviceArray<float> d_pos((size_t)J * N1 * 3, device);
+        plf::DeviceArray<uint8_t> d_reason((size_t)J * N1, device);
+        std::vector<int32_t> kf1(J, 0), kf2(J);
+        for (int j = 0; j < J; j++) kf2[j] = j + 1;
+        plf::DeviceArray<int32_t> d_kf1(kf1, device), d_kf2(kf2, device);
+        plf_matcher *m = nullptr;
+        plf::check(plf_matcher_create(device, max_n, 1024, 64, 1, &m), "plf_matcher_create");
+        struct Free { plf_matcher *m; ~Free() { plf_matcher_destroy(m); } } free_m{m};
+        plf_triangulate_view tv = {};
+        tv.n_kf = K; tv.kf_keys = d_keys.get(); tv.kf_uright = d_ur.get(); tv.kf_depth = d_depth.get(); tv.kf_n = d_n.get(); tv.kf_pose = d_pose.get();
+        tv.scale_factors = d_sf.get(); tv.level_sigma2 = d_sg.get(); tv.nlevels = (int32_t)sf.size(); tv.scale_factor = cur->mfScaleFactor;
+        tv.mb = cur->mb; tv.mbf = cur->mbf;
+        plf_camera cam = {};
+        cam.fx = cur->fx; cam.fy = cur->fy; cam.cx = cur->cx; cam.cy = cur->cy; cam.bf = cur->mbf;
+        plf_triangulate_marks marks = {d_has.get(), nullptr, nullptr};
+        const cv::Mat Ow1 = cur->GetCameraCenter();
+        const float Cw1[3] = {Ow1.template at<float>(0, 0), Ow1.template at<float>(1, 0), Ow1.template at<float>(2, 0)};
+        for (int j = 0; j < J; j++) {
+            KeyFrameT *pKF2 = kfs[j + 1];
+            const cv::Mat F12 = computeF12(cur, pKF2);
+            float F[9];
+            for (int r = 0; r < 3; r++)
+                for (int c = 0; c < 3; c++) F[3 * r + c] = F12.template at<float>(r, c);
+            plf_tri_view v = {};
+            v.n1 = d[0].n; v.n2 = d[j + 1].n;
+            v.keys1 = d[0].keys.get(); v.keys2 = d[j + 1].keys.get(); v.uright1 = d[0].uright.get(); v.uright2 = d[j + 1].uright.get();
+            v.desc1 = d[0].desc.get(); v.desc2 = d[j + 1].desc.get(); v.has_mp1 = d[0].has_mp.get(); v.has_mp2 = d[j + 1].has_mp.get();
+            v.nodes1 = d[0].nodes; v.nodes2 = d[j + 1].nodes; v.node_id1 = d[0].node_id.get(); v.node_id2 = d[j + 1].node_id.get();
+            v.node_start1 = d[0].node_start.get(); v.node_start2 = d[j + 1].node_start.get(); v.feat1 = d[0].feat.get(); v.feat2 = d[j + 1].feat.get();
+            v.scale_factors2 = d_sf.get(); v.level_sigma2_2 = d_sg.get();
+            plf_kf_pose p2 = {};
+            std::memcpy(p2.Rcw, poses[j + 1].Rcw, sizeof(p2.Rcw)); std::memcpy(p2.tcw, poses[j + 1].tcw, sizeof(p2.tcw)); std::memcpy(p2.Ow, poses[j + 1].Ow, sizeof(p2.Ow));
+            p2.fx = pKF2->fx; p2.fy = pKF2->fy; p2.cx = pKF2->cx; p2.cy = pKF2->cy; p2.bf = pKF2->mbf; p2.log_scale_factor = pKF2->mfLogScaleFactor;
+            p2.inv_level_sigma2 = pKF2->mvInvLevelSigma2.data();
+            // ORBmatcher matcher(0.6, false); matcher.SearchForTriangulation(mpCurrentKeyFrame, pKF2, F12, vMatchedIndices, false)
+            plf::check(plf_match_triangulation(m, &v, F, Cw1, &p2, 0, 0, d_match.get() + (size_t)j * N1, d_cnt.get(), nullptr), "SearchForTriangulation");
+            (void)d_cnt.download();                                  // waits: the handle's stream is its own
+            plf_triangulate_jobs jobs = {1, N1, N1, d_kf1.get() + j, d_kf2.get() + j, d_match.get() + (size_t)j * N1};
+            plf::Triangulator::CreateNewMapPoints(tv, cam, jobs, &marks, d_i1.get() + (size_t)j * N1, d_i2.get() + (size_t)j * N1, d_pos.get() + (size_t)j * N1 * 3,
+                                                  d_nnew.get() + j, d_status.get() + j, d_reason.get() + (size_t)j * N1, device, nullptr);
+            (void)d_cnt.download();                                  // waits: the next search reads the marks
+        }
+        const std::vector<int32_t> n_new = d_nnew.download(), i1 = d_i1.download(), i2 = d_i2.download();
+        const std::vector<float> pos = d_pos.download();
+        int nnew = 0;
+        for (int j = 0; j < J; j++)
+            for (int k = 0; k < n_new[j]; k++) {
+                const size_t o = (size_t)j * N1 + k;
+                cv::Mat x3D(3, 1, CV_32F);
+                for (int r = 0; r < 3; r++) x3D.template at<float>(r, 0) = pos[o * 3 + r];
+                make(x3D, cur, kfs[j + 1], i1[o], i2[o]);
+                nnew++;
+            }
+        return nnew;
     }
 };
 }  // namespace ORB_SLAM2_PLF

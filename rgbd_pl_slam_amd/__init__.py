@@ -20,3 +20,5 @@ from . import pose  # noqa: F401
 from .pose import pose_optimization, pose_commit, PoseResult  # noqa: F401
 from . import track  # noqa: F401
 from .track import close_points, need_new_keyframe, motion_model, clean_matches, kf_state  # noqa: F401
+from . import triangulate  # noqa: F401
+from .triangulate import triangulate_points, KeyFrameSet  # noqa: F401

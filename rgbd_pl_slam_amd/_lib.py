@@ -365,3 +365,32 @@ def track_prototypes(l):
     l.plf_track_motion.argtypes = [I, I, P, P, P, P, P, P, P, P, P, P, P, I, P]
     l.plf_track_clean.argtypes = [I, P, P, P, I, I, I, P, I, P, I, I, P]
     return l
+
+
+# ---- new map points (include/plf.h, "New map points")
+TRI_OVERFLOW, TRI_SKIPPED_BASELINE, TRI_BAD_SLOT = 1, 2, 4
+(TRI_NO_PAIR, TRI_CREATED, TRI_NO_BRANCH, TRI_W_ZERO, TRI_Z1, TRI_Z2, TRI_REPROJ1, TRI_REPROJ2, TRI_ZERO_DIST, TRI_SCALE, TRI_BAD_I2) = range(1, 12)
+TRI_BRANCH_SVD, TRI_BRANCH_KF1, TRI_BRANCH_KF2, TRI_BRANCH_MASK = 0x10, 0x20, 0x30, 0x30
+
+
+class TriangulateView(C.Structure):
+    _fields_ = [("n_kf", C.c_int32), ("kf_keys", C.c_void_p), ("kf_uright", C.c_void_p), ("kf_depth", C.c_void_p), ("kf_n", C.c_void_p),
+                ("kf_pose", C.c_void_p), ("scale_factors", C.c_void_p), ("level_sigma2", C.c_void_p), ("nlevels", C.c_int32),
+                ("scale_factor", C.c_float), ("mb", C.c_float), ("mbf", C.c_float)]
+
+
+class TriangulateJobs(C.Structure):
+    _fields_ = [("n_jobs", C.c_int32), ("kp_stride", C.c_int32), ("new_stride", C.c_int32), ("job_kf1", C.c_void_p), ("job_kf2", C.c_void_p),
+                ("match12", C.c_void_p)]
+
+
+class TriangulateMarks(C.Structure):
+    _fields_ = [("kf_has_mp", C.c_void_p), ("kf_mappoints", C.c_void_p), ("id_base", C.c_void_p)]
+
+
+def tri_prototypes(l, name="plf_triangulate_points"):
+    """the device call; name="tri_cpu_points": the host loop tools/tri_cpu.cpp, the same signature without device and stream"""
+    P, I = C.c_void_p, C.c_int32
+    tail = [I, P] if name == "plf_triangulate_points" else []
+    getattr(l, name).argtypes = [C.POINTER(TriangulateView), C.POINTER(Camera), C.POINTER(TriangulateJobs), C.POINTER(TriangulateMarks), P, P, P, P, P, P] + tail
+    return l

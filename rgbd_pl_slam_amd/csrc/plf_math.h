@@ -109,6 +109,118 @@ PLF_MATH void plf_sincosf_glibc(float y, float *sinp, float *cosp)
     if (n & 1) { *sinp = cv; *cosp = sv; } else { *sinp = sv; *cosp = cv; }
 }
 
+// cosf as the reference's libm computes it (glibc >= 2.28 s_cosf.c): the reduction and the two polynomials of sincosf above, the cosine taken.
+// LocalMapping::CreateNewMapPoints calls cosf@plt on 2 * atan2f(mb / 2, depth) (so@0x5ebf5).  Valid for 0 <= |y| < 120; bit-identical to glibc 2.35 on
+// every float of [0, 2 pi] (tests/test_tri_ref.py).
+PLF_MATH float plf_cosf_glibc(float y)
+{
+    float s, c;
+    plf_sincosf_glibc(y, &s, &c);
+    return c;
+}
+
+// atanf and atan2f as the reference's libm computes them (glibc 2.35 sysdeps/ieee754/flt-32/s_atanf.c, e_atan2f.c: the fdlibm float forms, Sun
+// Microsystems 1993, freely usable), operation by operation in float (no FMA).  CreateNewMapPoints calls atan2f@plt (so@0x5ebec, 0x611fc).
+PLF_MATH float plf_atanf_fdlibm(float x)
+{
+    const float hi0 = 4.6364760399e-01f, hi1 = 7.8539812565e-01f, hi2 = 9.8279368877e-01f, hi3 = 1.5707962513e+00f;
+    const float lo0 = 5.0121582440e-09f, lo1 = 3.7748947079e-08f, lo2 = 3.4473217170e-08f, lo3 = 7.5497894159e-08f;
+    const float a0 = 3.3333334327e-01f, a1 = -2.0000000298e-01f, a2 = 1.4285714924e-01f, a3 = -1.1111110449e-01f, a4 = 9.0908870101e-02f,
+                a5 = -7.6918758452e-02f, a6 = 6.6610731184e-02f, a7 = -5.8335702866e-02f, a8 = 4.9768779427e-02f, a9 = -3.6531571299e-02f,
+                a10 = 1.6285819933e-02f;
+    const uint32_t hx = __float_as_uint(x), ix = hx & 0x7fffffffu;
+    const bool neg = (hx >> 31) != 0;
+    int id;
+    if (ix >= 0x4c000000u) {                          // |x| >= 2^25
+        if (ix > 0x7f800000u) return x + x;           // NaN
+        return neg ? -hi3 - lo3 : hi3 + lo3;
+    }
+    if (ix < 0x3ee00000u) {                           // |x| < 0.4375
+        if (ix < 0x31000000u) return x;               // |x| < 2^-29
+        id = -1;
+    } else {
+        x = fabsf(x);
+        if (ix < 0x3f980000u) {                       // |x| < 1.1875
+            if (ix < 0x3f300000u) { id = 0; x = __fdiv_rn(2.0f * x - 1.0f, 2.0f + x); }
+            else { id = 1; x = __fdiv_rn(x - 1.0f, x + 1.0f); }
+        } else {
+            if (ix < 0x401c0000u) { id = 2; x = __fdiv_rn(x - 1.5f, 1.0f + 1.5f * x); }
+            else { id = 3; x = __fdiv_rn(-1.0f, x); }
+        }
+    }
+    const float z = x * x;
+    const float w = z * z;
+    const float s1 = z * (a0 + w * (a2 + w * (a4 + w * (a6 + w * (a8 + w * a10)))));
+    const float s2 = w * (a1 + w * (a3 + w * (a5 + w * (a7 + w * a9))));
+    if (id < 0) return x - x * (s1 + s2);
+    const float hi = id == 0 ? hi0 : id == 1 ? hi1 : id == 2 ? hi2 : hi3;
+    const float lo = id == 0 ? lo0 : id == 1 ? lo1 : id == 2 ? lo2 : lo3;
+    const float r = hi - ((x * (s1 + s2) - lo) - x);
+    return neg ? -r : r;
+}
+
+PLF_MATH float plf_atan2f_fdlibm(float y, float x)
+{
+    const float tiny = 1.0e-30f, pi_o_4 = 7.8539818525e-01f, pi_o_2 = 1.5707963705e+00f, pi = 3.1415927410e+00f, pi_lo = -8.7422776573e-08f;
+    const uint32_t hx = __float_as_uint(x), hy = __float_as_uint(y), ix = hx & 0x7fffffffu, iy = hy & 0x7fffffffu;
+    if (ix > 0x7f800000u || iy > 0x7f800000u) return x + y;                      // NaN
+    if (hx == 0x3f800000u) return plf_atanf_fdlibm(y);                           // x = 1.0
+    const int m = (int)((hy >> 31) & 1u) | (int)((hx >> 30) & 2u);               // 2 * sign(x) + sign(y)
+    if (iy == 0) return m < 2 ? y : m == 2 ? pi + tiny : -pi - tiny;
+    if (ix == 0) return (hy >> 31) ? -pi_o_2 - tiny : pi_o_2 + tiny;
+    if (ix == 0x7f800000u) {
+        if (iy == 0x7f800000u) return m == 0 ? pi_o_4 + tiny : m == 1 ? -pi_o_4 - tiny : m == 2 ? 3.0f * pi_o_4 + tiny : -3.0f * pi_o_4 - tiny;
+        return m == 0 ? 0.0f : m == 1 ? -0.0f : m == 2 ? pi + tiny : -pi - tiny;
+    }
+    if (iy == 0x7f800000u) return (hy >> 31) ? -pi_o_2 - tiny : pi_o_2 + tiny;
+    const int k = ((int)iy - (int)ix) >> 23;
+    float z;
+    if (k > 60) z = pi_o_2 + 0.5f * pi_lo;                                       // |y / x| > 2^60
+    else if ((hx >> 31) && k < -60) z = 0.0f;                                    // |y| / x < -2^60
+    else z = plf_atanf_fdlibm(fabsf(__fdiv_rn(y, x)));
+    if (m == 0) return z;
+    if (m == 1) return __uint_as_float(__float_as_uint(z) ^ 0x80000000u);
+    if (m == 2) return pi - (z - pi_lo);
+    return (z - pi_lo) - pi;
+}
+
+// hypot as glibc 2.35 computes it without FMA (sysdeps/ieee754/dbl-64/e_hypot.c: a square root and one correction step, after C. Borges, "An improved
+// algorithm for hypot(a, b)"), operation by operation in double: the gamma of cv::SVD's Jacobi rotation (tri_common.h).  sqrt is the correctly rounded
+// double square root on both sides.  Against this host's libm: tests/test_tri_ref.py.
+PLF_MATH double plf_hypot_kernel(double ax, double ay)
+{
+    double h = sqrt(ax * ax + ay * ay);
+    double t1, t2;
+    if (h <= 2.0 * ay) {
+        const double delta = h - ay;
+        t1 = ax * (2.0 * delta - ax);
+        t2 = (delta - 2.0 * (ax - ay)) * delta;
+    } else {
+        const double delta = h - ax;
+        t1 = 2.0 * delta * (ax - 2.0 * ay);
+        t2 = (4.0 * delta - ay) * ay + delta * delta;
+    }
+    h -= (t1 + t2) / (2.0 * h);
+    return h;
+}
+PLF_MATH double plf_hypot_glibc(double x, double y)
+{
+    const double inf = (double)__uint_as_float(0x7f800000u);
+    x = fabs(x); y = fabs(y);
+    if (!(x < inf) || !(y < inf)) return (x == inf || y == inf) ? inf : x + y;    // Inf wins over NaN
+    const double ax = x < y ? y : x, ay = x < y ? x : y;
+    if (ax > 0x1p+511) {
+        if (ay <= ax * 0x1p-54) return ax + ay;
+        return plf_hypot_kernel(ax * 0x1p-600, ay * 0x1p-600) / 0x1p-600;
+    }
+    if (ay < 0x1p-459) {
+        if (ax >= ay / 0x1p-54) return ax + ay;
+        return plf_hypot_kernel(ax / 0x1p-600, ay / 0x1p-600) * 0x1p-600;
+    }
+    if (ax >= ay / 0x1p-54) return ax + ay;
+    return plf_hypot_kernel(ax, ay);
+}
+
 // sin and cos of a double angle as ONE explicit sequence of IEEE double operations (no FMA, no libm call), so that the device (pose_kernels.hip:
 // the update angle of SE3Quat::exp), the host loop (tools/pose_cpu.cpp) and the definition (tests/poseref.py, through tests/cpp/pose_mathhost.cpp)
 // share the bits.  Valid on [0, 7); the pose routine calls it on [1e-5, ...), below that the exp map takes its series branch.  Reduction
