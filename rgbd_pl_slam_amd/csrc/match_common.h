@@ -7,6 +7,9 @@
 #define GRID_COLS 64
 #define GRID_ROWS 48
 #define GRID_CELLS (GRID_COLS * GRID_ROWS)
+// flat_walk reads the CSR offsets of WALK_COLS window columns per trip without clamping the last ones: the table of all frames ends in WALK_COLS columns
+// of padding (a frame's read-ahead lands in the next frame's row; what is read past the window is never used)
+#define WALK_COLS 4
 
 struct FrameDev {
     int n;
@@ -17,7 +20,7 @@ struct FrameDev {
     float min_x, min_y, max_x, max_y, inv_w, inv_h;
     const float *scale_factors;
     int nlevels;
-    const int *cell_start;  // GRID_CELLS + 1
+    const int *cell_start;  // GRID_CELLS + 1 (readable up to WALK_COLS columns further)
     const int *cell_idx;    // n
     const float4 *cell_kp;  // n: (x, y, octave, index) of the key points in cell order (cell_idx order)
 };

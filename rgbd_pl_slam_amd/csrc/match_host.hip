@@ -86,7 +86,7 @@ extern "C" int plf_matcher_create(int32_t device, int32_t max_keypoints, int32_t
     } while (0)
     ALLOC(h->d_frames, B * sizeof(FrameDev));
     ALLOC(h->d_lframes, B * sizeof(LineFrameDev));
-    ALLOC(h->d_cell_start, B * (GRID_CELLS + 1) * sizeof(int));
+    ALLOC(h->d_cell_start, (B * (GRID_CELLS + 1) + WALK_COLS * GRID_ROWS) * sizeof(int));   // (+ the read-ahead of flat_walk behind the last frame's row)
     ALLOC(h->d_cell_idx, B * (size_t)max_keypoints * sizeof(int));
     ALLOC(h->d_cell_of, B * (size_t)max_keypoints * sizeof(int));
     ALLOC(h->d_cell_kp, B * (size_t)max_keypoints * sizeof(float4));

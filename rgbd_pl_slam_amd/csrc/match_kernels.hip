@@ -210,7 +210,8 @@ __global__ void __launch_bounds__(256) k_match_project_points_slow(const FrameDe
 
 // ------------------------------------------------------------------------------------------------
 // SearchByProjection against the local map, fast path: two kernels.
-// k_mp_candidates (one thread per (frame, map point), whole GPU busy) enumerates every map point's candidates ONCE
+// k_mp_candidates (one lane per (frame, map point) for the window and the span, one lane per window key point for the
+// walk: flat_walk below; whole GPU busy) enumerates every map point's candidates ONCE
 // (GetFeaturesInArea order, level / window / uRight tests, statically occupied key points dropped) and caches
 // (index, Hamming distance, octave) per candidate in a span allocated from the frame's candidate pool.
 // k_mp_rounds (one block per frame) then resolves the greedy order in rounds on the cached lists.  A map point's
@@ -224,6 +225,79 @@ __global__ void __launch_bounds__(256) k_match_project_points_slow(const FrameDe
 // qualifies, so the result is the sequential loop's for any schedule (and for any placement of the spans).
 // cand entry: idx (16 bits) | dist (9 bits) << 16 | octave (4 bits) << 25.
 // ------------------------------------------------------------------------------------------------
+
+__device__ __forceinline__ unsigned long long lanes_below(int n) { return n >= 64 ? ~0ull : (1ull << n) - 1ull; }
+
+// The candidate walk of k_mp_candidates and k_lf_candidates, ONE WINDOW KEY POINT PER LANE.  Lane l owns the ub key points of its item's cell window: the
+// ranks [excl, excl + ub) of the wave's wsum.  A loop of every lane over its own window lasts as long as the wave's largest window (a level-7 item with
+// th = 3 spans eleven columns) while most lanes sit masked off; here the wave takes the wsum key points 64 at a time instead.  A lane finds the owner of its
+// rank by a six-step search over the scanned offsets, takes the owner's projection, radius, level bounds and window by shuffles, finds its key point by
+// walking the window columns' CSR counts (a column is one index range), and runs the tests and the popcount distance of the old loop on it.  The ranks of
+// one owner are consecutive lanes and keep the reference order (column by column, CSR order inside), so a survivor's slot in the owner's span is the
+// owner's count of earlier chunks (run, a register of the owner lane) plus the survivors between the owner's first lane of this chunk and this lane: the
+// span holds the same entries in the same order as before.  Called by whole waves (wsum is wave-uniform); returns the lane's own number of candidates.
+// item_desc: descriptor of the item of lane 0; cand: the frame's pool at the wave's base; lo, hi: inclusive octave bounds.
+template <bool PACK_OCT>
+__device__ __forceinline__ int flat_walk(const FrameDev &F, const int *__restrict__ claim, const uint8_t *__restrict__ obs_positive,
+                                         const uint8_t *__restrict__ item_desc, uint32_t *__restrict__ cand, int ub, int excl, int wsum, float x, float y,
+                                         float rad, float ur, int lo, int hi, const CellWin &w)
+{
+    const int lane = plf_lane();
+    const int win = ub > 0 ? (w.x0 | (w.x1 << 8) | (w.y0 << 16) | (w.y1 << 24)) : 0;   // (all four below 64)
+    int run = 0;
+    for (int c0 = 0; c0 < wsum; c0 += 64) {
+        const int t = c0 + lane;
+        int own = 0;   // the last lane whose first rank is <= t: the lanes behind it that share its offset own nothing, so for t < wsum it owns rank t
+#pragma unroll
+        for (int s = 32; s; s >>= 1) {
+            const int e = __shfl(excl, own + s, 64);
+            if (e <= t) own += s;
+        }
+        const int o_excl = __shfl(excl, own, 64), o_win = __shfl(win, own, 64), o_lo = __shfl(lo, own, 64), o_hi = __shfl(hi, own, 64);
+        const int o_run = __shfl(run, own, 64);
+        const float ox = __shfl(x, own, 64), oy = __shfl(y, own, 64), orad = __shfl(rad, own, 64), our = __shfl(ur, own, 64);
+        bool ok = t < wsum;
+        uint32_t entry = 0;
+        if (ok) {
+            const int x1 = (o_win >> 8) & 0xFF, y0 = (o_win >> 16) & 0xFF, y1 = (o_win >> 24) & 0xFF;
+            int r = t - o_excl, j = -1;
+            // WALK_COLS columns per trip, their eight loads in flight together at constant offsets from two pointers: the walk is a chain of L2 round
+            // trips, and it is the longest one of a chunk.  Columns past x1 are read (the table is padded for it, match_common.h) and count as empty.
+            const int *lo_p = F.cell_start + (o_win & 0xFF) * GRID_ROWS + y0, *hi_p = F.cell_start + (o_win & 0xFF) * GRID_ROWS + y1 + 1;
+            for (int left = x1 - (o_win & 0xFF); left >= 0 && j < 0; left -= WALK_COLS, lo_p += WALK_COLS * GRID_ROWS, hi_p += WALK_COLS * GRID_ROWS) {
+                static_assert(WALK_COLS == 4, "the selection below is written for four columns");
+                const int a0 = lo_p[0], a1 = lo_p[GRID_ROWS], a2 = lo_p[2 * GRID_ROWS], a3 = lo_p[3 * GRID_ROWS];
+                const int b0 = hi_p[0], b1 = hi_p[GRID_ROWS], b2 = hi_p[2 * GRID_ROWS], b3 = hi_p[3 * GRID_ROWS];
+                const int p1 = b0 - a0, p2 = p1 + (left >= 1 ? b1 - a1 : 0), p3 = p2 + (left >= 2 ? b2 - a2 : 0), p4 = p3 + (left >= 3 ? b3 - a3 : 0);
+                if (r < p4) j = r < p1 ? a0 + r : r < p2 ? a1 + r - p1 : r < p3 ? a2 + r - p2 : a3 + r - p3;
+                else r -= p4;
+            }
+            ok = j >= 0;
+            if (ok) {
+                const float4 e = F.cell_kp[j];
+                const int oct = __float_as_int(e.z), idx = __float_as_int(e.w);
+                ok = oct >= o_lo && oct <= o_hi && fabsf(e.x - ox) < orad && fabsf(e.y - oy) < orad;
+                if (ok && blocked(claim, idx, obs_positive)) ok = false;
+                if (ok && F.uright) { const float urr = F.uright[idx]; if (urr > 0 && fabsf(our - urr) > orad) ok = false; }
+                if (ok) {
+                    const uint4 *dp = reinterpret_cast<const uint4 *>(item_desc + (size_t)own * 32);
+                    const uint4 *kp = reinterpret_cast<const uint4 *>(F.desc + (size_t)idx * 32);
+                    const uint4 d0 = dp[0], d1 = dp[1], k0 = kp[0], k1 = kp[1];
+                    const int dist = __popc(d0.x ^ k0.x) + __popc(d0.y ^ k0.y) + __popc(d0.z ^ k0.z) + __popc(d0.w ^ k0.w) + __popc(d1.x ^ k1.x) +
+                                     __popc(d1.y ^ k1.y) + __popc(d1.z ^ k1.z) + __popc(d1.w ^ k1.w);
+                    entry = (uint32_t)idx | ((uint32_t)dist << 16);
+                    if (PACK_OCT) entry |= (uint32_t)(oct & 15) << 25;
+                }
+            }
+        }
+        const unsigned long long sv = __ballot(ok);
+        if (ok) cand[o_excl + o_run + __popcll(sv & lanes_below(lane) & ~lanes_below(max(o_excl - c0, 0)))] = entry;
+        // the owner's count moves by the survivors among its lanes of this chunk
+        run += __popcll(sv & lanes_below(min(max(excl + ub - c0, 0), 64)) & ~lanes_below(min(max(excl - c0, 0), 64)));
+    }
+    return run;
+}
+
 __global__ void __launch_bounds__(256) k_mp_candidates(const FrameDev *__restrict__ frames, MapDev MP, float th,
                                                        const int *__restrict__ match_all, int kp_stride, uint8_t *__restrict__ done_all,
                                                        uint32_t *__restrict__ cand_all, int2 *__restrict__ span_all, int cand_cap,
@@ -253,7 +327,7 @@ __global__ void __launch_bounds__(256) k_mp_candidates(const FrameDev *__restric
         if (w.ok)
             for (int ix = w.x0; ix <= w.x1; ix++) ub += F.cell_start[ix * GRID_ROWS + w.y1 + 1] - F.cell_start[ix * GRID_ROWS + w.y0];
     }
-    const int excl = plf_wave_excl_scan(ub), wsum = plf_wave_sum(ub);
+    const int excl = plf_wave_excl_scan(ub), wsum = __builtin_amdgcn_readfirstlane(plf_wave_sum(ub));
     int base = 0;
     if (wsum > 0) {
         if (plf_lane() == 0) base = atomicAdd(&total[f], wsum);
@@ -261,29 +335,11 @@ __global__ void __launch_bounds__(256) k_mp_candidates(const FrameDev *__restric
     }
     const bool fits = base + wsum <= cand_cap;
     if (!fits && plf_lane() == 0) overflow[f] = 1;   // this frame is left to k_match_project_points_slow
-    if (!in) return;
     const int o0 = base + excl;
     int o = o0;
-    if (ub > 0 && fits) {
-        const uint4 *dp = reinterpret_cast<const uint4 *>(MP.desc + (size_t)m * 32);
-        const uint4 d0 = dp[0], d1 = dp[1];
-        for (int ix = w.x0; ix <= w.x1; ix++) {
-            const int j1 = F.cell_start[ix * GRID_ROWS + w.y1 + 1];
-            for (int j = F.cell_start[ix * GRID_ROWS + w.y0]; j < j1; j++) {
-                const float4 e = F.cell_kp[j];
-                const int oct = __float_as_int(e.z), idx = __float_as_int(e.w);
-                if (oct < lvl - 1 || oct > lvl) continue;
-                if (!(fabsf(e.x - x) < rad && fabsf(e.y - y) < rad)) continue;
-                if (blocked(claim, idx, MP.obs_positive)) continue;
-                if (F.uright) { const float ur = F.uright[idx]; if (ur > 0 && fabsf(xr - ur) > rad) continue; }
-                const uint4 *kp = reinterpret_cast<const uint4 *>(F.desc + (size_t)idx * 32);
-                const uint4 k0 = kp[0], k1 = kp[1];
-                const int dist = __popc(d0.x ^ k0.x) + __popc(d0.y ^ k0.y) + __popc(d0.z ^ k0.z) + __popc(d0.w ^ k0.w) + __popc(d1.x ^ k1.x) +
-                                 __popc(d1.y ^ k1.y) + __popc(d1.z ^ k1.z) + __popc(d1.w ^ k1.w);
-                cand[o++] = (uint32_t)idx | ((uint32_t)dist << 16) | ((uint32_t)(oct & 15) << 25);
-            }
-        }
-    }
+    if (wsum > 0 && fits)
+        o += flat_walk<true>(F, claim, MP.obs_positive, MP.desc + (size_t)(m - plf_lane()) * 32, cand + base, ub, excl, wsum, x, y, rad, xr, lvl - 1, lvl, w);
+    if (!in) return;
     span_all[(size_t)f * MP.m + m] = make_int2(o0, o - o0);
     done_all[(size_t)f * MP.m + m] = (o > o0) ? 0 : 1;
 }
@@ -539,6 +595,7 @@ __global__ void __launch_bounds__(256) k_match_lastframe(const FrameDev *__restr
 // Fast path of the motion-model search for batches (plf_match_project_lastframe_batch): the scheme of k_mp_candidates / k_mp_rounds.
 //   k_lf_candidates   one thread per (frame, last-frame point): projection with the frame's pose, cell window, level window, uRight test and the
 //                     Hamming distance of every admissible key point, cached as (index | distance << 16) in the reference's candidate order
+//                     (the walk over the window key points is flat_walk, one key point per lane, as in k_mp_candidates)
 //   k_lf_rounds       one block per frame: the greedy loop in conflict-free rounds on the cached lists.  This overload keeps the BEST distance only
 //                     (no ratio test), so a point's outcome is decided by its best still-available candidate alone: it is final as soon as no
 //                     unfinished EARLIER point lists that key point (owner[best] == i).  Then the rotation histogram and its per-assignment cull.
@@ -584,7 +641,7 @@ __global__ void __launch_bounds__(256) k_lf_candidates(const FrameDev *__restric
                 for (int ix = w.x0; ix <= w.x1; ix++) ub += F.cell_start[ix * GRID_ROWS + w.y1 + 1] - F.cell_start[ix * GRID_ROWS + w.y0];
         }
     }
-    const int excl = plf_wave_excl_scan(ub), wsum = plf_wave_sum(ub);
+    const int excl = plf_wave_excl_scan(ub), wsum = __builtin_amdgcn_readfirstlane(plf_wave_sum(ub));
     int base = 0;
     if (wsum > 0) {
         if (plf_lane() == 0) base = atomicAdd(&total[f], wsum);
@@ -592,35 +649,17 @@ __global__ void __launch_bounds__(256) k_lf_candidates(const FrameDev *__restric
     }
     const bool fits = base + wsum <= cand_cap;
     if (!fits && plf_lane() == 0) overflow[f] = 1;
-    if (!in) return;
     const int o0 = base + excl;
     int o = o0;
-    if (ub > 0 && fits) {
+    if (wsum > 0 && fits) {
+        // "no level test" (minL <= 0 and maxL < 0) and "no upper level" (maxL < 0) become bounds no octave reaches
         const int minL = bForward ? oct : (bBackward ? 0 : oct - 1), maxL = bForward ? -1 : (bBackward ? oct : oct + 1);
         const bool chk = (minL > 0) || (maxL >= 0);
-        const uint4 *dp = reinterpret_cast<const uint4 *>(Lf.mp_desc + (size_t)i * 32);
-        const uint4 d0 = dp[0], d1 = dp[1];
         const float ur = fmaf(-P.bf, invzc, u);   // so@0x81eb5
-        for (int ix = w.x0; ix <= w.x1; ix++) {
-            const int j1 = F.cell_start[ix * GRID_ROWS + w.y1 + 1];
-            for (int j = F.cell_start[ix * GRID_ROWS + w.y0]; j < j1; j++) {
-                const float4 e = F.cell_kp[j];
-                const int ko = __float_as_int(e.z), idx = __float_as_int(e.w);
-                if (chk) {
-                    if (ko < minL) continue;
-                    if (maxL >= 0 && ko > maxL) continue;
-                }
-                if (!(fabsf(e.x - u) < rad && fabsf(e.y - v) < rad)) continue;
-                if (blocked(claim, idx, Lf.obs_positive)) continue;
-                if (F.uright) { const float urr = F.uright[idx]; if (urr > 0 && fabsf(ur - urr) > rad) continue; }
-                const uint4 *kp = reinterpret_cast<const uint4 *>(F.desc + (size_t)idx * 32);
-                const uint4 k0 = kp[0], k1 = kp[1];
-                const int dist = __popc(d0.x ^ k0.x) + __popc(d0.y ^ k0.y) + __popc(d0.z ^ k0.z) + __popc(d0.w ^ k0.w) + __popc(d1.x ^ k1.x) +
-                                 __popc(d1.y ^ k1.y) + __popc(d1.z ^ k1.z) + __popc(d1.w ^ k1.w);
-                cand[o++] = (uint32_t)idx | ((uint32_t)dist << 16);
-            }
-        }
+        o += flat_walk<false>(F, claim, Lf.obs_positive, Lf.mp_desc + (size_t)(i - plf_lane()) * 32, cand + base, ub, excl, wsum, u, v, rad, ur,
+                              chk ? minL : INT_MIN, maxL >= 0 ? maxL : INT_MAX, w);
     }
+    if (!in) return;
     span_all[(size_t)f * item_stride + i] = make_int2(o0, o - o0);
     done_all[(size_t)f * item_stride + i] = (o > o0) ? 0 : 1;
 }
