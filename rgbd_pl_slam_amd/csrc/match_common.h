@@ -1,5 +1,7 @@
 // match_common.h -- shared by match_kernels.hip and match_host.hip (include/plf.h, "Matchers"): the frame grid, the argument structs passed by value or
-// through device tables, and the kernels the host launches
+// through device tables, and the kernels the host launches.  The device helpers the kernels are built from (one definition per reference rule: radius,
+// GetFeaturesInArea, availability, round loops, rotation consistency) are file-local to match_kernels.hip and indexed in
+// its header comment; this header stays the host/kernel contract.
 #pragma once
 #include "plf_common.h"
 

@@ -17,6 +17,23 @@
 // claims -- exactly what the sequential loop would see.  Items decided in one round never share a candidate, the
 // lowest unfinished item always qualifies, and the result equals the sequential loop for any schedule.
 // No MFMA: 256-bit XOR + popcount per candidate; the work is gather / compare bound.
+//
+// Every rule of the reference has ONE definition here, and the kernels are set-up code plus callables on top of them (exceptions, each marked where
+// it stands: the pool span of the two candidates kernels, the last-frame projection (k_match_lastframe, k_lf_candidates) and the popcount chain of flat_walk are
+// written out, to keep those kernels instruction for instruction what they were):
+//   hamming_g                          DescriptorDistance (pointer and uint4-pair forms)
+//   map_radius                         RadiusByViewingCos * th * scale factor of the predicted level (map points and map lines)
+//   cell_window, candidates_in_area    Frame / KeyFrame::GetFeaturesInArea, candidates in the reference order
+//   blocked, load_claim, store_claim   "is this key point still available" and the claim array's way in and out of LDS (free_slot: its one-compare
+//                                      form without obs_positive, for the inner loops of the line kernels)
+//   reset_owner, greedy_rounds         the slow round loop (candidates re-enumerated every round): k_match_project_points_slow,
+//                                      k_match_lastframe, k_project_kf_greedy; the line kernels keep their own loop (see match_project_lines_body)
+//   wave_append, list_unfinished       the list scaffold of the fast round kernels k_mp_rounds / k_lf_rounds
+//   rot_bin, three_maxima, rot_cull    rotation consistency (rotHist, ComputeThreeMaxima, the per-assignment cull): k_match_lastframe,
+//                                      k_lf_rounds, k_match_bow; lf_orientation_cull is the tail the two last-frame kernels make of them
+//   accept_best_of_two                 TH_HIGH and the same-level ratio test of the best / second-best searches (map points, map lines)
+//   line_fields, stage_line,           a key line in LDS and Frame::GetLinesInArea's test on its four fields
+//   line_in_area4
 #include "plf_common.h"
 #include "match_common.h"
 
@@ -77,14 +94,34 @@ __global__ void __launch_bounds__(256) k_build_grid(const FrameDev *__restrict__
     }
 }
 
+// search radius of a map point or map line: ORBmatcher::RadiusByViewingCos, times th unless th is 1, times the scale factor of the predicted level
 __device__ __forceinline__ float radius_by_viewing_cos(float vc) { return ((double)vc > 0.998) ? 2.5f : 4.0f; }
+__device__ __forceinline__ float map_radius(float view_cos, float th, float scale)
+{
+    float r = radius_by_viewing_cos(view_cos);
+    if (th != 1.0f) r *= th;
+    return r * scale;
+}
 
+// acceptance of the searches that keep a best and a second-best candidate (map points, map lines): best <= TH_HIGH, and the ratio test only between
+// candidates of one level ("if (bestLevel == bestLevel2 && bestDist > mfNNratio * bestDist2) continue")
+__device__ __forceinline__ bool accept_best_of_two(int bestDist, int bestLevel, int bestDist2, int bestLevel2, float nnratio)
+{
+    if (bestDist > TH_HIGH) return false;
+    if (bestLevel == bestLevel2 && (float)bestDist > nnratio * (float)bestDist2) return false;
+    return true;
+}
+
+// the two halves of one 256-bit descriptor against those of another
+__device__ __forceinline__ int hamming_g(const uint4 a0, const uint4 a1, const uint4 b0, const uint4 b1)
+{
+    return __popc(a0.x ^ b0.x) + __popc(a0.y ^ b0.y) + __popc(a0.z ^ b0.z) + __popc(a0.w ^ b0.w) + __popc(a1.x ^ b1.x) +
+           __popc(a1.y ^ b1.y) + __popc(a1.z ^ b1.z) + __popc(a1.w ^ b1.w);
+}
 __device__ __forceinline__ int hamming_g(const uint8_t *a, const uint8_t *b)
 {
     const uint4 *pa = reinterpret_cast<const uint4 *>(a), *pb = reinterpret_cast<const uint4 *>(b);
-    const uint4 a0 = pa[0], a1 = pa[1], b0 = pb[0], b1 = pb[1];
-    return __popc(a0.x ^ b0.x) + __popc(a0.y ^ b0.y) + __popc(a0.z ^ b0.z) + __popc(a0.w ^ b0.w) + __popc(a1.x ^ b1.x) +
-           __popc(a1.y ^ b1.y) + __popc(a1.z ^ b1.z) + __popc(a1.w ^ b1.w);
+    return hamming_g(pa[0], pa[1], pb[0], pb[1]);
 }
 
 // Frame::GetFeaturesInArea cell window
@@ -105,35 +142,100 @@ __device__ __forceinline__ CellWin cell_window(const FrameDev &F, float x, float
     return w;
 }
 
-// iterate the candidates of GetFeaturesInArea(x, y, r, minLevel, maxLevel) in the reference order
-#define FOR_EACH_CANDIDATE(F, W, X, Y, R, MINL, MAXL, IDX, BODY)                                              \
-    {                                                                                                         \
-        const bool _chk = ((MINL) > 0) || ((MAXL) >= 0);                                                      \
-        for (int _ix = (W).x0; _ix <= (W).x1; _ix++)                                                          \
-            for (int _iy = (W).y0; _iy <= (W).y1; _iy++) {                                                    \
-                const int _c = _ix * GRID_ROWS + _iy;                                                         \
-                for (int _j = (F).cell_start[_c]; _j < (F).cell_start[_c + 1]; _j++) {                        \
-                    const int IDX = (F).cell_idx[_j];                                                         \
-                    const plf_keypoint _kp = (F).keys[IDX];                                                   \
-                    if (_chk) {                                                                               \
-                        if (_kp.octave < (MINL)) continue;                                                    \
-                        if ((MAXL) >= 0 && _kp.octave > (MAXL)) continue;                                     \
-                    }                                                                                         \
-                    if (!(fabsf(_kp.x - (X)) < (R) && fabsf(_kp.y - (Y)) < (R))) continue;                    \
-                    BODY                                                                                      \
-                }                                                                                             \
-            }                                                                                                 \
-    }
+// GetFeaturesInArea(x, y, r, minLevel, maxLevel): body(idx, key point) for every candidate, in the reference order
+template <class Body>
+__device__ __forceinline__ void candidates_in_area(const FrameDev &F, float x, float y, float r, int minL, int maxL, Body body)
+{
+    const CellWin w = cell_window(F, x, y, r);
+    if (!w.ok) return;
+    const bool chk = (minL > 0) || (maxL >= 0);
+    for (int ix = w.x0; ix <= w.x1; ix++)
+        for (int iy = w.y0; iy <= w.y1; iy++) {
+            const int c = ix * GRID_ROWS + iy;
+            for (int j = F.cell_start[c]; j < F.cell_start[c + 1]; j++) {
+                const int idx = F.cell_idx[j];
+                const plf_keypoint kp = F.keys[idx];
+                if (chk) {
+                    if (kp.octave < minL) continue;
+                    if (maxL >= 0 && kp.octave > maxL) continue;
+                }
+                if (!(fabsf(kp.x - x) < r && fabsf(kp.y - y) < r)) continue;
+                body(idx, kp);
+            }
+        }
+}
 
+// ---- the claim array: claim[k] = item that holds key point k, -1 free, -2 occupied before the call and by nothing this call knows.
+// blocked() is the ONE availability rule, "CurrentFrame.mvpMapPoints[k] && ->Observations() > 0" (so@0x81e3d): a key point held by an item WITHOUT
+// observations (a temporal point of localisation mode; obs_positive[item] == 0) stays available to later items and is overwritten.  obs_positive == NULL
+// tests the pointer only (relocalisation, Fuse / SearchBySim3, lines): on the values load_claim leaves (-2, -1, >= 0) that is claim[k] != -1.  The -3 marks
+// of an earlier check_orientation = 2 call read as free, in load_claim and here alike (flat_walk reads the caller's array as it came).
 __device__ __forceinline__ bool blocked(const int *claim, int k, const uint8_t *obs_positive)
 {
     const int c = claim[k];
     return c == -2 || (c >= 0 && (!obs_positive || obs_positive[c]));
 }
+// !blocked(claim, k, NULL) on the values load_claim leaves, in one compare: for the inner loops of the line kernels, which walk ALL lines per item
+// (with the two compares of blocked() k_match_project_lines was 3-7 % slower).  A change to the pointer-only rule of blocked() is made here too.
+__device__ __forceinline__ bool free_slot(const int *claim, int k) { return claim[k] == -1; }
+// whole block: match[] of the caller -> claim[] in LDS; also_per_k(k) rides in the same loop (the line kernels stage key line k there)
+template <class Also>
+__device__ __forceinline__ void load_claim(int *claim, const int *match, int n, Also also_per_k)
+{
+    const int t = threadIdx.x, T = blockDim.x;
+    for (int k = t; k < n; k += T) {
+        claim[k] = match[k] < -2 ? -1 : match[k];
+        also_per_k(k);
+    }
+}
+__device__ __forceinline__ void load_claim(int *claim, const int *match, int n) { load_claim(claim, match, n, [](int) {}); }
+// whole block: claim[] -> match[], and the number of accepted items
+__device__ __forceinline__ void store_claim(int *match, const int *claim, int n, int *nmatches, const int *s_acc)
+{
+    const int t = threadIdx.x, T = blockDim.x;
+    for (int k = t; k < n; k += T) match[k] = claim[k];
+    if (t == 0) *nmatches = *s_acc;
+}
+__device__ __forceinline__ void reset_owner(int *owner, int n)
+{
+    const int t = threadIdx.x, T = blockDim.x;
+    for (int k = t; k < n; k += T) owner[k] = 0x7fffffff;
+}
+
+// The slow round loop of the header comment, for kernels that re-enumerate an item's candidates from the grid in every round (whole block):
+//   candidates(i, body)   body(idx, key point) for every admissible, still-available candidate of item i, in the reference order
+//   decide(i)             item i owns all of them: scan them, write claim[] and the kernel's bookkeeping, set bit 0 of done[i]
+// The loop owns owner[], the post pass, the safety pass ("an item must own ALL its free candidates"), s_left and the barriers.
+template <class Candidates, class Decide>
+__device__ __forceinline__ void greedy_rounds(int n_items, int n_kp, int *owner, int *s_left, const uint8_t *done, Candidates candidates, Decide decide)
+{
+    const int t = threadIdx.x, T = blockDim.x;
+    for (int round = 0; round <= n_items; round++) {
+        reset_owner(owner, n_kp);
+        if (t == 0) *s_left = 0;
+        __syncthreads();
+        // post: every unfinished item marks its free candidates with its index
+        for (int i = t; i < n_items; i += T) {
+            if (done[i] & 1) continue;
+            candidates(i, [&](int idx, const plf_keypoint &) { atomicMin(&owner[idx], i); });
+        }
+        __syncthreads();
+        // decide: items owning all their free candidates are independent of every unfinished predecessor
+        for (int i = t; i < n_items; i += T) {
+            if (done[i] & 1) continue;
+            bool safe = true;
+            candidates(i, [&](int idx, const plf_keypoint &) { if (owner[idx] != i) safe = false; });
+            if (!safe) { atomicAdd(s_left, 1); continue; }
+            decide(i);
+        }
+        __syncthreads();
+        if (*s_left == 0) break;
+        __syncthreads();
+    }
+}
 
 // Fallback used only for frames whose candidate lists do not fit the cache of k_mp_candidates (gate:
-// overflow[f] != 0): same round scheme with the conservative rule "an item must own ALL its free candidates" and
-// the candidates re-enumerated from the grid in every round.
+// overflow[f] != 0): the slow round loop on GetFeaturesInArea(proj, radius, level - 1, level).
 // one block per frame; claim[] and owner[] live in LDS (kp_cap ints each)
 __global__ void __launch_bounds__(256) k_match_project_points_slow(const FrameDev *__restrict__ frames, MapDev MP, float th, float nnratio,
                                                                    int *__restrict__ match_all, int kp_stride, int *__restrict__ nmatches,
@@ -148,64 +250,38 @@ __global__ void __launch_bounds__(256) k_match_project_points_slow(const FrameDe
     if (F.n_dev) F.n = min(F.n, *F.n_dev);
     int *match = match_all + (size_t)f * kp_stride;
     uint8_t *done = done_all + (size_t)f * MP.m;
-    const bool bFactor = th != 1.0f;
-    for (int k = t; k < F.n; k += T) claim[k] = match[k] < -2 ? -1 : match[k];   // (-3 marks of an earlier check_orientation = 2 call read as free; -2 stays "occupied")
+    load_claim(claim, match, F.n);
     if (t == 0) s_acc = 0;
     for (int m = t; m < MP.m; m += T) done[m] = MP.in_view[m] ? 0 : 1;
     __syncthreads();
-    for (int round = 0; round <= MP.m; round++) {
-        for (int k = t; k < F.n; k += T) owner[k] = 0x7fffffff;
-        if (t == 0) s_left = 0;
-        __syncthreads();
-        // post: every unfinished map point marks its free candidates with its index
-        for (int m = t; m < MP.m; m += T) {
-            if (done[m]) continue;
-            const int lvl = MP.level[m];
-            float r = radius_by_viewing_cos(MP.view_cos[m]);
-            if (bFactor) r *= th;
-            const float rad = r * F.scale_factors[lvl];
-            const float x = MP.proj_x[m], y = MP.proj_y[m];
-            const CellWin w = cell_window(F, x, y, rad);
-            if (w.ok) FOR_EACH_CANDIDATE(F, w, x, y, rad, lvl - 1, lvl, idx, { if (!blocked(claim, idx, MP.obs_positive)) atomicMin(&owner[idx], m); })
-        }
-        __syncthreads();
-        // decide: map points owning all their free candidates are independent of every unfinished predecessor
-        for (int m = t; m < MP.m; m += T) {
-            if (done[m]) continue;
-            const int lvl = MP.level[m];
-            float r = radius_by_viewing_cos(MP.view_cos[m]);
-            if (bFactor) r *= th;
-            const float rad = r * F.scale_factors[lvl];
-            const float x = MP.proj_x[m], y = MP.proj_y[m];
-            const CellWin w = cell_window(F, x, y, rad);
-            bool safe = true;
-            if (w.ok) FOR_EACH_CANDIDATE(F, w, x, y, rad, lvl - 1, lvl, idx, { if (!blocked(claim, idx, MP.obs_positive) && owner[idx] != m) safe = false; })
-            if (!safe) { atomicAdd(&s_left, 1); continue; }
-            int bestDist = 256, bestLevel = -1, bestDist2 = 256, bestLevel2 = -1, bestIdx = -1;
-            const uint8_t *d = MP.desc + (size_t)m * 32;
-            if (w.ok) FOR_EACH_CANDIDATE(F, w, x, y, rad, lvl - 1, lvl, idx, {
-                if (blocked(claim, idx, MP.obs_positive)) continue;
-                if (F.uright) {
-                    const float ur = F.uright[idx];
-                    if (ur > 0) { const float er = fabsf(MP.proj_xr[m] - ur); if (er > rad) continue; }
-                }
-                const int dist = hamming_g(d, F.desc + (size_t)idx * 32);
-                if (dist < bestDist) { bestDist2 = bestDist; bestDist = dist; bestLevel2 = bestLevel; bestLevel = _kp.octave; bestIdx = idx; }
-                else if (dist < bestDist2) { bestLevel2 = _kp.octave; bestDist2 = dist; }
-            })
-            done[m] = 1;
-            if (bestDist <= TH_HIGH) {
-                if (bestLevel == bestLevel2 && (float)bestDist > nnratio * (float)bestDist2) continue;
-                claim[bestIdx] = m;  // only this map point can touch bestIdx in this round
-                atomicAdd(&s_acc, 1);
+    auto radius = [&](int m) { return map_radius(MP.view_cos[m], th, F.scale_factors[MP.level[m]]); };
+    auto candidates = [&](int m, auto body) {
+        const int lvl = MP.level[m];
+        candidates_in_area(F, MP.proj_x[m], MP.proj_y[m], radius(m), lvl - 1, lvl, [&](int idx, const plf_keypoint &kp) {
+            if (!blocked(claim, idx, MP.obs_positive)) body(idx, kp);
+        });
+    };
+    auto decide = [&](int m) {
+        int bestDist = 256, bestLevel = -1, bestDist2 = 256, bestLevel2 = -1, bestIdx = -1;
+        const uint8_t *d = MP.desc + (size_t)m * 32;
+        const float rad = radius(m);
+        candidates(m, [&](int idx, const plf_keypoint &kp) {
+            if (F.uright) {
+                const float ur = F.uright[idx];
+                if (ur > 0) { const float er = fabsf(MP.proj_xr[m] - ur); if (er > rad) return; }
             }
+            const int dist = hamming_g(d, F.desc + (size_t)idx * 32);
+            if (dist < bestDist) { bestDist2 = bestDist; bestDist = dist; bestLevel2 = bestLevel; bestLevel = kp.octave; bestIdx = idx; }
+            else if (dist < bestDist2) { bestLevel2 = kp.octave; bestDist2 = dist; }
+        });
+        done[m] = 1;
+        if (accept_best_of_two(bestDist, bestLevel, bestDist2, bestLevel2, nnratio)) {
+            claim[bestIdx] = m;  // only this map point can touch bestIdx in this round
+            atomicAdd(&s_acc, 1);
         }
-        __syncthreads();
-        if (s_left == 0) break;
-        __syncthreads();
-    }
-    for (int k = t; k < F.n; k += T) match[k] = claim[k];
-    if (t == 0) nmatches[f] = s_acc;
+    };
+    greedy_rounds(MP.m, F.n, owner, &s_left, done, candidates, decide);
+    store_claim(match, claim, F.n, &nmatches[f], &s_acc);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -226,7 +302,8 @@ __global__ void __launch_bounds__(256) k_match_project_points_slow(const FrameDe
 // cand entry: idx (16 bits) | dist (9 bits) << 16 | octave (4 bits) << 25.
 // ------------------------------------------------------------------------------------------------
 
-__device__ __forceinline__ unsigned long long lanes_below(int n) { return n >= 64 ? ~0ull : (1ull << n) - 1ull; }
+// mask of the lanes below n (plf_lanes_below(mask) is the other thing: the COUNT of a ballot's lanes below this one)
+__device__ __forceinline__ unsigned long long lane_mask_below(int n) { return n >= 64 ? ~0ull : (1ull << n) - 1ull; }
 
 // The candidate walk of k_mp_candidates and k_lf_candidates, ONE WINDOW KEY POINT PER LANE.  Lane l owns the ub key points of its item's cell window: the
 // ranks [excl, excl + ub) of the wave's wsum.  A loop of every lane over its own window lasts as long as the wave's largest window (a level-7 item with
@@ -283,6 +360,8 @@ __device__ __forceinline__ int flat_walk(const FrameDev &F, const int *__restric
                     const uint4 *dp = reinterpret_cast<const uint4 *>(item_desc + (size_t)own * 32);
                     const uint4 *kp = reinterpret_cast<const uint4 *>(F.desc + (size_t)idx * 32);
                     const uint4 d0 = dp[0], d1 = dp[1], k0 = kp[0], k1 = kp[1];
+                    // hamming_g written out: through the function the compiler folds the add chain into the packing below differently (the walk's hot path
+                    // is kept instruction for instruction)
                     const int dist = __popc(d0.x ^ k0.x) + __popc(d0.y ^ k0.y) + __popc(d0.z ^ k0.z) + __popc(d0.w ^ k0.w) + __popc(d1.x ^ k1.x) +
                                      __popc(d1.y ^ k1.y) + __popc(d1.z ^ k1.z) + __popc(d1.w ^ k1.w);
                     entry = (uint32_t)idx | ((uint32_t)dist << 16);
@@ -291,9 +370,9 @@ __device__ __forceinline__ int flat_walk(const FrameDev &F, const int *__restric
             }
         }
         const unsigned long long sv = __ballot(ok);
-        if (ok) cand[o_excl + o_run + __popcll(sv & lanes_below(lane) & ~lanes_below(max(o_excl - c0, 0)))] = entry;
+        if (ok) cand[o_excl + o_run + __popcll(sv & lane_mask_below(lane) & ~lane_mask_below(max(o_excl - c0, 0)))] = entry;
         // the owner's count moves by the survivors among its lanes of this chunk
-        run += __popcll(sv & lanes_below(min(max(excl + ub - c0, 0), 64)) & ~lanes_below(min(max(excl - c0, 0), 64)));
+        run += __popcll(sv & lane_mask_below(min(max(excl + ub - c0, 0), 64)) & ~lane_mask_below(min(max(excl - c0, 0), 64)));
     }
     return run;
 }
@@ -316,9 +395,7 @@ __global__ void __launch_bounds__(256) k_mp_candidates(const FrameDev *__restric
     w.ok = false;
     if (act) {
         lvl = MP.level[m];
-        float r = radius_by_viewing_cos(MP.view_cos[m]);
-        if (th != 1.0f) r *= th;
-        rad = r * F.scale_factors[lvl];
+        rad = map_radius(MP.view_cos[m], th, F.scale_factors[lvl]);
         x = MP.proj_x[m]; y = MP.proj_y[m];
         if (F.uright) xr = MP.proj_xr[m];
         w = cell_window(F, x, y, rad);
@@ -327,6 +404,8 @@ __global__ void __launch_bounds__(256) k_mp_candidates(const FrameDev *__restric
         if (w.ok)
             for (int ix = w.x0; ix <= w.x1; ix++) ub += F.cell_start[ix * GRID_ROWS + w.y1 + 1] - F.cell_start[ix * GRID_ROWS + w.y0];
     }
+    // the pool span: wave scan of ub, one atomicAdd per wave, overflow flag, span / done.  Written out here and, the same, in k_lf_candidates: as a shared
+    // helper it left this kernel with another register allocation and a time 0.6-2 % above the old one, more than the run-to-run spread
     const int excl = plf_wave_excl_scan(ub), wsum = __builtin_amdgcn_readfirstlane(plf_wave_sum(ub));
     int base = 0;
     if (wsum > 0) {
@@ -344,6 +423,27 @@ __global__ void __launch_bounds__(256) k_mp_candidates(const FrameDev *__restric
     done_all[(size_t)f * MP.m + m] = (o > o0) ? 0 : 1;
 }
 
+// ---- the list scaffold of the fast round kernels (k_mp_rounds, k_lf_rounds): the unfinished items as a uint16 list in LDS, rebuilt smaller every round.
+// wave_append: the lanes with `take` add their item behind *count, in lane order, with one atomicAdd per wave.  Lane 0 does the add and
+// the others read its result, so every lane of the wave must arrive: the callers' loops have block-uniform trip counts
+__device__ __forceinline__ void wave_append(bool take, int item, uint16_t *list, int *count)
+{
+    const unsigned long long mask = __ballot(take);
+    int base = 0;
+    if (plf_lane() == 0 && mask) base = atomicAdd(count, __popcll(mask));
+    base = __shfl(base, 0, 64);
+    if (take) list[base + plf_lanes_below(mask)] = (uint16_t)item;
+}
+// whole block: the items the candidates kernel left unfinished (those with a non-empty span)
+__device__ __forceinline__ void list_unfinished(int n, const uint8_t *done, uint16_t *list, int *count)
+{
+    const int t = threadIdx.x, T = blockDim.x;
+    for (int m0 = 0; m0 < n; m0 += T) {
+        const int m = m0 + t;
+        wave_append(m < n && !done[m], m, list, count);
+    }
+}
+
 // LDS: claim[kp_cap], owner[kp_cap] (int), ONE list of unfinished map points (uint16, MP.m <= 65535), compacted in place after every round -- a second
 // list made the block 28 KB at 5000 map points (5 blocks per CU, and no room next to an ORB tile in the shadow of the region-growing kernel)
 // Round 4: ONE scan of an item's cached candidates per round.  The scan that posts the item's index on its free candidates also finds its two best free candidates
@@ -358,7 +458,7 @@ __global__ void __launch_bounds__(256) k_mp_rounds(const FrameDev *__restrict__ 
     int *claim = (int *)smem, *owner = claim + kp_cap;
     uint16_t *la = (uint16_t *)(owner + kp_cap);
     __shared__ int s_n[2], s_acc;
-    const int f = blockIdx.x, t = threadIdx.x, T = blockDim.x, lane = plf_lane();
+    const int f = blockIdx.x, t = threadIdx.x, T = blockDim.x;
     if (overflow[f]) return;
     FrameDev F = frames[f];
     if (F.n_dev) F.n = min(F.n, *F.n_dev);
@@ -366,24 +466,16 @@ __global__ void __launch_bounds__(256) k_mp_rounds(const FrameDev *__restrict__ 
     const uint8_t *done = done_all + (size_t)f * MP.m;
     const uint32_t *cand = cand_all + (size_t)f * cand_cap;
     const int2 *span = span_all + (size_t)f * MP.m;
-    for (int k = t; k < F.n; k += T) claim[k] = match[k] < -2 ? -1 : match[k];   // (-3 marks of an earlier check_orientation = 2 call read as free; -2 stays "occupied")
+    load_claim(claim, match, F.n);
     if (t == 0) { s_acc = 0; s_n[0] = 0; s_n[1] = 0; }
     __syncthreads();
-    for (int m0 = 0; m0 < MP.m; m0 += T) {
-        const int m = m0 + t;
-        const bool un = m < MP.m && !done[m];
-        const unsigned long long mask = __ballot(un);
-        int base = 0;
-        if (lane == 0 && mask) base = atomicAdd(&s_n[0], __popcll(mask));
-        base = __shfl(base, 0, 64);
-        if (un) la[base + __popcll(mask & ((1ull << lane) - 1ull))] = (uint16_t)m;
-    }
+    list_unfinished(MP.m, done, la, &s_n[0]);
     __syncthreads();
     int cur = 0;
     for (int round = 0; round <= MP.m; round++) {
         const int nact = s_n[cur];
         if (nact == 0) break;
-        for (int k = t; k < F.n; k += T) owner[k] = 0x7fffffff;
+        reset_owner(owner, F.n);
         __syncthreads();
         unsigned long long *top2 = top2_all + (size_t)f * top2_stride;
         for (int i = t; i < nact; i += T) {
@@ -418,26 +510,72 @@ __global__ void __launch_bounds__(256) k_mp_rounds(const FrameDev *__restrict__ 
                 const int bestLevel = (int)((tw >> 50) & 0x7F), bestLevel2 = (int)((tw >> 57) & 0x7F);   // (0x7F = none: only ever compared for equality, with a real level on one side)
                 const bool safe = (bestIdx < 0 || owner[bestIdx] == m) && (idx2 < 0 || owner[idx2] == m);
                 keep = !safe;
-                if (safe && bestDist <= TH_HIGH && !(bestLevel == bestLevel2 && (float)bestDist > nnratio * (float)bestDist2)) {
+                if (safe && bestDist <= TH_HIGH && !(bestLevel == bestLevel2 && (float)bestDist > nnratio * (float)bestDist2)) {   // (accept_best_of_two, written out: the decide rule of this kernel stays visible)
                     claim[bestIdx] = m;   // only this map point can touch bestIdx in this round
                     atomicAdd(&s_acc, 1);
                 }
             }
             // in place: the kept items of chunks 0 .. i0 / T land below i0 + T; every thread of the block has read its entry of THIS chunk before any is written
             __syncthreads();
-            const unsigned long long mask = __ballot(keep);
-            int base = 0;
-            if (lane == 0 && mask) base = atomicAdd(&s_n[cur ^ 1], __popcll(mask));
-            base = __shfl(base, 0, 64);
-            if (keep) la[base + __popcll(mask & ((1ull << lane) - 1ull))] = (uint16_t)m;
+            wave_append(keep, m, la, &s_n[cur ^ 1]);
         }
         __syncthreads();
         if (t == 0) s_n[cur] = 0;
         cur ^= 1;
         __syncthreads();
     }
-    for (int k = t; k < F.n; k += T) match[k] = claim[k];
-    if (t == 0) nmatches[f] = s_acc;
+    store_claim(match, claim, F.n, &nmatches[f], &s_acc);
+}
+
+// ---- rotation consistency (CheckOrientation): rotHist of the accepted assignments, ComputeThreeMaxima, and the cull of every assignment outside the kept bins
+__device__ __forceinline__ int rot_bin(float angle_a, float angle_b)
+{
+    float rot = angle_a - angle_b;
+    if (rot < 0.0f) rot += 360.0f;
+    int bin = (int)roundf(rot * (1.0f / 12.0f));  // this binary: HISTO_LENGTH / 360 (so@0x829b5)
+    if (bin == HISTO_LENGTH) bin = 0;
+    return bin;
+}
+// ORBmatcher::ComputeThreeMaxima (so@0x823eb, so@0x79c40), one thread: the three fullest bins, the second and third only above a tenth of the first
+__device__ __forceinline__ void three_maxima(const int *hist, int *keepbin)
+{
+    int max1 = 0, max2 = 0, max3 = 0, i1 = -1, i2 = -1, i3 = -1;
+    for (int i = 0; i < HISTO_LENGTH; i++) {
+        const int s = hist[i];
+        if (s > max1) { max3 = max2; max2 = max1; max1 = s; i3 = i2; i2 = i1; i1 = i; }
+        else if (s > max2) { max3 = max2; max2 = s; i3 = i2; i2 = i; }
+        else if (s > max3) { max3 = s; i3 = i; }
+    }
+    if ((float)max2 < 0.1f * (float)max1) { i2 = -1; i3 = -1; }
+    else if ((float)max3 < 0.1f * (float)max1) { i3 = -1; }
+    keepbin[0] = i1; keepbin[1] = i2; keepbin[2] = i3;
+}
+// whole block, after three_maxima and a barrier.  The reference culls per ASSIGNMENT (rotHist entries): an overwritten key point whose earlier or later
+// assignment falls in a dropped bin ends up NULL, and nmatches is decremented once per dropped assignment.
+//   assigned(i)   the key point of assignment i, negative for none;   bin(i, k)   its rot_bin;   drop(i, k)   clears the slot
+template <class Assigned, class Bin, class Drop>
+__device__ __forceinline__ void rot_cull(int n, const int *keepbin, int *s_acc, Assigned assigned, Bin bin, Drop drop)
+{
+    const int t = threadIdx.x, T = blockDim.x;
+    for (int i = t; i < n; i += T) {
+        const int k = assigned(i);
+        if (k < 0) continue;
+        const int b = bin(i, k);
+        if (b != keepbin[0] && b != keepbin[1] && b != keepbin[2]) { drop(i, k); atomicSub(s_acc, 1); }
+    }
+}
+
+// the tail of both last-frame kernels (whole block, hist complete): assignment = last-frame point i -> key point assigned(i); check_orientation = 2 marks
+// a culled key point -3 instead of -1
+template <class Assigned>
+__device__ __forceinline__ void lf_orientation_cull(const FrameDev &F, const LastDev &Lf, int check_ori, const int *hist, int *keepbin, int *claim, int *s_acc,
+                                                    Assigned assigned)
+{
+    if (threadIdx.x == 0) three_maxima(hist, keepbin);
+    __syncthreads();
+    rot_cull(Lf.n, keepbin, s_acc, assigned, [&](int i, int k) { return rot_bin(Lf.keys[i].angle, F.keys[k].angle); },
+             [&](int, int k) { claim[k] = check_ori == 2 ? -3 : -1; });
+    __syncthreads();
 }
 
 // one block; items = key points of the last frame.  proj[i] = (u, v, invzc, radius) prepared in the first phase.
@@ -467,11 +605,8 @@ __global__ void __launch_bounds__(256) k_match_lastframe(const FrameDev *__restr
         twc[i] = (float)(-((double)P.Rcw[i] * P.tcw[0] + (double)P.Rcw[3 + i] * P.tcw[1] + (double)P.Rcw[6 + i] * P.tcw[2]));
     for (int i = 0; i < 3; i++) tlc[i] = P.Rlw[i * 3] * twc[0] + P.Rlw[i * 3 + 1] * twc[1] + P.Rlw[i * 3 + 2] * twc[2] + P.tlw[i];
     const bool bForward = tlc[2] > P.b && !mono, bBackward = -tlc[2] > P.b && !mono;
-    // "CurrentFrame.mvpMapPoints[i2] && ->Observations() > 0" (so@0x81e3d): a key point taken by a last-frame point WITHOUT observations (a temporal
-    // point of localisation mode) stays available to later points and is overwritten; the relocalisation overload tests the pointer only
-    const uint8_t *obs = RL.on ? nullptr : Lf.obs_positive;
-#define KP_FREE(idx) (claim[idx] == -1 || (obs && claim[idx] >= 0 && !obs[claim[idx]]))
-    for (int k = t; k < F.n; k += T) claim[k] = match[k] < -2 ? -1 : match[k];   // (-3 marks of an earlier check_orientation = 2 call read as free; -2 stays "occupied")
+    const uint8_t *obs = RL.on ? nullptr : Lf.obs_positive;   // (the relocalisation overload tests the pointer only)
+    load_claim(claim, match, F.n);
     if (t < HISTO_LENGTH) hist[t] = 0;
     if (t == 0) s_acc = 0;
     for (int i = t; i < Lf.n; i += T) {
@@ -507,88 +642,39 @@ __global__ void __launch_bounds__(256) k_match_lastframe(const FrameDev *__restr
         done[i] = act ? (uint8_t)(lvl << 1) : 1;   // bit 0: finished, bits 1..: predicted level (relocalisation)
     }
     __syncthreads();
-    for (int round = 0; round <= Lf.n; round++) {
-        for (int k = t; k < F.n; k += T) owner[k] = 0x7fffffff;
-        if (t == 0) s_left = 0;
-        __syncthreads();
-        for (int i = t; i < Lf.n; i += T) {
-            if (done[i] & 1) continue;
-            const float4 pr = proj[i];
-            const int oct = RL.on ? (done[i] >> 1) : Lf.keys[i].octave;
-            const int minL = RL.on ? oct - 1 : (bForward ? oct : (bBackward ? 0 : oct - 1)), maxL = RL.on ? oct + 1 : (bForward ? -1 : (bBackward ? oct : oct + 1));
-            const CellWin w = cell_window(F, pr.x, pr.y, pr.w);
-            if (w.ok) FOR_EACH_CANDIDATE(F, w, pr.x, pr.y, pr.w, minL, maxL, idx, { if (KP_FREE(idx)) atomicMin(&owner[idx], i); })
-        }
-        __syncthreads();
-        for (int i = t; i < Lf.n; i += T) {
-            if (done[i] & 1) continue;
-            const float4 pr = proj[i];
-            const int oct = RL.on ? (done[i] >> 1) : Lf.keys[i].octave;
-            const int minL = RL.on ? oct - 1 : (bForward ? oct : (bBackward ? 0 : oct - 1)), maxL = RL.on ? oct + 1 : (bForward ? -1 : (bBackward ? oct : oct + 1));
-            const CellWin w = cell_window(F, pr.x, pr.y, pr.w);
-            bool safe = true;
-            if (w.ok) FOR_EACH_CANDIDATE(F, w, pr.x, pr.y, pr.w, minL, maxL, idx, { if (KP_FREE(idx) && owner[idx] != i) safe = false; })
-            if (!safe) { atomicAdd(&s_left, 1); continue; }
-            int bestDist = 256, bestIdx2 = -1;
-            const uint8_t *d = Lf.mp_desc + 32 * (size_t)i;
-            if (w.ok) FOR_EACH_CANDIDATE(F, w, pr.x, pr.y, pr.w, minL, maxL, idx, {
-                if (!KP_FREE(idx)) continue;
-                if (F.uright && !RL.on) {
-                    const float urr = F.uright[idx];
-                    if (urr > 0) { const float ur = fmaf(-P.bf, pr.z, pr.x); const float er = fabsf(ur - urr); if (er > pr.w) continue; }
-                }
-                const int dist = hamming_g(d, F.desc + 32 * (size_t)idx);
-                if (dist < bestDist) { bestDist = dist; bestIdx2 = idx; }
-            })
-            done[i] |= 1;
-            proj[i].x = __int_as_float(-1);   // the item's projection is no longer needed: the slot records its assignment
-            if (bestDist <= (RL.on ? RL.orb_dist : TH_HIGH)) {
-                claim[bestIdx2] = i;
-                proj[i].x = __int_as_float(bestIdx2);
-                atomicAdd(&s_acc, 1);
-                if (check_ori) {
-                    float rot = Lf.keys[i].angle - F.keys[bestIdx2].angle;
-                    if (rot < 0.0f) rot += 360.0f;
-                    int bin = (int)roundf(rot * (1.0f / 12.0f));  // this binary: HISTO_LENGTH / 360 (so@0x829b5)
-                    if (bin == HISTO_LENGTH) bin = 0;
-                    atomicAdd(&hist[bin], 1);
-                }
+    auto candidates = [&](int i, auto body) {
+        const float4 pr = proj[i];
+        const int oct = RL.on ? (done[i] >> 1) : Lf.keys[i].octave;
+        const int minL = RL.on ? oct - 1 : (bForward ? oct : (bBackward ? 0 : oct - 1)), maxL = RL.on ? oct + 1 : (bForward ? -1 : (bBackward ? oct : oct + 1));
+        candidates_in_area(F, pr.x, pr.y, pr.w, minL, maxL, [&](int idx, const plf_keypoint &kp) {
+            if (!blocked(claim, idx, obs)) body(idx, kp);
+        });
+    };
+    auto decide = [&](int i) {
+        const float4 pr = proj[i];
+        int bestDist = 256, bestIdx2 = -1;
+        const uint8_t *d = Lf.mp_desc + 32 * (size_t)i;
+        candidates(i, [&](int idx, const plf_keypoint &) {
+            if (F.uright && !RL.on) {
+                const float urr = F.uright[idx];
+                if (urr > 0) { const float ur = fmaf(-P.bf, pr.z, pr.x); const float er = fabsf(ur - urr); if (er > pr.w) return; }
             }
+            const int dist = hamming_g(d, F.desc + 32 * (size_t)idx);
+            if (dist < bestDist) { bestDist = dist; bestIdx2 = idx; }
+        });
+        done[i] |= 1;
+        proj[i].x = __int_as_float(-1);   // the item's projection is no longer needed: the slot records its assignment
+        if (bestDist <= (RL.on ? RL.orb_dist : TH_HIGH)) {
+            claim[bestIdx2] = i;
+            proj[i].x = __int_as_float(bestIdx2);
+            atomicAdd(&s_acc, 1);
+            if (check_ori) atomicAdd(&hist[rot_bin(Lf.keys[i].angle, F.keys[bestIdx2].angle)], 1);
         }
-        __syncthreads();
-        if (s_left == 0) break;
-        __syncthreads();
-    }
-    if (check_ori) {
-        if (t == 0) {  // ComputeThreeMaxima (so@0x823eb)
-            int max1 = 0, max2 = 0, max3 = 0, i1 = -1, i2 = -1, i3 = -1;
-            for (int i = 0; i < HISTO_LENGTH; i++) {
-                const int s = hist[i];
-                if (s > max1) { max3 = max2; max2 = max1; max1 = s; i3 = i2; i2 = i1; i1 = i; }
-                else if (s > max2) { max3 = max2; max2 = s; i3 = i2; i2 = i; }
-                else if (s > max3) { max3 = s; i3 = i; }
-            }
-            if ((float)max2 < 0.1f * (float)max1) { i2 = -1; i3 = -1; }
-            else if ((float)max3 < 0.1f * (float)max1) { i3 = -1; }
-            keepbin[0] = i1; keepbin[1] = i2; keepbin[2] = i3;
-        }
-        __syncthreads();
-        // the reference culls per ASSIGNMENT (rotHist entries): an overwritten key point whose earlier or later assignment falls in a dropped bin
-        // ends up NULL, and nmatches is decremented once per dropped assignment
-        for (int i = t; i < Lf.n; i += T) {
-            const int k = __float_as_int(proj[i].x);
-            if (k < 0 || k >= F.n) continue;
-            float rot = Lf.keys[i].angle - F.keys[k].angle;
-            if (rot < 0.0f) rot += 360.0f;
-            int bin = (int)roundf(rot * (1.0f / 12.0f));
-            if (bin == HISTO_LENGTH) bin = 0;
-            if (bin != keepbin[0] && bin != keepbin[1] && bin != keepbin[2]) { claim[k] = check_ori == 2 ? -3 : -1; atomicSub(&s_acc, 1); }
-        }
-        __syncthreads();
-    }
-    for (int k = t; k < F.n; k += T) match[k] = claim[k];
-    if (t == 0) *nmatches = s_acc;
-#undef KP_FREE
+    };
+    greedy_rounds(Lf.n, F.n, owner, &s_left, done, candidates, decide);
+    if (check_ori)
+        lf_orientation_cull(F, Lf, check_ori, hist, keepbin, claim, &s_acc, [&](int i) { const int k = __float_as_int(proj[i].x); return k < F.n ? k : -1; });
+    store_claim(match, claim, F.n, nmatches, &s_acc);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -612,6 +698,8 @@ __global__ void __launch_bounds__(256) k_lf_candidates(const FrameDev *__restric
     const plf_pose_pair P = poses[f];
     const int *claim = match_all + (size_t)f * kp_stride;   // occupancy before this call
     uint32_t *cand = cand_all + (size_t)f * cand_cap;
+    // the projection of k_match_lastframe's first phase, statement for statement: a change to it is made there and here (through shared functions this
+    // kernel came out with other code, 0.5 % slower in the batch step and 1.4 % with one frame in flight, above the run-to-run spread)
     float twc[3], tlc[3];
     for (int k = 0; k < 3; k++)
         twc[k] = (float)(-((double)P.Rcw[k] * P.tcw[0] + (double)P.Rcw[3 + k] * P.tcw[1] + (double)P.Rcw[6 + k] * P.tcw[2]));
@@ -674,7 +762,7 @@ __global__ void __launch_bounds__(256) k_lf_rounds(const FrameDev *__restrict__ 
     int *claim = (int *)smem, *owner = claim + kp_cap;
     uint16_t *la = (uint16_t *)(owner + kp_cap), *lb = la + item_cap, *assign = lb + item_cap;
     __shared__ int s_n[2], s_acc, hist[HISTO_LENGTH], keepbin[3];
-    const int f = blockIdx.x, t = threadIdx.x, T = blockDim.x, lane = plf_lane();
+    const int f = blockIdx.x, t = threadIdx.x, T = blockDim.x;
     if (overflow[f]) return;
     FrameDev F = frames[f];
     if (F.n_dev) F.n = min(F.n, *F.n_dev);
@@ -683,26 +771,18 @@ __global__ void __launch_bounds__(256) k_lf_rounds(const FrameDev *__restrict__ 
     const uint32_t *cand = cand_all + (size_t)f * cand_cap;
     const int2 *span = span_all + (size_t)f * item_stride;
     const uint8_t *obs = Lf.obs_positive;
-    for (int k = t; k < F.n; k += T) claim[k] = match[k] < -2 ? -1 : match[k];   // (-3 marks of an earlier check_orientation = 2 call read as free; -2 stays "occupied")
+    load_claim(claim, match, F.n);
     for (int i = t; i < Lf.n; i += T) assign[i] = 0xFFFFu;
     if (t < HISTO_LENGTH) hist[t] = 0;
     if (t == 0) { s_acc = 0; s_n[0] = 0; s_n[1] = 0; }
     __syncthreads();
-    for (int m0 = 0; m0 < Lf.n; m0 += T) {
-        const int m = m0 + t;
-        const bool un = m < Lf.n && !done[m];
-        const unsigned long long mask = __ballot(un);
-        int base = 0;
-        if (lane == 0 && mask) base = atomicAdd(&s_n[0], __popcll(mask));
-        base = __shfl(base, 0, 64);
-        if (un) la[base + __popcll(mask & ((1ull << lane) - 1ull))] = (uint16_t)m;
-    }
+    list_unfinished(Lf.n, done, la, &s_n[0]);
     __syncthreads();
     int cur = 0;
     for (int round = 0; round <= Lf.n; round++) {
         const int nact = s_n[cur];
         if (nact == 0) break;
-        for (int k = t; k < F.n; k += T) owner[k] = 0x7fffffff;
+        reset_owner(owner, F.n);
         __syncthreads();
         for (int q = t; q < nact; q += T) {
             const int i = la[q];
@@ -734,20 +814,10 @@ __global__ void __launch_bounds__(256) k_lf_rounds(const FrameDev *__restrict__ 
                     claim[bestIdx] = i;   // only this point can touch bestIdx in this round
                     assign[i] = (uint16_t)bestIdx;
                     atomicAdd(&s_acc, 1);
-                    if (check_ori) {
-                        float rot = Lf.keys[i].angle - F.keys[bestIdx].angle;
-                        if (rot < 0.0f) rot += 360.0f;
-                        int bin = (int)roundf(rot * (1.0f / 12.0f));  // this binary: HISTO_LENGTH / 360 (so@0x829b5)
-                        if (bin == HISTO_LENGTH) bin = 0;
-                        atomicAdd(&hist[bin], 1);
-                    }
+                    if (check_ori) atomicAdd(&hist[rot_bin(Lf.keys[i].angle, F.keys[bestIdx].angle)], 1);
                 }
             }
-            const unsigned long long mask = __ballot(keep);
-            int base = 0;
-            if (lane == 0 && mask) base = atomicAdd(&s_n[cur ^ 1], __popcll(mask));
-            base = __shfl(base, 0, 64);
-            if (keep) lb[base + __popcll(mask & ((1ull << lane) - 1ull))] = (uint16_t)i;
+            wave_append(keep, i, lb, &s_n[cur ^ 1]);
         }
         __syncthreads();
         if (t == 0) s_n[cur] = 0;
@@ -755,33 +825,9 @@ __global__ void __launch_bounds__(256) k_lf_rounds(const FrameDev *__restrict__ 
         cur ^= 1;
         __syncthreads();
     }
-    if (check_ori) {
-        if (t == 0) {  // ComputeThreeMaxima (so@0x823eb)
-            int max1 = 0, max2 = 0, max3 = 0, i1 = -1, i2 = -1, i3 = -1;
-            for (int b = 0; b < HISTO_LENGTH; b++) {
-                const int sz = hist[b];
-                if (sz > max1) { max3 = max2; max2 = max1; max1 = sz; i3 = i2; i2 = i1; i1 = b; }
-                else if (sz > max2) { max3 = max2; max2 = sz; i3 = i2; i2 = b; }
-                else if (sz > max3) { max3 = sz; i3 = b; }
-            }
-            if ((float)max2 < 0.1f * (float)max1) { i2 = -1; i3 = -1; }
-            else if ((float)max3 < 0.1f * (float)max1) { i3 = -1; }
-            keepbin[0] = i1; keepbin[1] = i2; keepbin[2] = i3;
-        }
-        __syncthreads();
-        for (int i = t; i < Lf.n; i += T) {   // per ASSIGNMENT, as the reference's rotHist entries
-            const int k = assign[i];
-            if (k == 0xFFFF) continue;
-            float rot = Lf.keys[i].angle - F.keys[k].angle;
-            if (rot < 0.0f) rot += 360.0f;
-            int bin = (int)roundf(rot * (1.0f / 12.0f));
-            if (bin == HISTO_LENGTH) bin = 0;
-            if (bin != keepbin[0] && bin != keepbin[1] && bin != keepbin[2]) { claim[k] = check_ori == 2 ? -3 : -1; atomicSub(&s_acc, 1); }
-        }
-        __syncthreads();
-    }
-    for (int k = t; k < F.n; k += T) match[k] = claim[k];
-    if (t == 0) nmatches[f] = s_acc;
+    if (check_ori)
+        lf_orientation_cull(F, Lf, check_ori, hist, keepbin, claim, &s_acc, [&](int i) { const int k = assign[i]; return k == 0xFFFF ? -1 : k; });
+    store_claim(match, claim, F.n, &nmatches[f], &s_acc);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -843,28 +889,27 @@ __global__ void __launch_bounds__(256) k_project_kf(FrameDev F, Pts3Dev P, ProjK
     int bestDist = 256, bestIdx = -1, lvl = 0;
     float u = 0.f, v = 0.f, invz = 0.f, radius = 0.f;
     if (project_gate(F, P, C, th, i, u, v, invz, lvl, radius)) {
-        const CellWin w = cell_window(F, u, v, radius);
         const uint8_t *d = P.desc + 32 * (size_t)i;
-        if (w.ok) FOR_EACH_CANDIDATE(F, w, u, v, radius, -1, -1, idx, {
-            const int kpLevel = _kp.octave;
-            if (kpLevel < lvl - 1 || kpLevel > lvl) continue;
+        candidates_in_area(F, u, v, radius, -1, -1, [&](int idx, const plf_keypoint &kp) {
+            const int kpLevel = kp.octave;
+            if (kpLevel < lvl - 1 || kpLevel > lvl) return;
             if (C.chi2) {
-                const float ey = v - _kp.y;
-                const float ex = u - _kp.x;
+                const float ey = v - kp.y;
+                const float ex = u - kp.x;
                 const float kur = F.uright ? F.uright[idx] : -1.f;
                 if (kur >= 0.0f) {
                     const float ur = fmaf(-C.bf, invz, u);   // so@0x7b63e
                     const float er = ur - kur;
                     const float e2 = fmaf(er, er, fmaf(ex, ex, ey * ey));
-                    if ((double)(e2 * C.inv_sigma2[kpLevel]) > 7.8) continue;
+                    if ((double)(e2 * C.inv_sigma2[kpLevel]) > 7.8) return;
                 } else {
                     const float e2 = fmaf(ex, ex, ey * ey);
-                    if ((double)(e2 * C.inv_sigma2[kpLevel]) > 5.99) continue;
+                    if ((double)(e2 * C.inv_sigma2[kpLevel]) > 5.99) return;
                 }
             }
             const int dist = hamming_g(d, F.desc + 32 * (size_t)idx);
             if (dist < bestDist) { bestDist = dist; bestIdx = idx; }
-        })
+        });
     }
     const bool hit = bestIdx >= 0 && bestDist <= C.accept;
     best_idx[i] = hit ? bestIdx : -1;
@@ -883,7 +928,7 @@ __global__ void __launch_bounds__(256) k_project_kf_greedy(FrameDev F, Pts3Dev P
     __shared__ int s_left, s_acc;
     const int t = threadIdx.x, T = blockDim.x;
     if (F.n_dev) F.n = min(F.n, *F.n_dev);
-    for (int k = t; k < F.n; k += T) claim[k] = match[k] < -2 ? -1 : match[k];   // (-3 marks of an earlier check_orientation = 2 call read as free; -2 stays "occupied")
+    load_claim(claim, match, F.n);
     if (t == 0) s_acc = 0;
     for (int i = t; i < P.m; i += T) {
         float u = 0.f, v = 0.f, invz = 0.f, radius = 0.f;
@@ -893,49 +938,27 @@ __global__ void __launch_bounds__(256) k_project_kf_greedy(FrameDev F, Pts3Dev P
         done[i] = act ? 0 : 1;
     }
     __syncthreads();
-    for (int round = 0; round <= P.m; round++) {
-        for (int k = t; k < F.n; k += T) owner[k] = 0x7fffffff;
-        if (t == 0) s_left = 0;
-        __syncthreads();
-        for (int i = t; i < P.m; i += T) {
-            if (done[i]) continue;
-            const float4 pr = proj[i];
-            const int lvl = __float_as_int(pr.w);
-            const CellWin w = cell_window(F, pr.x, pr.y, pr.z);
-            if (w.ok) FOR_EACH_CANDIDATE(F, w, pr.x, pr.y, pr.z, -1, -1, idx, {
-                if (_kp.octave < lvl - 1 || _kp.octave > lvl) continue;
-                if (claim[idx] == -1) atomicMin(&owner[idx], i);
-            })
-        }
-        __syncthreads();
-        for (int i = t; i < P.m; i += T) {
-            if (done[i]) continue;
-            const float4 pr = proj[i];
-            const int lvl = __float_as_int(pr.w);
-            const CellWin w = cell_window(F, pr.x, pr.y, pr.z);
-            bool safe = true;
-            if (w.ok) FOR_EACH_CANDIDATE(F, w, pr.x, pr.y, pr.z, -1, -1, idx, {
-                if (_kp.octave < lvl - 1 || _kp.octave > lvl) continue;
-                if (claim[idx] == -1 && owner[idx] != i) safe = false;
-            })
-            if (!safe) { atomicAdd(&s_left, 1); continue; }
-            int bestDist = 256, bestIdx = -1;
-            const uint8_t *d = P.desc + 32 * (size_t)i;
-            if (w.ok) FOR_EACH_CANDIDATE(F, w, pr.x, pr.y, pr.z, -1, -1, idx, {
-                if (claim[idx] != -1) continue;
-                if (_kp.octave < lvl - 1 || _kp.octave > lvl) continue;
-                const int dist = hamming_g(d, F.desc + 32 * (size_t)idx);
-                if (dist < bestDist) { bestDist = dist; bestIdx = idx; }
-            })
-            done[i] = 1;
-            if (bestIdx >= 0 && bestDist <= C.accept) { claim[bestIdx] = i; atomicAdd(&s_acc, 1); }
-        }
-        __syncthreads();
-        if (s_left == 0) break;
-        __syncthreads();
-    }
-    for (int k = t; k < F.n; k += T) match[k] = claim[k];
-    if (t == 0) *nmatches = s_acc;
+    // KeyFrame::GetFeaturesInArea has no level filter: the predicted level and the one below are tested here; vpMatched holds plain pointers (no obs_positive)
+    auto candidates = [&](int i, auto body) {
+        const float4 pr = proj[i];
+        const int lvl = __float_as_int(pr.w);
+        candidates_in_area(F, pr.x, pr.y, pr.z, -1, -1, [&](int idx, const plf_keypoint &kp) {
+            if (kp.octave < lvl - 1 || kp.octave > lvl) return;
+            if (!blocked(claim, idx, nullptr)) body(idx, kp);
+        });
+    };
+    auto decide = [&](int i) {
+        int bestDist = 256, bestIdx = -1;
+        const uint8_t *d = P.desc + 32 * (size_t)i;
+        candidates(i, [&](int idx, const plf_keypoint &) {
+            const int dist = hamming_g(d, F.desc + 32 * (size_t)idx);
+            if (dist < bestDist) { bestDist = dist; bestIdx = idx; }
+        });
+        done[i] = 1;
+        if (bestIdx >= 0 && bestDist <= C.accept) { claim[bestIdx] = i; atomicAdd(&s_acc, 1); }
+    };
+    greedy_rounds(P.m, F.n, owner, &s_left, done, candidates, decide);
+    store_claim(match, claim, F.n, nmatches, &s_acc);
 }
 
 // SearchBySim3, last loop (so@0x838b0): a pair stands when both directions chose each other
@@ -1087,32 +1110,21 @@ __global__ void __launch_bounds__(256) k_match_bow(const BowDev *__restrict__ pa
     }
     __syncthreads();
     if (check_ori) {
-        for (int pass = 0; pass < 2; pass++) {
-            for (int j = t; j < nslot; j += T) {
-                const int i = match[j];
-                if (i < 0) continue;
-                float rot = kfkf == 2 ? TR.keys1[j].angle - TR.keys2[i].angle : (kfkf ? P.kf_angle[j] - P.f_angle[i] : P.kf_angle[i] - P.f_angle[j]);
-                if (rot < 0.0f) rot += 360.0f;
-                int bin = (int)roundf(rot * (1.0f / 12.0f));
-                if (bin == HISTO_LENGTH) bin = 0;
-                if (pass == 0) atomicAdd(&hist[bin], 1);
-                else if (bin != keepbin[0] && bin != keepbin[1] && bin != keepbin[2]) { match[j] = -1; atomicSub(&s_acc, 1); }
-            }
-            __syncthreads();
-            if (pass == 0 && t == 0) {  // ComputeThreeMaxima (so@0x79c40)
-                int max1 = 0, max2 = 0, max3 = 0, i1 = -1, i2 = -1, i3 = -1;
-                for (int i = 0; i < HISTO_LENGTH; i++) {
-                    const int sz = hist[i];
-                    if (sz > max1) { max3 = max2; max2 = max1; max1 = sz; i3 = i2; i2 = i1; i1 = i; }
-                    else if (sz > max2) { max3 = max2; max2 = sz; i3 = i2; i2 = i; }
-                    else if (sz > max3) { max3 = sz; i3 = i; }
-                }
-                if ((float)max2 < 0.1f * (float)max1) { i2 = -1; i3 = -1; }
-                else if ((float)max3 < 0.1f * (float)max1) { i3 = -1; }
-                keepbin[0] = i1; keepbin[1] = i2; keepbin[2] = i3;
-            }
-            __syncthreads();
+        // slot j holds i = match[j]; the angle pair of the assignment by overload
+        auto bin = [&](int j, int i) {
+            const float a1 = kfkf == 2 ? TR.keys1[j].angle : (kfkf ? P.kf_angle[j] : P.kf_angle[i]);
+            const float a2 = kfkf == 2 ? TR.keys2[i].angle : (kfkf ? P.f_angle[i] : P.f_angle[j]);
+            return rot_bin(a1, a2);
+        };
+        for (int j = t; j < nslot; j += T) {
+            const int i = match[j];
+            if (i >= 0) atomicAdd(&hist[bin(j, i)], 1);
         }
+        __syncthreads();
+        if (t == 0) three_maxima(hist, keepbin);
+        __syncthreads();
+        rot_cull(nslot, keepbin, &s_acc, [&](int j) { return match[j]; }, bin, [&](int j, int) { match[j] = -1; });
+        __syncthreads();
     }
     if (t == 0) nmatches[pr] = s_acc;
 }
@@ -1292,22 +1304,16 @@ __global__ void __launch_bounds__(256) k_lines_fuse_pick(const int *__restrict__
     if (plf_lane() == 0 && mk) atomicAdd(nfused, __popcll(mk));
 }
 
-// Frame::GetLinesInArea test for line i
-__device__ __forceinline__ bool line_in_area(const plf_keyline &kl, float x1, float y1, float x2, float y2, float r, int minLevel, int maxLevel)
+// the four fields of key line k that the window test reads (x = pt_x, y = pt_y, z = angle, w = octave bits)
+__device__ __forceinline__ float4 line_fields(const plf_keyline &kl) { return make_float4(kl.pt_x, kl.pt_y, kl.angle, __int_as_float(kl.octave)); }
+// key line k into LDS: its fields in lg[k], the two halves of its descriptor in ld[2k], ld[2k + 1] (56 bytes per line)
+__device__ __forceinline__ void stage_line(const LineFrameDev &F, int k, float4 *lg, uint4 *ld)
 {
-    const double dx = 0.5 * (double)(x1 + x2) - (double)kl.pt_x, dy = 0.5 * (double)(y1 + y2) - (double)kl.pt_y;
-    const double distance = dx * dx + dy * dy;
-    if (distance > (double)(r * r)) return false;
-    const float slope = (y1 - y2) / (x1 - x2) - kl.angle;
-    if ((double)slope > (double)r * 0.01) return false;
-    if ((minLevel > 0) || (maxLevel > 0)) {
-        if (kl.octave < minLevel) return false;
-        if (maxLevel >= 0 && kl.octave > maxLevel) return false;
-    }
-    return true;
+    lg[k] = line_fields(F.lines[k]);
+    const uint4 *dsrc = reinterpret_cast<const uint4 *>(F.desc + 32 * (size_t)k);
+    ld[2 * k] = dsrc[0]; ld[2 * k + 1] = dsrc[1];
 }
-
-// the same test on the four fields of a key line staged in LDS (x = pt_x, y = pt_y, z = angle, w = octave bits): identical arithmetic
+// Frame::GetLinesInArea test on those four fields
 __device__ __forceinline__ bool line_in_area4(const float4 kl, float x1, float y1, float x2, float y2, float r, int minLevel, int maxLevel)
 {
     const double dx = 0.5 * (double)(x1 + x2) - (double)kl.x, dy = 0.5 * (double)(y1 + y2) - (double)kl.y;
@@ -1324,7 +1330,10 @@ __device__ __forceinline__ bool line_in_area4(const float4 kl, float x1, float y
 }
 
 // STAGED: the frame's lines live in LDS (56 bytes per line; host: while line_cap * 56 fits the 150 KB the kernel may ask for, i.e. up to 2688 lines); otherwise
-// they are read from global memory as before round 5 (8 bytes of LDS per line: plf_matcher_create accepts max_lines up to 18000 -- ADVICE r05)
+// they are read from global memory (8 bytes of LDS per line: plf_matcher_create accepts max_lines up to 18000)
+// The round loop is written out here and in k_match_project_lines_w, not greedy_rounds: an item's candidates are ALL lines of the frame, the safety pass
+// tests owner[i] before the double-precision window test (greedy_rounds asks for the candidates first and the owner second), and the wave kernel spreads
+// one item over 64 lanes.  They share the claim array, reset_owner, map_radius, line_in_area4, hamming_g and accept_best_of_two with the rest.
 template <bool STAGED>
 __device__ __forceinline__ void match_project_lines_body(const LineFrameDev *__restrict__ frames, MapLineDev ML, float th, float nnratio,
                                                              int *__restrict__ match_all, int line_stride, int *__restrict__ nmatches,
@@ -1343,68 +1352,49 @@ __device__ __forceinline__ void match_project_lines_body(const LineFrameDev *__r
     if (F.n_dev) F.n = min(F.n, *F.n_dev);
     int *match = match_all + (size_t)f * line_stride;
     uint8_t *done = done_all + (size_t)f * ML.m;
-    const bool bFactor = th != 1.0f;
-    for (int k = t; k < F.n; k += T) {
-        claim[k] = match[k] < -2 ? -1 : match[k];   // (-3 marks of an earlier check_orientation = 2 call read as free; -2 stays "occupied")
-        if (STAGED) {
-            const plf_keyline kl = F.lines[k];
-            lg[k] = make_float4(kl.pt_x, kl.pt_y, kl.angle, __int_as_float(kl.octave));
-            const uint4 *dsrc = reinterpret_cast<const uint4 *>(F.desc + 32 * (size_t)k);
-            ld[2 * k] = dsrc[0]; ld[2 * k + 1] = dsrc[1];
-        }
-    }
+    load_claim(claim, match, F.n, [&](int k) { if (STAGED) stage_line(F, k, lg, ld); });
     // the four window-test fields / the two descriptor halves of key line i
-    auto line4 = [&](int i) -> float4 {
-        if (STAGED) return lg[i];
-        const plf_keyline &kl = F.lines[i];
-        return make_float4(kl.pt_x, kl.pt_y, kl.angle, __int_as_float(kl.octave));
-    };
+    auto line4 = [&](int i) -> float4 { return STAGED ? lg[i] : line_fields(F.lines[i]); };
     auto desc_half = [&](int i, int hlf) -> uint4 { return STAGED ? ld[2 * i + hlf] : reinterpret_cast<const uint4 *>(F.desc + 32 * (size_t)i)[hlf]; };
     if (t == 0) s_acc = 0;
     for (int m = t; m < ML.m; m += T) done[m] = ML.in_view[m] ? 0 : 1;
     __syncthreads();
     for (int round = 0; round <= ML.m; round++) {
-        for (int k = t; k < F.n; k += T) owner[k] = 0x7fffffff;
+        reset_owner(owner, F.n);
         if (t == 0) s_left = 0;
         __syncthreads();
         for (int m = t; m < ML.m; m += T) {
             if (done[m]) continue;
             const int lvl = ML.level[m];
-            float r = radius_by_viewing_cos(ML.view_cos[m]);
-            if (bFactor) r *= th;
-            const float rad = r * F.scale_factors[lvl];
+            const float rad = map_radius(ML.view_cos[m], th, F.scale_factors[lvl]);
             const float mx1 = ML.x1[m], my1 = ML.y1[m], mx2 = ML.x2[m], my2 = ML.y2[m];
             for (int i = 0; i < F.n; i++)
-                if (claim[i] == -1 && line_in_area4(line4(i), mx1, my1, mx2, my2, rad, lvl - 1, lvl)) atomicMin(&owner[i], m);
+                if (free_slot(claim, i) && line_in_area4(line4(i), mx1, my1, mx2, my2, rad, lvl - 1, lvl)) atomicMin(&owner[i], m);
         }
         __syncthreads();
         for (int m = t; m < ML.m; m += T) {
             if (done[m]) continue;
             const int lvl = ML.level[m];
-            float r = radius_by_viewing_cos(ML.view_cos[m]);
-            if (bFactor) r *= th;
-            const float rad = r * F.scale_factors[lvl];
+            const float rad = map_radius(ML.view_cos[m], th, F.scale_factors[lvl]);
             const float mx1 = ML.x1[m], my1 = ML.y1[m], mx2 = ML.x2[m], my2 = ML.y2[m];
             bool safe = true;
             for (int i = 0; i < F.n; i++)
-                if (claim[i] == -1 && owner[i] != m && line_in_area4(line4(i), mx1, my1, mx2, my2, rad, lvl - 1, lvl)) safe = false;
+                if (free_slot(claim, i) && owner[i] != m && line_in_area4(line4(i), mx1, my1, mx2, my2, rad, lvl - 1, lvl)) safe = false;
             if (!safe) { atomicAdd(&s_left, 1); continue; }
             int bestDist = 256, bestLevel = -1, bestDist2 = 256, bestLevel2 = -1, bestIdx = -1;
             const uint4 d0 = reinterpret_cast<const uint4 *>(ML.desc + 32 * (size_t)m)[0], d1 = reinterpret_cast<const uint4 *>(ML.desc + 32 * (size_t)m)[1];
             for (int i = 0; i < F.n; i++) {
-                if (claim[i] != -1) continue;
+                if (!free_slot(claim, i)) continue;
                 const float4 kl = line4(i);
                 if (!line_in_area4(kl, mx1, my1, mx2, my2, rad, lvl - 1, lvl)) continue;
                 const uint4 b0 = desc_half(i, 0), b1 = desc_half(i, 1);
-                const int dist = __popc(d0.x ^ b0.x) + __popc(d0.y ^ b0.y) + __popc(d0.z ^ b0.z) + __popc(d0.w ^ b0.w) + __popc(d1.x ^ b1.x) + __popc(d1.y ^ b1.y) +
-                                 __popc(d1.z ^ b1.z) + __popc(d1.w ^ b1.w);
+                const int dist = hamming_g(d0, d1, b0, b1);
                 const int oct = __float_as_int(kl.w);
                 if (dist < bestDist) { bestDist2 = bestDist; bestDist = dist; bestLevel2 = bestLevel; bestLevel = oct; bestIdx = i; }
                 else if (dist < bestDist2) { bestLevel2 = oct; bestDist2 = dist; }
             }
             done[m] = 1;
-            if (bestDist <= TH_HIGH) {
-                if (bestLevel == bestLevel2 && (float)bestDist > nnratio * (float)bestDist2) continue;
+            if (accept_best_of_two(bestDist, bestLevel, bestDist2, bestLevel2, nnratio)) {
                 claim[bestIdx] = m;
                 atomicAdd(&s_acc, 1);
             }
@@ -1413,8 +1403,7 @@ __device__ __forceinline__ void match_project_lines_body(const LineFrameDev *__r
         if (s_left == 0) break;
         __syncthreads();
     }
-    for (int k = t; k < F.n; k += T) match[k] = claim[k];
-    if (t == 0) nmatches[f] = s_acc;
+    store_claim(match, claim, F.n, &nmatches[f], &s_acc);
 }
 
 __global__ void __launch_bounds__(256) k_match_project_lines(const LineFrameDev *__restrict__ frames, MapLineDev ML, float th, float nnratio,
@@ -1456,53 +1445,40 @@ __global__ void __launch_bounds__(1024) k_match_project_lines_w(const LineFrameD
     if (F.n_dev) F.n = min(F.n, *F.n_dev);
     int *match = match_all + (size_t)f * line_stride;
     uint8_t *done = done_all + (size_t)f * ML.m;
-    const bool bFactor = th != 1.0f;
-    for (int k = t; k < F.n; k += T) {
-        claim[k] = match[k] < -2 ? -1 : match[k];
-        const plf_keyline kl = F.lines[k];
-        lg[k] = make_float4(kl.pt_x, kl.pt_y, kl.angle, __int_as_float(kl.octave));
-        const uint4 *dsrc = reinterpret_cast<const uint4 *>(F.desc + 32 * (size_t)k);
-        ld[2 * k] = dsrc[0]; ld[2 * k + 1] = dsrc[1];
-    }
+    load_claim(claim, match, F.n, [&](int k) { stage_line(F, k, lg, ld); });
     if (t == 0) s_acc = 0;
     for (int m = t; m < ML.m; m += T) done[m] = ML.in_view[m] ? 0 : 1;
     __syncthreads();
     const int nchunk = (F.n + 63) >> 6;
     for (int round = 0; round <= ML.m; round++) {
-        for (int k = t; k < F.n; k += T) owner[k] = 0x7fffffff;
+        reset_owner(owner, F.n);
         if (t == 0) s_left = 0;
         __syncthreads();
         for (int m = wv; m < ML.m; m += NW) {
             if (done[m]) continue;
             const int lvl = ML.level[m];
-            float r = radius_by_viewing_cos(ML.view_cos[m]);
-            if (bFactor) r *= th;
-            const float rad = r * F.scale_factors[lvl];
+            const float rad = map_radius(ML.view_cos[m], th, F.scale_factors[lvl]);
             const float mx1 = ML.x1[m], my1 = ML.y1[m], mx2 = ML.x2[m], my2 = ML.y2[m];
             for (int c = 0; c < nchunk; c++) {
                 const int i = c * 64 + lane;
-                if (i < F.n && claim[i] == -1 && line_in_area4(lg[i], mx1, my1, mx2, my2, rad, lvl - 1, lvl)) atomicMin(&owner[i], m);
+                if (i < F.n && free_slot(claim, i) && line_in_area4(lg[i], mx1, my1, mx2, my2, rad, lvl - 1, lvl)) atomicMin(&owner[i], m);
             }
         }
         __syncthreads();
         for (int m = wv; m < ML.m; m += NW) {
             if (done[m]) continue;
             const int lvl = ML.level[m];
-            float r = radius_by_viewing_cos(ML.view_cos[m]);
-            if (bFactor) r *= th;
-            const float rad = r * F.scale_factors[lvl];
+            const float rad = map_radius(ML.view_cos[m], th, F.scale_factors[lvl]);
             const float mx1 = ML.x1[m], my1 = ML.y1[m], mx2 = ML.x2[m], my2 = ML.y2[m];
             const uint4 d0 = reinterpret_cast<const uint4 *>(ML.desc + 32 * (size_t)m)[0], d1 = reinterpret_cast<const uint4 *>(ML.desc + 32 * (size_t)m)[1];
             bool unsafe = false;
             int k1 = 0x7fffffff, k2 = 0x7fffffff;      // this lane's two smallest keys (distance << 16 | line); its lines come in ascending order
             for (int c = 0; c < nchunk; c++) {
                 const int i = c * 64 + lane;
-                const bool cand = i < F.n && claim[i] == -1 && line_in_area4(lg[i], mx1, my1, mx2, my2, rad, lvl - 1, lvl);
+                const bool cand = i < F.n && free_slot(claim, i) && line_in_area4(lg[i], mx1, my1, mx2, my2, rad, lvl - 1, lvl);
                 if (cand) {
                     if (owner[i] != m) unsafe = true;
-                    const uint4 b0 = ld[2 * i], b1 = ld[2 * i + 1];
-                    const int dist = __popc(d0.x ^ b0.x) + __popc(d0.y ^ b0.y) + __popc(d0.z ^ b0.z) + __popc(d0.w ^ b0.w) + __popc(d1.x ^ b1.x) + __popc(d1.y ^ b1.y) +
-                                     __popc(d1.z ^ b1.z) + __popc(d1.w ^ b1.w);
+                    const int dist = hamming_g(d0, d1, ld[2 * i], ld[2 * i + 1]);
                     if (dist < 256) {                  // (a distance of 256 never enters the reference's `dist < 256` chain)
                         const int key = (dist << 16) | i;
                         if (key < k1) { k2 = k1; k1 = key; } else if (key < k2) k2 = key;
@@ -1518,7 +1494,7 @@ __global__ void __launch_bounds__(1024) k_match_project_lines_w(const LineFrameD
                     const int bestDist = kb >> 16, bestIdx = kb & 0xFFFF;
                     const int bestLevel = __float_as_int(lg[bestIdx].w);
                     const int bestDist2 = ks != 0x7fffffff ? ks >> 16 : 256, bestLevel2 = ks != 0x7fffffff ? __float_as_int(lg[ks & 0xFFFF].w) : -1;
-                    if (bestDist <= TH_HIGH && !(bestLevel == bestLevel2 && (float)bestDist > nnratio * (float)bestDist2)) {
+                    if (accept_best_of_two(bestDist, bestLevel, bestDist2, bestLevel2, nnratio)) {
                         claim[bestIdx] = m;
                         atomicAdd(&s_acc, 1);
                     }
@@ -1529,8 +1505,7 @@ __global__ void __launch_bounds__(1024) k_match_project_lines_w(const LineFrameD
         if (s_left == 0) break;
         __syncthreads();
     }
-    for (int k = t; k < F.n; k += T) match[k] = claim[k];
-    if (t == 0) nmatches[f] = s_acc;
+    store_claim(match, claim, F.n, &nmatches[f], &s_acc);
 }
 
 __global__ void __launch_bounds__(256) k_hamming_matrix(const uint8_t *__restrict__ a, int na, const uint8_t *__restrict__ b, int nb,
