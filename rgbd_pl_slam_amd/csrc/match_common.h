@@ -12,6 +12,9 @@
 // flat_walk reads the CSR offsets of WALK_COLS window columns per trip without clamping the last ones: the table of all frames ends in WALK_COLS columns
 // of padding (a frame's read-ahead lands in the next frame's row; what is read past the window is never used)
 #define WALK_COLS 4
+// k_mp_rounds: threads of its one block per frame, and the default number of list entries a frame may bring into LDS (plf_matcher_create)
+#define MP_ROUNDS_THREADS 512
+#define MP_ROUNDS_LDS_ENTRIES 10240
 
 struct FrameDev {
     int n;
@@ -74,10 +77,10 @@ struct MapLineDev { int m; const float *x1, *y1, *x2, *y2; const int *level; con
 
 // ---- kernels (match_kernels.hip)
 __global__ void k_build_grid(const FrameDev *frames, int *cell_start_all, int *cell_idx_all, int *cell_of_all, int kp_stride);
-__global__ void k_mp_candidates(const FrameDev *frames, MapDev MP, float th, const int *match_all, int kp_stride, uint8_t *done_all, uint32_t *cand_all, int2 *span_all, int cand_cap, int *overflow,
-                                int *total);
+__global__ void k_mp_candidates(const FrameDev *frames, MapDev MP, float th, float nnratio, const int *match_all, int kp_stride, uint8_t *done_all, uint32_t *cand_all, int2 *span_all,
+                                int cand_cap, int *overflow, int *total, int *kept);
 __global__ void k_mp_rounds(const FrameDev *frames, MapDev MP, float nnratio, int *match_all, int kp_stride, int *nmatches, const uint8_t *done_all, int kp_cap, const uint32_t *cand_all,
-                            const int2 *span_all, int cand_cap, const int *overflow, unsigned long long *top2_all, int top2_stride);
+                            const int2 *span_all, int cand_cap, const int *overflow, const int *kept, int budget);
 __global__ void k_match_project_points_slow(const FrameDev *frames, MapDev MP, float th, float nnratio, int *match_all, int kp_stride, int *nmatches, uint8_t *done_all, int kp_cap,
                                             const int *overflow);
 __global__ void k_match_lastframe(const FrameDev *frames, LastDev Lf, const plf_pose_pair *poses, RelocDev RL, float th, int mono, int check_ori, int *match_all, int kp_stride, int *nmatches_all,

@@ -1,6 +1,7 @@
 // match_host.hip -- host side of the matchers: scratch handle, grid construction, launch sequence, C ABI.
 // Mirrors the tracking overloads of ORB_SLAM2::ORBmatcher (include/ORBmatcher.h:44,61,78) and
 // ORB_SLAM2::LSDmatcher (include/LSDmatcher.h:32,40,43).
+#include <algorithm>
 #include <math.h>
 #include <stdlib.h>
 #include <string.h>
@@ -23,9 +24,9 @@ struct plf_matcher {
     plf_dmatch *d_dm;
     double *d_mad;
     uint32_t *d_cand;        // cached candidate lists of the projection matcher
-    unsigned long long *d_top2;   // [frame][max_mappoints]: the two best free candidates of every unfinished map point in the current round (k_mp_rounds)
     int *d_cand_off, *d_overflow;
     int cand_cap;
+    int rounds_lds;          // list entries a frame may bring into the LDS of k_mp_rounds; a frame with more runs its rounds on the pool
     FrameDev *h_frames;      // host copy of the frame table last uploaded (skips the upload + sync when unchanged)
     LineFrameDev *h_lframes;
     int h_nframes, h_nlframes;
@@ -52,7 +53,7 @@ static int matcher_stream(plf_matcher *h, void *stream, hipStream_t *out)
 
 static void matcher_free(plf_matcher *h)
 {
-    void *ptrs[] = {h->d_frames, h->d_lframes, h->d_cell_start, h->d_cell_idx, h->d_cell_of, h->d_knn_idx, h->d_knn_dist, h->d_done, h->d_proj, h->d_dm, h->d_mad, h->d_cand, h->d_top2, h->d_cand_off, h->d_overflow, h->d_cell_kp, h->d_bow, h->d_bow_fnode, h->d_bow_used};
+    void *ptrs[] = {h->d_frames, h->d_lframes, h->d_cell_start, h->d_cell_idx, h->d_cell_of, h->d_knn_idx, h->d_knn_dist, h->d_done, h->d_proj, h->d_dm, h->d_mad, h->d_cand, h->d_cand_off, h->d_overflow, h->d_cell_kp, h->d_bow, h->d_bow_fnode, h->d_bow_used};
     for (void *p : ptrs) if (p) (void)hipFree(p);
     for (auto &ps : h->pose_ring) { if (ps.d) (void)hipFree(ps.d); if (ps.h) (void)hipHostFree(ps.h); if (ps.ev) (void)hipEventDestroy(ps.ev); }
     if (h->stream) (void)hipStreamDestroy(h->stream);
@@ -113,8 +114,11 @@ extern "C" int plf_matcher_create(int32_t device, int32_t max_keypoints, int32_t
     h->cand_cap = cand_avg * max_mappoints;
     ALLOC(h->d_cand, B * (size_t)h->cand_cap * sizeof(uint32_t));
     ALLOC(h->d_cand_off, B * (size_t)max_mappoints * sizeof(int2));   // (start, count) of every map point's span in the pool
-    ALLOC(h->d_top2, B * (size_t)max_mappoints * sizeof(unsigned long long));
-    ALLOC(h->d_overflow, 2 * B * sizeof(int));                         // [0, B) overflow flags, [B, 2B) pool fill
+    ALLOC(h->d_overflow, 3 * B * sizeof(int));                         // [0, B) overflow flags, [B, 2B) pool fill, [2B, 3B) list entries kept (map search)
+    // k_mp_rounds: two blocks of 78 KB a CU at 1024 key points and 5000 map points (PLF_MATCH_ROUNDS_LDS: test hook, 0 = every frame on the pool)
+    const char *lds_env = getenv("PLF_MATCH_ROUNDS_LDS");
+    h->rounds_lds = (lds_env && atoi(lds_env) >= 0) ? atoi(lds_env) : MP_ROUNDS_LDS_ENTRIES;
+    if (h->rounds_lds > 65535) h->rounds_lds = 65535;                  // a list's start is 16 bits of its record
 #undef ALLOC
     h->h_frames = (FrameDev *)calloc(B, sizeof(FrameDev));
     h->h_lframes = (LineFrameDev *)calloc(B, sizeof(LineFrameDev));
@@ -186,14 +190,25 @@ extern "C" int plf_match_project_points(plf_matcher *h, const plf_frame_view *fr
     const int kp_cap = (maxn + 63) & ~63;
     if (maxn > 65535) return PLF_E_BADARG;  // candidate cache packs key point indices in 16 bits
     // fast path needs 16-bit map point indices and its lists in LDS; otherwise every frame takes the fallback kernel
-    const size_t lds_fast = (size_t)kp_cap * 8 + (size_t)((M.m + 1) & ~1) * sizeof(uint16_t);
-    const bool fast = M.m <= 65535 && lds_fast <= 150 * 1024;
+    const size_t slots = (size_t)((M.m + 1) & ~1);
+    const size_t lds_pool = (size_t)kp_cap * 8 + slots * sizeof(uint16_t);    // lists left in the pool: claim, owner, the unfinished map points
+    const bool fast = M.m <= 65535 && lds_pool <= 150 * 1024;
+    // the LDS budget of the lists, cut to what the block has left beside a record per map point (none left: every frame runs on the pool)
+    int budget = h->rounds_lds;
+    if (fast && budget > 0) {
+        const size_t room = 150 * 1024 - lds_pool;
+        budget = room > slots * sizeof(uint32_t) ? (int)std::min<size_t>((size_t)budget, (room - slots * sizeof(uint32_t)) / sizeof(uint32_t)) : 0;
+    }
+    const size_t lds_fast = lds_pool + (budget > 0 ? (slots + (size_t)budget) * sizeof(uint32_t) : 0);
     PLF_HIP_TRY(hipMemsetAsync(h->d_overflow, fast ? 0 : 1, 2 * (size_t)h->max_batch * sizeof(int), s));
+    PLF_HIP_TRY(hipMemsetAsync(h->d_overflow + 2 * (size_t)h->max_batch, 0, (size_t)h->max_batch * sizeof(int), s));
     if (fast && M.m > 0) {
-        hipLaunchKernelGGL(k_mp_candidates, dim3((M.m + 255) / 256, n_frames), dim3(256), 0, s, h->d_frames, M, th, match_of_kp, kp_stride,
-                           h->d_done, h->d_cand, (int2 *)h->d_cand_off, h->cand_cap, h->d_overflow, h->d_overflow + h->max_batch);
-        hipLaunchKernelGGL(k_mp_rounds, dim3(n_frames), dim3(256), lds_fast, s, h->d_frames, M, nnratio, match_of_kp, kp_stride, nmatches,
-                           h->d_done, kp_cap, h->d_cand, (const int2 *)h->d_cand_off, h->cand_cap, h->d_overflow, h->d_top2, h->max_mp);
+        hipLaunchKernelGGL(k_mp_candidates, dim3((M.m + 255) / 256, n_frames), dim3(256), 0, s, h->d_frames, M, th, nnratio, match_of_kp, kp_stride,
+                           h->d_done, h->d_cand, (int2 *)h->d_cand_off, h->cand_cap, h->d_overflow, h->d_overflow + h->max_batch,
+                           h->d_overflow + 2 * (size_t)h->max_batch);
+        hipLaunchKernelGGL(k_mp_rounds, dim3(n_frames), dim3(MP_ROUNDS_THREADS), lds_fast, s, h->d_frames, M, nnratio, match_of_kp, kp_stride, nmatches,
+                           h->d_done, kp_cap, h->d_cand, (const int2 *)h->d_cand_off, h->cand_cap, h->d_overflow,
+                           h->d_overflow + 2 * (size_t)h->max_batch, budget);
     }
     hipLaunchKernelGGL(k_match_project_points_slow, dim3(n_frames), dim3(256), (size_t)kp_cap * 8, s, h->d_frames, M, th, nnratio, match_of_kp,
                        kp_stride, nmatches, h->d_done, kp_cap, h->d_overflow);

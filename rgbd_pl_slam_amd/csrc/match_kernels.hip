@@ -29,6 +29,7 @@
 //   reset_owner, greedy_rounds         the slow round loop (candidates re-enumerated every round): k_match_project_points_slow,
 //                                      k_match_lastframe, k_project_kf_greedy; the line kernels keep their own loop (see match_project_lines_body)
 //   wave_append, list_unfinished       the list scaffold of the fast round kernels k_mp_rounds / k_lf_rounds
+//   wave_append_rec, mp_rounds         the rounds of k_mp_rounds: one definition for lists in LDS and lists left in the pool
 //   rot_bin, three_maxima, rot_cull    rotation consistency (rotHist, ComputeThreeMaxima, the per-assignment cull): k_match_lastframe,
 //                                      k_lf_rounds, k_match_bow; lf_orientation_cull is the tail the two last-frame kernels make of them
 //   accept_best_of_two                 TH_HIGH and the same-level ratio test of the best / second-best searches (map points, map lines)
@@ -300,6 +301,22 @@ __global__ void __launch_bounds__(256) k_match_project_points_slow(const FrameDe
 // Two map points decided in the same round can never take each other's top-2, the lowest unfinished one always
 // qualifies, so the result is the sequential loop's for any schedule (and for any placement of the spans).
 // cand entry: idx (16 bits) | dist (9 bits) << 16 | octave (4 bits) << 25.
+//
+// DROP RULE.  A map point is accepted when bestDist <= TH_HIGH && !(bestLevel == bestLevel2 && (float)bestDist > nnratio * (float)bestDist2).
+// k_mp_candidates does not store an entry of distance d with d > TH_HIGH && !((float)TH_HIGH > nnratio * (float)d):
+//   as best it cannot be accepted (d > TH_HIGH), and then no entry behind it can either: the map point ends without a claim with or without it;
+//   as second-best it cannot reject: bestDist <= TH_HIGH and !(TH_HIGH > nnratio * d) give !(bestDist > nnratio * d), what "no second-best" gives too
+//   (and every entry of a larger distance is dropped as well, so none moves up into its place).
+// The test is written as that float expression so that it holds for every nnratio (zero or negative: nothing is dropped; NaN: the ratio test never
+// rejects, and everything above TH_HIGH goes).  Kept entries keep their order, so first-occurrence ties are as before.
+// EARLY FINISH.  The free set only shrinks within a call, so a map point whose best free entry lies above TH_HIGH (or that has none left) is final
+// without a claim, in the round in which that shows; it does not wait until it is "safe".
+// Every unfinished map point posts on ALL its kept free entries.  Posting only on those it could claim (d <= TH_HIGH) is NOT sound: the posts also keep a
+// later map point from taking this one's second-best before this one decides, and that second-best may lie above TH_HIGH (tests/test_match_rounds_rule.py
+// holds a scene on which the restricted variant gives a wrong claim).
+// k_mp_rounds takes a frame's lists into LDS once (they are about 7 k entries after the drop for 5000 map points on 1000 key points) and runs post, decide
+// and the compaction of its list of unfinished map points there; a frame whose entries exceed the handle's budget (plf_matcher_create,
+// PLF_MATCH_ROUNDS_LDS) runs the same rounds on the pool in global memory.
 // ------------------------------------------------------------------------------------------------
 
 // mask of the lanes below n (plf_lanes_below(mask) is the other thing: the COUNT of a ballot's lanes below this one)
@@ -310,18 +327,24 @@ __device__ __forceinline__ unsigned long long lane_mask_below(int n) { return n 
 // th = 3 spans eleven columns) while most lanes sit masked off; here the wave takes the wsum key points 64 at a time instead.  A lane finds the owner of its
 // rank by a six-step search over the scanned offsets, takes the owner's projection, radius, level bounds and window by shuffles, finds its key point by
 // walking the window columns' CSR counts (a column is one index range), and runs the tests and the popcount distance of the old loop on it.  The ranks of
-// one owner are consecutive lanes and keep the reference order (column by column, CSR order inside), so a survivor's slot in the owner's span is the
-// owner's count of earlier chunks (run, a register of the owner lane) plus the survivors between the owner's first lane of this chunk and this lane: the
-// span holds the same entries in the same order as before.  Called by whole waves (wsum is wave-uniform); returns the lane's own number of candidates.
+// one owner are consecutive lanes and keep the reference order (column by column, CSR order inside); the owner lane counts its survivors chunk by chunk
+// (run, a register of the owner lane).  Called by whole waves (wsum is wave-uniform).
 // item_desc: descriptor of the item of lane 0; cand: the frame's pool at the wave's base; lo, hi: inclusive octave bounds.
+// DENSE LISTS: the wave reserved wsum slots (the upper bound), but its survivors go one behind the other from the wave's base (wrun, wave-uniform): ranks
+// are visited in order and an owner's ranks are consecutive, so an owner's entries stay contiguous and in order, across a chunk boundary too.  An owner's
+// list starts at the number of survivors before its first rank (start).  A frame's lists then lie in one short run per wave instead of one fragment per item.
+// DROP RULE: an entry that can decide nothing is not stored (see the comment above k_mp_candidates): with the ratio test (PACK_OCT, the map search)
+// dist > TH_HIGH && !(TH_HIGH > nnratio * dist), without it (the last-frame search, best distance only) dist > TH_HIGH.
+// Returns the lane's own number of entries; start: where they begin, relative to cand; wave_total: the wave's entries (wave-uniform).
 template <bool PACK_OCT>
 __device__ __forceinline__ int flat_walk(const FrameDev &F, const int *__restrict__ claim, const uint8_t *__restrict__ obs_positive,
                                          const uint8_t *__restrict__ item_desc, uint32_t *__restrict__ cand, int ub, int excl, int wsum, float x, float y,
-                                         float rad, float ur, int lo, int hi, const CellWin &w)
+                                         float rad, float ur, int lo, int hi, const CellWin &w, float nnratio, int &start, int &wave_total)
 {
     const int lane = plf_lane();
     const int win = ub > 0 ? (w.x0 | (w.x1 << 8) | (w.y0 << 16) | (w.y1 << 24)) : 0;   // (all four below 64)
-    int run = 0;
+    int run = 0, wrun = 0;
+    start = 0;
     for (int c0 = 0; c0 < wsum; c0 += 64) {
         const int t = c0 + lane;
         int own = 0;   // the last lane whose first rank is <= t: the lanes behind it that share its offset own nothing, so for t < wsum it owns rank t
@@ -331,7 +354,6 @@ __device__ __forceinline__ int flat_walk(const FrameDev &F, const int *__restric
             if (e <= t) own += s;
         }
         const int o_excl = __shfl(excl, own, 64), o_win = __shfl(win, own, 64), o_lo = __shfl(lo, own, 64), o_hi = __shfl(hi, own, 64);
-        const int o_run = __shfl(run, own, 64);
         const float ox = __shfl(x, own, 64), oy = __shfl(y, own, 64), orad = __shfl(rad, own, 64), our = __shfl(ur, own, 64);
         bool ok = t < wsum;
         uint32_t entry = 0;
@@ -366,21 +388,26 @@ __device__ __forceinline__ int flat_walk(const FrameDev &F, const int *__restric
                                      __popc(d1.y ^ k1.y) + __popc(d1.z ^ k1.z) + __popc(d1.w ^ k1.w);
                     entry = (uint32_t)idx | ((uint32_t)dist << 16);
                     if (PACK_OCT) entry |= (uint32_t)(oct & 15) << 25;
+                    if (dist > TH_HIGH && (!PACK_OCT || !((float)TH_HIGH > nnratio * (float)dist))) ok = false;   // the drop rule
                 }
             }
         }
         const unsigned long long sv = __ballot(ok);
-        if (ok) cand[o_excl + o_run + __popcll(sv & lane_mask_below(lane) & ~lane_mask_below(max(o_excl - c0, 0)))] = entry;
+        if (ok) cand[wrun + __popcll(sv & lane_mask_below(lane))] = entry;
+        // an owner whose first rank lies in this chunk starts behind the survivors before that rank
+        if (ub > 0 && excl >= c0 && excl < c0 + 64) start = wrun + __popcll(sv & lane_mask_below(excl - c0));
         // the owner's count moves by the survivors among its lanes of this chunk
         run += __popcll(sv & lane_mask_below(min(max(excl + ub - c0, 0), 64)) & ~lane_mask_below(min(max(excl - c0, 0), 64)));
+        wrun += __popcll(sv);
     }
+    wave_total = wrun;
     return run;
 }
 
-__global__ void __launch_bounds__(256) k_mp_candidates(const FrameDev *__restrict__ frames, MapDev MP, float th,
+__global__ void __launch_bounds__(256) k_mp_candidates(const FrameDev *__restrict__ frames, MapDev MP, float th, float nnratio,
                                                        const int *__restrict__ match_all, int kp_stride, uint8_t *__restrict__ done_all,
                                                        uint32_t *__restrict__ cand_all, int2 *__restrict__ span_all, int cand_cap,
-                                                       int *__restrict__ overflow, int *__restrict__ total)
+                                                       int *__restrict__ overflow, int *__restrict__ total, int *__restrict__ kept)
 {
     const int f = blockIdx.y, m = blockIdx.x * blockDim.x + threadIdx.x;
     FrameDev F = frames[f];
@@ -414,13 +441,16 @@ __global__ void __launch_bounds__(256) k_mp_candidates(const FrameDev *__restric
     }
     const bool fits = base + wsum <= cand_cap;
     if (!fits && plf_lane() == 0) overflow[f] = 1;   // this frame is left to k_match_project_points_slow
-    const int o0 = base + excl;
-    int o = o0;
-    if (wsum > 0 && fits)
-        o += flat_walk<true>(F, claim, MP.obs_positive, MP.desc + (size_t)(m - plf_lane()) * 32, cand + base, ub, excl, wsum, x, y, rad, xr, lvl - 1, lvl, w);
+    int start = 0, n = 0, wave_total = 0;
+    if (wsum > 0 && fits) {
+        n = flat_walk<true>(F, claim, MP.obs_positive, MP.desc + (size_t)(m - plf_lane()) * 32, cand + base, ub, excl, wsum, x, y, rad, xr, lvl - 1, lvl, w,
+                            nnratio, start, wave_total);
+        // the frame's entries in all: k_mp_rounds takes its lists into LDS when they fit its budget
+        if (wave_total > 0 && plf_lane() == 0) atomicAdd(&kept[f], wave_total);
+    }
     if (!in) return;
-    span_all[(size_t)f * MP.m + m] = make_int2(o0, o - o0);
-    done_all[(size_t)f * MP.m + m] = (o > o0) ? 0 : 1;
+    span_all[(size_t)f * MP.m + m] = make_int2(base + start, n);
+    done_all[(size_t)f * MP.m + m] = (n > 0) ? 0 : 1;
 }
 
 // ---- the list scaffold of the fast round kernels (k_mp_rounds, k_lf_rounds): the unfinished items as a uint16 list in LDS, rebuilt smaller every round.
@@ -444,20 +474,104 @@ __device__ __forceinline__ void list_unfinished(int n, const uint8_t *done, uint
     }
 }
 
-// LDS: claim[kp_cap], owner[kp_cap] (int), ONE list of unfinished map points (uint16, MP.m <= 65535), compacted in place after every round -- a second
-// list made the block 28 KB at 5000 map points (5 blocks per CU, and no room next to an ORB tile in the shadow of the region-growing kernel)
-// Round 4: ONE scan of an item's cached candidates per round.  The scan that posts the item's index on its free candidates also finds its two best free candidates
-// (both depend only on the claims at the start of the round) and parks them, packed in 64 bits, in a per-frame scratch row; the decision pass reads that word back
-// instead of scanning the candidates again -- the kernel moved 3.7 MB per frame through the L2 for 1.3 MB of candidate lists (FETCH_SIZE 31 GB per 8192-frame launch).
-__global__ void __launch_bounds__(256) k_mp_rounds(const FrameDev *__restrict__ frames, MapDev MP, float nnratio, int *__restrict__ match_all,
-                                                   int kp_stride, int *__restrict__ nmatches, const uint8_t *__restrict__ done_all, int kp_cap,
-                                                   const uint32_t *__restrict__ cand_all, const int2 *__restrict__ span_all, int cand_cap,
-                                                   const int *__restrict__ overflow, unsigned long long *__restrict__ top2_all, int top2_stride)
+// wave_append for k_mp_rounds, whose list carries a record per item when the lists live in LDS (rec, NULL otherwise)
+__device__ __forceinline__ void wave_append_rec(bool take, int item, uint32_t r, uint16_t *list, uint32_t *rec, int *count)
+{
+    const unsigned long long mask = __ballot(take);
+    int base = 0;
+    if (plf_lane() == 0 && mask) base = atomicAdd(count, __popcll(mask));
+    base = __shfl(base, 0, 64);
+    if (take) {
+        const int at = base + plf_lanes_below(mask);
+        list[at] = (uint16_t)item;
+        if (rec) rec[at] = r;
+    }
+}
+
+// The rounds of k_mp_rounds (whole block; the rule is in the comment above k_mp_candidates).  la[0 .. s_n[0]): the unfinished map points, compacted in place
+// after every round.  The list of map point la[i]: LDS_LISTS ? count rec[i] >> 16 from ent[rec[i] & 0xFFFF], all in LDS : span[m] in the frame's pool (ent).
+// ONE definition of a round for both, instantiated once on LDS pointers and once on global ones.
+// The decide pass scans the list again instead of reading back what the post pass found: a list is two or three entries, and nothing is parked
+// between the passes.  It may see a claim made in this same pass; that claim is by the lowest poster of the key point, an EARLIER map point, and final: the
+// sequential loop shows it to this map point too.
+template <bool LDS_LISTS>
+__device__ __forceinline__ void mp_rounds(int n_items, int n_kp, int *claim, int *owner, uint16_t *la, uint32_t *rec, const uint32_t *ent, const int2 *span,
+                                          const uint8_t *obs_positive, float nnratio, int *s_n, int *s_acc)
+{
+    const int t = threadIdx.x, T = blockDim.x;
+    auto list_of = [&](int i, int m) {
+        if (LDS_LISTS) { const uint32_t r = rec[i]; return make_int2((int)(r & 0xFFFF), (int)(r >> 16)); }
+        return span[m];
+    };
+    int cur = 0;
+    for (int round = 0; round <= n_items; round++) {
+        const int nact = s_n[cur];
+        if (nact == 0) break;
+        reset_owner(owner, n_kp);
+        __syncthreads();
+        // post: on every kept free entry
+        for (int i = t; i < nact; i += T) {
+            const int m = la[i];
+            const int2 sp = list_of(i, m);
+            for (int j = sp.x; j < sp.x + sp.y; j++) {
+                const int idx = (int)(ent[j] & 0xFFFF);
+                if (!blocked(claim, idx, obs_positive)) atomicMin(&owner[idx], m);
+            }
+        }
+        __syncthreads();
+        for (int i0 = 0; i0 < nact; i0 += T) {
+            const int i = i0 + t;
+            bool keep = false;
+            int m = 0;
+            uint32_t r = 0;
+            if (i < nact) {
+                m = la[i];
+                if (LDS_LISTS) r = rec[i];
+                const int2 sp = list_of(i, m);
+                int bestDist = 256, bestLevel = -1, bestDist2 = 256, bestLevel2 = -1, bestIdx = -1, idx2 = -1;
+                for (int j = sp.x; j < sp.x + sp.y; j++) {
+                    const uint32_t e = ent[j];
+                    const int idx = (int)(e & 0xFFFF);
+                    if (blocked(claim, idx, obs_positive)) continue;
+                    const int dist = (int)((e >> 16) & 0x1FF), oct = (int)(e >> 25);
+                    if (dist < bestDist) { bestDist2 = bestDist; bestLevel2 = bestLevel; idx2 = bestIdx; bestDist = dist; bestLevel = oct; bestIdx = idx; }
+                    else if (dist < bestDist2) { bestLevel2 = oct; bestDist2 = dist; idx2 = idx; }
+                }
+                // early finish: no free entry left, or the best one above TH_HIGH -- final without a claim
+                if (bestIdx >= 0 && bestDist <= TH_HIGH) {
+                    const bool safe = owner[bestIdx] == m && (idx2 < 0 || owner[idx2] == m);
+                    keep = !safe;
+                    if (safe && !(bestLevel == bestLevel2 && (float)bestDist > nnratio * (float)bestDist2)) {   // (accept_best_of_two, written out: the decide rule of this kernel stays visible)
+                        claim[bestIdx] = m;   // only this map point can touch bestIdx in this round
+                        atomicAdd(s_acc, 1);
+                    }
+                }
+            }
+            // in place: the kept items of chunks 0 .. i0 / T land below i0 + T; every thread of the block has read its entry of THIS chunk before any is written
+            __syncthreads();
+            wave_append_rec(keep, m, r, la, LDS_LISTS ? rec : nullptr, &s_n[cur ^ 1]);
+        }
+        __syncthreads();
+        if (t == 0) s_n[cur] = 0;
+        cur ^= 1;
+        __syncthreads();
+    }
+}
+
+// LDS: claim[kp_cap], owner[kp_cap] (int); ent[budget] (uint32): the frame's lists, gathered once; rec[slots] (uint32: start | count << 16, only with a
+// budget) and la[slots] (uint16): the unfinished map points (MP.m <= 65535), compacted in place after every round.  kept[f]: the frame's entries in all
+// (k_mp_candidates); a frame with more than `budget` of them (<= 65535) leaves its lists in the pool and runs the same rounds there.
+__global__ void __launch_bounds__(MP_ROUNDS_THREADS) k_mp_rounds(const FrameDev *__restrict__ frames, MapDev MP, float nnratio, int *__restrict__ match_all,
+                                                                 int kp_stride, int *__restrict__ nmatches, const uint8_t *__restrict__ done_all, int kp_cap,
+                                                                 const uint32_t *__restrict__ cand_all, const int2 *__restrict__ span_all, int cand_cap,
+                                                                 const int *__restrict__ overflow, const int *__restrict__ kept, int budget)
 {
     extern __shared__ __attribute__((aligned(16))) char smem[];
+    const int slots = (MP.m + 1) & ~1;
     int *claim = (int *)smem, *owner = claim + kp_cap;
-    uint16_t *la = (uint16_t *)(owner + kp_cap);
-    __shared__ int s_n[2], s_acc;
+    uint32_t *ent = (uint32_t *)(owner + kp_cap), *rec = ent + budget;
+    uint16_t *la = (uint16_t *)(rec + (budget > 0 ? slots : 0));
+    __shared__ int s_n[2], s_acc, s_ent;
     const int f = blockIdx.x, t = threadIdx.x, T = blockDim.x;
     if (overflow[f]) return;
     FrameDev F = frames[f];
@@ -466,63 +580,36 @@ __global__ void __launch_bounds__(256) k_mp_rounds(const FrameDev *__restrict__ 
     const uint8_t *done = done_all + (size_t)f * MP.m;
     const uint32_t *cand = cand_all + (size_t)f * cand_cap;
     const int2 *span = span_all + (size_t)f * MP.m;
+    const bool in_lds = budget > 0 && kept[f] <= budget;   // (block-uniform)
     load_claim(claim, match, F.n);
-    if (t == 0) { s_acc = 0; s_n[0] = 0; s_n[1] = 0; }
+    if (t == 0) { s_acc = 0; s_n[0] = 0; s_n[1] = 0; s_ent = 0; }
     __syncthreads();
-    list_unfinished(MP.m, done, la, &s_n[0]);
-    __syncthreads();
-    int cur = 0;
-    for (int round = 0; round <= MP.m; round++) {
-        const int nact = s_n[cur];
-        if (nact == 0) break;
-        reset_owner(owner, F.n);
-        __syncthreads();
-        unsigned long long *top2 = top2_all + (size_t)f * top2_stride;
-        for (int i = t; i < nact; i += T) {
-            const int m = la[i];
-            const int2 sp = span[m];
-            int bestDist = 256, bestLevel = -1, bestDist2 = 256, bestLevel2 = -1, bestIdx = -1, idx2 = -1;
-            for (int j = sp.x; j < sp.x + sp.y; j++) {
-                const uint32_t e = cand[j];
-                const int idx = (int)(e & 0xFFFF);
-                if (blocked(claim, idx, MP.obs_positive)) continue;
-                atomicMin(&owner[idx], m);
-                const int dist = (int)((e >> 16) & 0x1FF), oct = (int)(e >> 25);
-                if (dist < bestDist) { bestDist2 = bestDist; bestLevel2 = bestLevel; idx2 = bestIdx; bestDist = dist; bestLevel = oct; bestIdx = idx; }
-                else if (dist < bestDist2) { bestLevel2 = oct; bestDist2 = dist; idx2 = idx; }
+    if (in_lds) {
+        // gather: every unfinished map point's list, once; the lists of a wave's map points lie one behind the other in the pool (flat_walk), so the lanes
+        // read neighbouring pieces of the same lines.  The lists of all unfinished map points add up to kept[f] <= budget entries.
+        for (int m0 = 0; m0 < MP.m; m0 += T) {
+            const int m = m0 + t;
+            const bool act = m < MP.m && !done[m];
+            const int2 sp = act ? span[m] : make_int2(0, 0);
+            const int excl = plf_wave_excl_scan(sp.y), wsum = __builtin_amdgcn_readfirstlane(plf_wave_sum(sp.y));
+            int at = 0;
+            if (plf_lane() == 0 && wsum > 0) at = atomicAdd(&s_ent, wsum);
+            at = __shfl(at, 0, 64) + excl;
+            int best = 256;
+            for (int j = 0; j < sp.y; j++) {
+                const uint32_t e = cand[sp.x + j];
+                ent[at + j] = e;
+                best = min(best, (int)((e >> 16) & 0x1FF));
             }
-            // bestIdx | idx2 << 16 | bestDist << 32 | bestDist2 << 41 | bestLevel << 50 | bestLevel2 << 57   (-1 -> all ones of the field; distances <= 256: 9 bits)
-            top2[i] = (unsigned long long)(bestIdx & 0xFFFF) | ((unsigned long long)(idx2 & 0xFFFF) << 16) | ((unsigned long long)(bestDist & 0x1FF) << 32) |
-                      ((unsigned long long)(bestDist2 & 0x1FF) << 41) | ((unsigned long long)(bestLevel & 0x7F) << 50) | ((unsigned long long)(bestLevel2 & 0x7F) << 57);
+            // every entry is free before the first round: a map point whose best one lies above TH_HIGH is final here (the early finish)
+            wave_append_rec(act && best <= TH_HIGH, m, (uint32_t)at | ((uint32_t)sp.y << 16), la, rec, &s_n[0]);
         }
         __syncthreads();
-        for (int i0 = 0; i0 < nact; i0 += T) {
-            const int i = i0 + t;
-            bool keep = false;
-            int m = 0;
-            if (i < nact) {
-                m = la[i];
-                const unsigned long long tw = top2[i];
-                int bestIdx = (int)(tw & 0xFFFF), idx2 = (int)((tw >> 16) & 0xFFFF);
-                if (bestIdx == 0xFFFF) bestIdx = -1;
-                if (idx2 == 0xFFFF) idx2 = -1;
-                const int bestDist = (int)((tw >> 32) & 0x1FF), bestDist2 = (int)((tw >> 41) & 0x1FF);
-                const int bestLevel = (int)((tw >> 50) & 0x7F), bestLevel2 = (int)((tw >> 57) & 0x7F);   // (0x7F = none: only ever compared for equality, with a real level on one side)
-                const bool safe = (bestIdx < 0 || owner[bestIdx] == m) && (idx2 < 0 || owner[idx2] == m);
-                keep = !safe;
-                if (safe && bestDist <= TH_HIGH && !(bestLevel == bestLevel2 && (float)bestDist > nnratio * (float)bestDist2)) {   // (accept_best_of_two, written out: the decide rule of this kernel stays visible)
-                    claim[bestIdx] = m;   // only this map point can touch bestIdx in this round
-                    atomicAdd(&s_acc, 1);
-                }
-            }
-            // in place: the kept items of chunks 0 .. i0 / T land below i0 + T; every thread of the block has read its entry of THIS chunk before any is written
-            __syncthreads();
-            wave_append(keep, m, la, &s_n[cur ^ 1]);
-        }
+        mp_rounds<true>(MP.m, F.n, claim, owner, la, rec, ent, span, MP.obs_positive, nnratio, s_n, &s_acc);
+    } else {
+        list_unfinished(MP.m, done, la, &s_n[0]);
         __syncthreads();
-        if (t == 0) s_n[cur] = 0;
-        cur ^= 1;
-        __syncthreads();
+        mp_rounds<false>(MP.m, F.n, claim, owner, la, nullptr, cand, span, MP.obs_positive, nnratio, s_n, &s_acc);
     }
     store_claim(match, claim, F.n, &nmatches[f], &s_acc);
 }
@@ -737,19 +824,19 @@ __global__ void __launch_bounds__(256) k_lf_candidates(const FrameDev *__restric
     }
     const bool fits = base + wsum <= cand_cap;
     if (!fits && plf_lane() == 0) overflow[f] = 1;
-    const int o0 = base + excl;
-    int o = o0;
+    int start = 0, n = 0, wave_total = 0;
     if (wsum > 0 && fits) {
         // "no level test" (minL <= 0 and maxL < 0) and "no upper level" (maxL < 0) become bounds no octave reaches
         const int minL = bForward ? oct : (bBackward ? 0 : oct - 1), maxL = bForward ? -1 : (bBackward ? oct : oct + 1);
         const bool chk = (minL > 0) || (maxL >= 0);
         const float ur = fmaf(-P.bf, invzc, u);   // so@0x81eb5
-        o += flat_walk<false>(F, claim, Lf.obs_positive, Lf.mp_desc + (size_t)(i - plf_lane()) * 32, cand + base, ub, excl, wsum, u, v, rad, ur,
-                              chk ? minL : INT_MIN, maxL >= 0 ? maxL : INT_MAX, w);
+        // (no ratio test in this search: k_lf_rounds accepts on bestDist <= TH_HIGH alone, so every entry above TH_HIGH is dropped)
+        n = flat_walk<false>(F, claim, Lf.obs_positive, Lf.mp_desc + (size_t)(i - plf_lane()) * 32, cand + base, ub, excl, wsum, u, v, rad, ur,
+                             chk ? minL : INT_MIN, maxL >= 0 ? maxL : INT_MAX, w, 0.f, start, wave_total);
     }
     if (!in) return;
-    span_all[(size_t)f * item_stride + i] = make_int2(o0, o - o0);
-    done_all[(size_t)f * item_stride + i] = (o > o0) ? 0 : 1;
+    span_all[(size_t)f * item_stride + i] = make_int2(base + start, n);
+    done_all[(size_t)f * item_stride + i] = (n > 0) ? 0 : 1;
 }
 
 // LDS: claim[kp_cap], owner[kp_cap] (int); la, lb (unfinished points) and assign (key point of a finished point, 0xFFFF none): uint16[item_cap] each
