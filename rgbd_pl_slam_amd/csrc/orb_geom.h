@@ -73,6 +73,41 @@ __host__ __device__
 #endif
 static inline int orb_bands(const OrbLevel &L, int band_shift) { return (L.h + (1 << band_shift) - 1) >> band_shift; }
 
+// LDS of k_octree (byte offsets into the dynamic block, by descending alignment): node state, cap_nodes entries of 56 bytes, the sort / best-key words and the
+// scanned cell counts of the gather (`off`, one int per cell of the level with the most cells).  The host sizes the launch with .total, the kernel carves the
+// block with the offsets.
+struct OctLds {
+    uint32_t ccnt, skey, rectA, rectB, nA, nB, slot_of, mid, off, newpos, work, candA, candB, misc, total;
+};
+#define PLF_OCT_MISC_INTS 48   // wave totals of the block scans (2 x 3 x 4), broadcast word, root counts (8)
+#ifdef __HIPCC__
+__host__ __device__
+#endif
+static inline OctLds orb_octree_lds(int cap_nodes, int cap_sort, int cap_cells)
+{
+    OctLds o;
+    const uint32_t C = (uint32_t)cap_nodes, NC = (uint32_t)cap_cells;
+    uint32_t p = 0;
+    o.ccnt = p; p += 16 * C;
+    p = (p + 7) & ~7u;
+    o.skey = p; p += 8 * (uint32_t)cap_sort;
+    o.rectA = p; p += 8 * C;
+    o.rectB = p; p += 8 * C;
+    o.nA = p; p += 4 * C;
+    o.nB = p; p += 4 * C;
+    o.slot_of = p; p += 4 * C;
+    o.mid = p; p += 4 * C;
+    o.off = p; p += 4 * NC;
+    o.newpos = p; p += 2 * C;
+    o.work = p; p += 2 * C;
+    o.candA = p; p += 2 * C;
+    o.candB = p; p += 2 * C;
+    p = (p + 3) & ~3u;
+    o.misc = p; p += 4 * PLF_OCT_MISC_INTS;
+    o.total = p;
+    return o;
+}
+
 #ifdef __HIPCC__
 #include "plf_common.h"
 // the __constant__ tables of orb_kernels.hip, uploaded when a handle is created
@@ -99,8 +134,8 @@ __global__ void k_orb_pyramid(const uint8_t *in, ptrdiff_t in_pitch, ptrdiff_t i
                               OrbGeom g);
 __global__ void k_orb_blur(const uint8_t *pyr, uint8_t *blur, int band_shift, OrbGeom g, int4 taps);
 __global__ void k_orb_level(const uint8_t *pyr, const int4 *cells, int2 *cellinfo, uint2 *pool, int *poolcnt, int *status, OrbGeom g);
-__global__ void k_octree(const int2 *cellinfo, const uint2 *pool, int *celloff, uint2 *keys_all, int *nodeof_all, uint8_t *quad_all, uint2 *sel, int *selcnt, int *ncand_dbg, int *status, OrbGeom g,
-                         int cap_nodes, int cap_sort);
+__global__ void k_octree(const int2 *cellinfo, const uint2 *pool, uint2 *keys_all, int *nodeof_all, uint8_t *quad_all, uint2 *sel, int *selcnt, int *ncand_dbg, int *status, OrbGeom g,
+                         int cap_nodes, int cap_sort, int cap_cells);
 __global__ void k_orient_brief(const uint8_t *pyr, const uint8_t *blur, const uint2 *sel, const int *selcnt, plf_keypoint *kps, uint8_t *desc, int *n_out, int capacity, int *status, OrbGeom g,
                                int nframes);
 #endif

@@ -12,6 +12,10 @@
 #include "plf_common.h"
 #include "orb_geom.h"
 
+#ifndef PLF_OCTREE_THREADS
+#define PLF_OCTREE_THREADS 128
+#endif
+
 struct plf_orb {
     plf_orb_params prm;
     int device;
@@ -24,13 +28,14 @@ struct plf_orb {
     int umax[16];
     int capacity;
     int cap_nodes, cap_sort;
+    int octree_cap_cells;   // cells of the level with the most cells: k_octree keeps their scanned counts in LDS
     size_t octree_lds;
     int4 taps;
     hipStream_t stream;
     // device buffers
     uint8_t *d_pyr, *d_blur, *d_quad, *d_in;
     uint2 *d_pool, *d_keys, *d_sel;
-    int *d_nodeof, *d_celloff, *d_counters;  // counters: poolcnt[B*nl], selcnt[B*nl], ncand[B*nl], status[1]
+    int *d_nodeof, *d_counters;  // counters: poolcnt[B*nl], selcnt[B*nl], ncand[B*nl], status[1]
     int2 *d_cellinfo;
     int4 *d_cells;
     int *d_xofs, *d_yofs;
@@ -198,7 +203,7 @@ static void resize_tables(int sw, int sh, int dw, int dh, int *xofs, short2 *xa,
 
 static void orb_free(plf_orb *h)
 {
-    void *ptrs[] = {h->d_pyr, h->d_blur, h->d_quad, h->d_in, h->d_pool, h->d_keys, h->d_sel, h->d_nodeof, h->d_celloff,
+    void *ptrs[] = {h->d_pyr, h->d_blur, h->d_quad, h->d_in, h->d_pool, h->d_keys, h->d_sel, h->d_nodeof,
                     h->d_counters, h->d_cellinfo, h->d_cells, h->d_xofs, h->d_yofs, h->d_xa, h->d_yb, h->d_kps, h->d_desc, h->d_nout};
     for (void *p : ptrs) if (p) (void)hipFree(p);
     if (h->stream) (void)hipStreamDestroy(h->stream);
@@ -218,6 +223,8 @@ static int orb_configure(plf_orb *h, int w, int hh)
     if (g.pyr_stride > big.pyr_stride || g.blur_stride > big.blur_stride || g.pool_stride > big.pool_stride ||
         g.cells_total > big.cells_total || g.sel_stride > big.sel_stride)
         return PLF_E_BADARG;
+    for (int l = 0; l < g.nlevels; l++)
+        if (g.lv[l].ncells > h->octree_cap_cells) return PLF_E_BADARG;   // k_octree keeps a level's scanned cell counts in LDS
     std::vector<int> xofs, yofs;
     std::vector<short2> xa, yb;
     uint32_t tx = 0, ty = 0;
@@ -280,7 +287,7 @@ static int orb_configure(plf_orb *h, int w, int hh)
     g.pyr_stride = big.pyr_stride; g.blur_stride = big.blur_stride; g.pool_stride = big.pool_stride; g.sel_stride = big.sel_stride;
     const int cells_alloc = big.cells_total;
     h->g = g;
-    // per-frame cell arrays (cellinfo, celloff) are indexed with the ALLOCATED cell count as frame stride
+    // the per-frame cell array (cellinfo) is indexed with the ALLOCATED cell count as frame stride
     h->g.cells_total = g.cells_total;
     (void)cells_alloc;
     h->cur_w = w; h->cur_h = hh;
@@ -316,7 +323,9 @@ extern "C" int plf_orb_create(const plf_orb_params *p, plf_orb **out)
     if (h->cap_nodes > 4000) { free(h); return PLF_E_BADARG; }  // node positions are packed in 12 bits
     h->cap_sort = 1;
     while (h->cap_sort < h->cap_nodes) h->cap_sort <<= 1;
-    h->octree_lds = sizeof(unsigned long long) * h->cap_sort + (size_t)h->cap_nodes * (8 + 8 + 4 + 4 + 4 + 4 + 4 + 4 + 16 + 4 + 4 + 4) + 4 * 260;
+    h->octree_cap_cells = 0;
+    for (int l = 0; l < p->nlevels; l++) h->octree_cap_cells = std::max(h->octree_cap_cells, h->alloc.lv[l].ncells);
+    h->octree_lds = orb_octree_lds(h->cap_nodes, h->cap_sort, h->octree_cap_cells).total;
     if (h->octree_lds > 160 * 1024) { free(h); return PLF_E_BADARG; }
     const size_t B = (size_t)p->max_batch;
     const OrbGeom &g = h->g;
@@ -337,7 +346,6 @@ extern "C" int plf_orb_create(const plf_orb_params *p, plf_orb **out)
     ALLOC(h->d_quad, B * g.pool_stride);
     ALLOC(h->d_sel, B * g.sel_stride * sizeof(uint2));
     ALLOC(h->d_cellinfo, B * g.cells_total * sizeof(int2));
-    ALLOC(h->d_celloff, B * g.cells_total * sizeof(int));
     ALLOC(h->d_cells, (size_t)g.cells_total * sizeof(int4));
     ALLOC(h->d_counters, (B * g.nlevels * 3 + 16) * sizeof(int));
     ALLOC(h->d_xofs, tx * sizeof(int)); ALLOC(h->d_xa, tx * sizeof(short2));
@@ -407,13 +415,11 @@ static int orb_enqueue(plf_orb *h, const uint8_t *d_gray, int n_frames, ptrdiff_
     }
     hipLaunchKernelGGL(k_orb_blur, dim3(blur_blocks, B), dim3(64), 0, s, h->d_pyr, h->d_blur, bs, g, h->taps);
     hipLaunchKernelGGL(k_orb_level, dim3(g.tiles_total, B), dim3(PLF_ORB_LEVEL_THREADS), (size_t)g.lds_total + PLF_ORB_LDS_PAD, s, h->d_pyr, h->d_cells, h->d_cellinfo, h->d_pool, poolcnt, status, g);
-// k_octree is a chain of LDS sweeps and barriers over <= 250 nodes: latency-bound per workgroup.  128 threads: twice as many independent workgroups per wave slot
-    // (4.9 -> 3.0 ms per 4096 frames solo, and two of them fit in the one-wave-per-SIMD room next to the region-growing kernel)
-#ifndef PLF_OCTREE_THREADS
-#define PLF_OCTREE_THREADS 128
-#endif
-    hipLaunchKernelGGL(k_octree, dim3(nl, B), dim3(PLF_OCTREE_THREADS), h->octree_lds, s, h->d_cellinfo, h->d_pool, h->d_celloff, h->d_keys,
-                       h->d_nodeof, h->d_quad, h->d_sel, selcnt, ncand, status, g, h->cap_nodes, h->cap_sort);
+    // k_octree is a chain of short passes and barriers over <= 250 nodes: latency-bound per workgroup.  128 threads: twice as many independent workgroups per wave slot
+    // as 256 (2.0 against 2.5 ms per 8192 frames solo, profiles/orb_octree.txt), and two of them -- two waves and 17 KB of LDS each at 1000 features on VGA -- fit
+    // in the one-wave-per-SIMD room next to the region-growing kernel
+    hipLaunchKernelGGL(k_octree, dim3(nl, B), dim3(PLF_OCTREE_THREADS), h->octree_lds, s, h->d_cellinfo, h->d_pool, h->d_keys,
+                       h->d_nodeof, h->d_quad, h->d_sel, selcnt, ncand, status, g, h->cap_nodes, h->cap_sort, h->octree_cap_cells);
     int slots = 0;   // at most sum of the per-level selection caps, and never more than the caller can take
     for (int l = 0; l < nl; l++) slots += (int)g.lv[l].sel_cap;
     if (slots > capacity) slots = capacity;
