@@ -340,7 +340,7 @@ def test_line_projection_search_global_memory_variant(monkeypatch, force):
 @pytest.mark.parametrize("wave_max", ["64", "0"], ids=["wave_per_map_line", "thread_per_map_line"])
 def test_line_projection_search_wave_and_thread_kernels(monkeypatch, wave_max):
     """Round 6: up to 64 frames per call the line projection search runs one wave per map line with the key lines across the lanes (k_match_project_lines_w); larger
-    batches keep the thread-per-map-line kernel.  Both on the same scenes (PLF_MATCH_LINES_WAVE_MAX is read per call): crowded windows (1500 map lines for ~250
+    batches keep the thread-per-map-line kernel.  Both on the same scenes (PLF_MATCH_LINES_WAVE_MAX is read when the Matcher is created): crowded windows (1500 map lines for ~250
     lines: several rounds), descriptors duplicated so that best and second-best tie at distance 0 and at equal distances (the reference's first-come order), pre-set
     matches, th = 1 and th != 1 -- and a call of 70 frames (always the thread kernel) next to one of 64."""
     _need_gpu()
