@@ -67,7 +67,10 @@ def test_orb_1280x960_4000():
 
 
 def test_orb_flat_and_noise_images():
-    """edge cases: no corners at all (empty output), and dense noise (retry threshold, many ties)"""
+    """edge cases: no corners at all (empty output), dense noise (many ties; pass A of k_orb_level finds more survivors than its list holds and is redone in row
+    halves), and 128 +- 6, where no cell has a corner at iniThFAST and every one is found by the retry with minThFAST -- in one piece: 14 % of the pixels pass the
+    pre-test there, far below the list's capacity (tests/test_orb_front_cases.py::test_the_128_6_image_never_overflows; the row halves of pass B are reached by
+    tests/test_gpu_orb_front.py)"""
     _need_gpu()
     from rgbd_pl_slam_amd import ORBextractor
     flat = np.full((480, 640), 128, np.uint8)
@@ -77,7 +80,7 @@ def test_orb_flat_and_noise_images():
     rng = np.random.default_rng(7)
     noise = rng.integers(0, 256, (480, 640), dtype=np.uint8)
     _compare(noise, 1000, ext=ext)
-    low = (128 + rng.integers(-6, 7, (480, 640))).astype(np.uint8)   # only the minTh retry can fire
+    low = (128 + rng.integers(-6, 7, (480, 640))).astype(np.uint8)   # only the minTh retry can fire (not the halves redo)
     _compare(low, 1000, ext=ext)
     ext.close()
 
