@@ -1493,6 +1493,135 @@ int plf_triangulate_points(const plf_triangulate_view *v, const plf_camera *cam,
                            int32_t *new_i1, int32_t *new_i2, float *new_pos, int32_t *n_new, int32_t *status, uint8_t *reason, int32_t device,
                            void *stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * Sim3 solver -- class Sim3Solver include/Sim3Solver.h as LoopClosing::ComputeSim3 drives it: the constructor (plf_sim3_pairs) and iterate()
+ * (plf_sim3_iterate) for any number of solvers per call, between the rows plf_match_bow_kf writes and the transform plf_match_sim3 /
+ * plf_match_project_sim3 / plf_match_fuse_sim3 read.  OptimizeSim3 and PnPsolver are not here.
+ *
+ * The definition is tests/sim3ref.py, one float32 / float64 operation per statement.  From the disassembly of the binary (Sim3Solver::Sim3Solver
+ * so@0x10e950, SetRansacParameters so@0x10e770, iterate so@0x10d010, ComputeSim3 so@0x104a90, ComputeCentroid so@0x104370, CheckInliers so@0x10bdd0,
+ * Project so@0x10a190, FromCameraToImage so@0x108ef0):
+ *  - Constructor: i1 over vpMatched12; skipped when the match is NULL, keyframe 1 has no point at i1, either point isBad() (so@0x10f327, 0x10f338), or
+ *    either GetIndexInKeyFrame (so@0x10f34c, 0x10f360) is < 0 (the sign bit, so@0x10f365-0x10f37a).  The octave is mvKeysUn[index].octave (so@0x10f3a0),
+ *    sigma2 = mvLevelSigma2[octave]; mvnMaxError1/2 (vector<size_t>) = (double)sigma2 * 9.210 [double, so@0x127b80] (vcvtss2sd, vmulsd so@0x10f3da-
+ *    0x10f3df, 0x10f42d-0x10f433), truncated by vcvttsd2si below 2^63 [so@0x1261a0] (so@0x10f3f5, 0x10f449); mvX3Dc = Rcw * Xw + tcw as cv::operator*
+ *    and cv::operator+ (so@0x10f532, 0x10f54a; 0x10fbe7, 0x10fbff); FromCameraToImage twice (so@0x1107aa, 0x110949); then the constructor itself calls
+ *    SetRansacParameters(0.99 [so@0x1265d8], 6, 300) (so@0x110a06).
+ *  - FromCameraToImage / Project: invz = 1.0f / z (vdivss so@0x1090db, 0x10aa8f), x = X * invz, y = Y * invz (vmulss), and u = fmaf(x, fx, cx),
+ *    v = fmaf(y, fy, cy) -- THE BINARY FUSES these (vfmadd132ss so@0x10914f, 0x109136; 0x10ab10, 0x10aaf7); upstream's source has plain mul / add.
+ *    Project's P3Dc = Rcw * P3Dw + tcw is cv::operator* and cv::operator+ (so@0x10a5bc, 0x10a5ce).
+ *  - SetRansacParameters: epsilon = (float)minInliers / (float)N (vcvtsi2ss twice, vdivss so@0x10e855-0x10e85e); nIterations = 1 for minInliers == N
+ *    (so@0x10e829), else ceil(log(1.0 - prob) / log(1.0 - pow((double)epsilon, 3.0 [so@0x127a38]))) (so@0x10e842-0x10e88e) through vcvttsd2si to a
+ *    32-bit int (so@0x10e893: a value beyond int becomes INT_MIN, and so 1 below); mRansacMaxIts = max(1, min(nIterations, maxIterations))
+ *    (so@0x10e89d-0x10e8af).  libm's log and pow stay on the HOST: plf_sim3_its_for_n fills the table its_for_n[n], n = 0 .. n_max, once per (prob,
+ *    min_inliers, max_iterations); the caller keeps it in device memory and plf_sim3_pairs looks it up at the N it counted.  The table holds 0 for
+ *    n < max(3, min_inliers): iterate() returns at once for N < minInliers (so@0x10d195), and has undefined behaviour for N < 3; both are
+ *    PLF_SIM3_TOO_FEW here.
+ *  - Sampling: three draws per iteration from a fresh copy of mvAllIndices (so@0x10d4a1), each DUtils::Random::RandomInt(0, size - 1) (so@0x10d4c8,
+ *    behind the PLT: [UPSTREAM] Thirdparty/DBoW2/DUtils/Random.cpp:47-49, int(((double)rand() / ((double)RAND_MAX + 1.0)) * d) + min, PARITY UNPINNED);
+ *    the picked entry is overwritten by the list's last, which is dropped.  The calls take the RAW rand() values.
+ *  - ComputeSim3: ComputeCentroid twice (so@0x104e0c, 0x104e28: cv::reduce so@0x10440a, C / (double)P.cols so@0x104419-0x10441f, per column
+ *    cv::operator- so@0x10469d); M = Pr2 * Pr1.t() (so@0x104e3a, 0x104e53); the ten N_ij as float sums (so@0x10501f-0x105142): N11 = (M00 + M11) + M22,
+ *    N22 = (M00 - M11) - M22, N33 = (M11 - M00) - M22, N44 = (-M00 - M11) + M22 with -M00 a sign flip (so@0x1050af), the six differences and sums of
+ *    off-diagonal pairs one operation each; cv::eigen (so@0x105e7b); vec = evec.row(0).colRange(1, 4) (so@0x105fa4, 0x105fec); ang =
+ *    atan2@plt(cv::norm(vec), (double)evec(0, 0)) (so@0x106180-0x106191); vec = 2 * ang * vec / norm(vec) as (ang + ang) (so@0x1061f2) through
+ *    cv::operator*(double, Mat) (so@0x1061f9) and cv::operator/(MatExpr, double) (so@0x106213): the MatExpr folds alpha = (2 * ang) * (1 / norm) in
+ *    double and stores v * (float)alpha + 0.0f [UPSTREAM]; cv::Rodrigues (so@0x1064d0); P3 = R * Pr2 (so@0x1064e9); mbFixScale (so@0x1065b5): 1.0f
+ *    (so@0x1065c4), else nom = Pr1.dot(P3) (so@0x108293), cv::pow(P3, 2) (so@0x1084d8), den a double sum of its floats row by row (so@0x108520-
+ *    0x108533), ms12i = (float)(nom / den) (so@0x108550-0x108558); t12 = O1 - s * R * O2 as operator*(double, Mat), operator*(MatExpr, Mat),
+ *    operator-(Mat, MatExpr) (so@0x10664e-0x106680): one gemm, (float)((double)sum * -(double)s + (double)O1) [UPSTREAM]; T12 = [s R | t12]
+ *    (so@0x106a57-0x106aa3); T21 = [(1.0 / (double)s) * R.t() | -(sRinv) * t12] (vdivsd so@0x10718d, so@0x107191, 0x107457, 0x107470).
+ *  - CheckInliers: Project twice (so@0x10bffe, 0x10c316); dist = a - b (so@0x10c4de, 0x10c7a2); err = dist.dot(dist) (so@0x10ca76, 0x10cab3) NARROWED TO
+ *    FLOAT (vcvtsd2ss so@0x10caa9, 0x10caf2 -- upstream keeps it in the type the dot returns --); the size_t thresholds converted to float
+ *    (vcvtsi2ss so@0x10cad9, 0x10cb07); inlier iff (float)mvnMaxError1[i] > err1 && (float)mvnMaxError2[i] > err2 (vucomiss, jbe so@0x10cade-0x10cb10):
+ *    strict, and a NaN error is an outlier.
+ *  - iterate: while mnIterations < mRansacMaxIts (so@0x10d466) and the call's count; mnInliersi >= mnBestInliers takes the best (so@0x10d77b); it returns
+ *    when also mnInliersi > mRansacMinInliers (so@0x10df78); bNoMore = mnIterations >= mRansacMaxIts.
+ * The binary agrees with upstream ORB-SLAM2 in control flow and constants; it DIFFERS in the fused operations of the two projections and in the float
+ * narrowing of the two errors.
+ * The OpenCV 3.3 routines behind the PLT are not in the snapshot; only these are restated [UPSTREAM] and PARITY UNPINNED:
+ *  - cv::reduce SUM of three CV_32F columns: two float accumulators, (p0 + p2) + p1.  Mat / int: x * (float)(1.0 / 3) + 0.0f.
+ *  - cv::gemm: the small-matrix float path for R * X (+ t) and R * Pr2; with a transposed operand (Pr2 * Pr1.t()) the general path, a double sum
+ *    rounded to float at the store.  cv::Mat::dot of nine floats: double products, four at a time added to the running double sum.
+ *  - cv::eigen for symmetric CV_32F is JacobiImpl_<float>: the indR / indC pivot search (with its stale entries), cv's own float hypot, the rotation
+ *    in float, at most n * n * 30 rotations, |p| <= FLT_EPSILON ends it, a descending selection sort that keeps the FIRST of equal values, and the
+ *    sign of the vectors as the rotations leave them.
+ *  - cv::Rodrigues from vector to matrix: theta = sqrt(rx^2 + ry^2 + rz^2) in double; theta < DBL_EPSILON gives the identity; else
+ *    (c * I + (1 - c) * r r^T) + s * [r]x in double, rounded to float at the store.  sin / cos: plf_sincos_d (csrc/plf_math.h), as at plf_pose_optimize.
+ *  - the double atan2 is fdlibm's __ieee754_atan2 / atan restated without FMA (plf_atan2_fdlibm_d); as for PoseOptimization, the last bit of glibc's
+ *    atan2 is fixed by the definition, not measured against the binary (tests/test_sim3_ref.py reports the difference in ulps).
+ * DEVIATIONS: a key-point octave outside [0, nlevels) is clamped, an index from kf_obs_index outside [0, kf_n) and a map-point id outside
+ * [0, n_points) are taken as "none" (the reference reads out of bounds); max_err is kept as int32: a NaN or negative product gives 0 (the binary's
+ * vcvttsd2si gives 2^63 resp. a huge size_t, i.e. no threshold at all), one beyond INT32_MAX the greatest int32.
+ *
+ * plf_sim3_pairs, job j: slots job_kf1[j], job_kf2[j]; match12 + j * kp_stride as plf_match_bow_kf wrote it (the feature of keyframe 2 whose map
+ * point feature i1 of keyframe 1 received, < 0: none; entries >= kf_n[kf2] are skipped); i1 over [0, min(kf_n[kf1], kp_stride)).  The points are
+ * kf_mappoints[kf1][i1] and kf_mappoints[kf2][i2] (-1: NULL); kf_obs_index[s][i] is GetIndexInKeyFrame of the point in slot i (the table NULL: i
+ * itself).  Outputs at j * pair_stride, in ascending i1, for the first pair_stride pairs: idx1, x3dc1 / x3dc2 (3 floats), max_err1 / max_err2,
+ * p1im1 / p2im2 (2 floats); n_pairs[j] the TRUE count; status[j] a mask of PLF_SIM3_OVERFLOW (n_pairs > pair_stride), PLF_SIM3_BAD_SLOT,
+ * PLF_SIM3_TOO_FEW (its_for_n[N] == 0).  It also sets the job's state: iterations_done = 0, best_inliers = 0, best_iter = -1, best_sim3 = 0,
+ * max_its = its_for_n[N] (0 for a job with any status bit: such a job never iterates), no_more = (max_its == 0).  its_for_n: pair_stride + 1 entries.
+ *
+ * plf_sim3_iterate runs iterations (iterations_done, min(iterations_done + iter_count, max_its)] of every job with active[j] != 0 (active NULL:
+ * all).  Iteration k reads rand3[(j * rand_stride + k - 1) * 3 ..+3) and writes count[j * rand_stride + k - 1]; rand_stride >= the greatest max_its.
+ * Hits are the iterations at which iterate() would have returned under the running-best rule started from the state at entry: count >= the best so
+ * far and count > min_inliers.  For hit h < max_hits, ascending, at j * max_hits + h: hit_iter, hit_inliers, hit_sim3 (R12 9, t12 3, s12) and
+ * hit_inlier12 (kp_stride bytes indexed by i1: vbInliers); n_hits[j] the TRUE count of this call.  The state leaves with iterations_done, best_inliers,
+ * best_iter, best_sim3 and no_more (iterations_done >= max_its).  Any split of the iterations into calls gives the same hits and the same final state.
+ * Stateless; every array is DEVICE memory (the structs themselves, and plf_sim3_its_for_n's table, are host); asynchronous on `stream`; nothing is
+ * read back; no scratch.  PLF_E_BADARG before any device work: a NULL required array, negative sizes, strides < 1, nlevels < 1, iter_count < 0,
+ * max_hits < 0.  NaN / Inf values, slots, ids and indices out of range fault nowhere.
+ * k_sim3_pairs: one workgroup of 256 per job, key points in chunks of 256, survivors numbered by ballot and a scan across waves and chunks.
+ * k_sim3_count: a workgroup takes 256 iterations of one job: one closed-form solve per lane into LDS, then one wave per iteration over the pairs
+ * (staged in LDS when they fit, else from global memory), counted by ballot.  k_sim3_resolve: one wave per job scans the counts and re-runs the
+ * hit iterations for their flag rows.
+ * ---------------------------------------------------------------------------------------------- */
+enum { PLF_SIM3_OVERFLOW = 1, PLF_SIM3_BAD_SLOT = 2, PLF_SIM3_TOO_FEW = 4 };
+typedef struct {
+    int32_t n_kf;
+    const plf_keypoint *const *kf_keys;                   /* n_kf device pointers: mvKeysUn (octave is read) */
+    const int32_t *kf_n;                                  /* n_kf */
+    const plf_frustum_pose *kf_pose;                      /* n_kf: Rcw, tcw (Ow is not read) */
+    const int32_t *const *kf_mappoints;                   /* n_kf device pointers: mvpMapPoints, -1 = NULL */
+    const int32_t *const *kf_obs_index;                   /* optional: n_kf device pointers, GetIndexInKeyFrame per slot; NULL: the slot itself */
+    const float *world_pos;                               /* n_points x 3 */
+    const uint8_t *point_bad;                             /* n_points */
+    int32_t n_points;
+    const float *level_sigma2;                            /* nlevels */
+    int32_t nlevels;
+} plf_sim3_view;
+typedef struct {
+    int32_t n_jobs, kp_stride, pair_stride;
+    const int32_t *job_kf1, *job_kf2;                     /* n_jobs (plf_sim3_pairs only) */
+    const int32_t *match12;                               /* n_jobs x kp_stride (plf_sim3_pairs only) */
+    const uint8_t *fix_scale;                             /* n_jobs: mbFixScale (plf_sim3_iterate only) */
+} plf_sim3_jobs;
+typedef struct {
+    int32_t *idx1;                                        /* n_jobs x pair_stride */
+    float *x3dc1, *x3dc2;                                 /* n_jobs x pair_stride x 3 */
+    int32_t *max_err1, *max_err2;                         /* n_jobs x pair_stride */
+    float *p1im1, *p2im2;                                 /* n_jobs x pair_stride x 2 */
+    int32_t *n_pairs, *status;                            /* n_jobs */
+} plf_sim3_pairset;
+typedef struct {
+    int32_t *iterations_done, *best_inliers, *best_iter, *max_its;   /* n_jobs each */
+    float *best_sim3;                                     /* n_jobs x 13 */
+    uint8_t *no_more;                                     /* n_jobs */
+} plf_sim3_state;
+typedef struct {
+    int32_t max_hits;
+    int32_t *n_hits;                                      /* n_jobs */
+    int32_t *hit_iter, *hit_inliers;                      /* n_jobs x max_hits */
+    float *hit_sim3;                                      /* n_jobs x max_hits x 13 */
+    uint8_t *hit_inlier12;                                /* n_jobs x max_hits x kp_stride */
+} plf_sim3_hits;
+int plf_sim3_its_for_n(double prob, int32_t min_inliers, int32_t max_iterations, int32_t n_max, int32_t *table_host);
+int plf_sim3_pairs(const plf_sim3_view *v, const plf_camera *cam, const plf_sim3_jobs *jobs, const int32_t *its_for_n, const plf_sim3_pairset *pairs,
+                   const plf_sim3_state *state, int32_t device, void *stream);
+int plf_sim3_iterate(const plf_sim3_jobs *jobs, const plf_camera *cam, const plf_sim3_pairset *pairs, const int32_t *rand3, int32_t rand_stride,
+                     int32_t iter_count, int32_t min_inliers, const uint8_t *active, const plf_sim3_state *state, int32_t *count,
+                     const plf_sim3_hits *hits, int32_t device, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -762,6 +762,57 @@ struct Triangulator {
     static int Branch(uint8_t reason) { return reason & PLF_TRI_BRANCH_MASK; }
 };
 
+// The Sim3 solver section of include/plf.h over arrays this object owns: n_jobs solvers, their pair sets, RANSAC state, raw random values, counts and
+// hits.  Pairs() is Sim3Solver's constructor + SetRansacParameters for all jobs in one launch, Iterate() is iterate(n) for all in one call; both only
+// enqueue on `stream`.  The table of SetRansacParameters (host libm) is filled and uploaded by SetRansacParameters().
+class Sim3Batch {
+public:
+    Sim3Batch(int n_jobs, int kp_stride, int pair_stride, int rand_stride, int max_hits, int device = 0)
+        : J(n_jobs), S(kp_stride), PS(pair_stride), RS(rand_stride), MH(max_hits), device_(device), idx1((size_t)J * PS, device), max_err1((size_t)J * PS, device),
+          max_err2((size_t)J * PS, device), n_pairs(J, device), status(J, device), iterations_done(J, device), best_inliers(J, device), best_iter(J, device),
+          max_its(J, device), count((size_t)J * RS, device), n_hits(J, device), hit_iter((size_t)J * MH, device), hit_inliers((size_t)J * MH, device),
+          rand3((size_t)J * RS * 3, device), table((size_t)PS + 1, device), x3dc1((size_t)J * PS * 3, device), x3dc2((size_t)J * PS * 3, device),
+          p1im1((size_t)J * PS * 2, device), p2im2((size_t)J * PS * 2, device), best_sim3((size_t)J * 13, device), hit_sim3((size_t)J * MH * 13, device),
+          no_more(J, device), fix_scale(J, device), hit_inlier12((size_t)J * MH * S, device)
+    {
+    }
+    void SetRansacParameters(double probability, int minInliers, int maxIterations)
+    {
+        std::vector<int32_t> t((size_t)PS + 1);
+        check(plf_sim3_its_for_n(probability, minInliers, maxIterations, PS, t.data()), "Sim3Solver::SetRansacParameters");
+        table.upload(t.data(), t.size());
+        min_inliers = minInliers;
+    }
+    void Pairs(const plf_sim3_view &keyframes, const plf_camera &cam, const int32_t *job_kf1_dev, const int32_t *job_kf2_dev, const int32_t *match12_dev,
+               void *stream = nullptr)
+    {
+        cam_ = cam;
+        const plf_sim3_jobs jobs = {J, S, PS, job_kf1_dev, job_kf2_dev, match12_dev, fix_scale.get()};
+        const plf_sim3_pairset p = pairset();
+        const plf_sim3_state st = state();
+        check(plf_sim3_pairs(&keyframes, &cam, &jobs, table.get(), &p, &st, device_, stream), "Sim3Solver::Sim3Solver");
+    }
+    void Iterate(int nIterations, const uint8_t *active_dev = nullptr, void *stream = nullptr)
+    {
+        const plf_sim3_jobs jobs = {J, S, PS, nullptr, nullptr, nullptr, fix_scale.get()};
+        const plf_sim3_pairset p = pairset();
+        const plf_sim3_state st = state();
+        const plf_sim3_hits h = {MH, n_hits.get(), hit_iter.get(), hit_inliers.get(), hit_sim3.get(), hit_inlier12.get()};
+        check(plf_sim3_iterate(&jobs, &cam_, &p, rand3.get(), RS, nIterations, min_inliers, active_dev, &st, count.get(), &h, device_, stream), "Sim3Solver::iterate");
+    }
+    plf_sim3_pairset pairset() const { return {idx1.get(), x3dc1.get(), x3dc2.get(), max_err1.get(), max_err2.get(), p1im1.get(), p2im2.get(), n_pairs.get(), status.get()}; }
+    plf_sim3_state state() const { return {iterations_done.get(), best_inliers.get(), best_iter.get(), max_its.get(), best_sim3.get(), no_more.get()}; }
+    const int J, S, PS, RS, MH;
+    int min_inliers = 6;
+private:
+    int device_;
+    plf_camera cam_ = {};
+public:
+    DeviceArray<int32_t> idx1, max_err1, max_err2, n_pairs, status, iterations_done, best_inliers, best_iter, max_its, count, n_hits, hit_iter, hit_inliers, rand3, table;
+    DeviceArray<float> x3dc1, x3dc2, p1im1, p2im2, best_sim3, hit_sim3;
+    DeviceArray<uint8_t> no_more, fix_scale, hit_inlier12;
+};
+
 }  // namespace plf
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -773,7 +824,9 @@ struct Triangulator {
 // ---------------------------------------------------------------------------------------------------------------
 #if defined(PLF_WITH_OPENCV) && defined(__has_include)
 #if __has_include(<opencv2/core.hpp>)
+#include <cstdlib>
 #include <cstring>
+#include <memory>
 #include <set>
 #include <unordered_map>
 #include <utility>
@@ -1999,6 +2052,218 @@ struct LocalMapping {
             }
         return nnew;
     }
+};
+
+// class Sim3Solver include/Sim3Solver.h with its reference signatures, over the reference's own KeyFrame / MapPoint classes (the members the reference's
+// constructor reads: GetMapPointMatches, GetRotation, GetTranslation, mvKeysUn, mvLevelSigma2, fx .. cy; isBad, GetIndexInKeyFrame, GetWorldPos).
+// The constructor flattens what the reference's reads and, like the reference's (so@0x110a06), sets the default parameters; it draws NOTHING from rand().
+// SetRansacParameters draws the solver's 3 * maxIterations raw values from rand() -- for one solver driven by find() exactly the values the reference
+// would consume up to the returning iteration; a solver left at the constructor's defaults draws at its first iterate() / Prepare().  iterate() is one
+// plf_sim3_iterate.  Prepare() + Step() step a vector of solvers with ONE device call per round: the loop of LoopClosing::ComputeSim3.  The camera and
+// mvLevelSigma2 are taken from pKF1 for both keyframes (the reference projects into keyframe 2 with pKF2's mK and reads pKF2->mvLevelSigma2): the same
+// values for one sensor, which is all plf_sim3_view holds.  The reference
+// interleaves one global rand() stream across its solvers and an early return shifts every later draw; a call that runs solvers side by side cannot
+// reproduce that and does not claim it: given the same triples the result is the reference's, which triples a solver gets is the caller's.
+template <class KeyFrameT, class MapPointT> class Sim3Solver {
+public:
+    Sim3Solver(KeyFrameT *pKF1, KeyFrameT *pKF2, const std::vector<MapPointT *> &vpMatched12, const bool bFixScale = true, int device = 0)
+        : mbFixScale(bFixScale), device_(device)
+    {
+        const std::vector<MapPointT *> vpKeyFrameMP1 = pKF1->GetMapPointMatches();
+        mN1 = (int)vpMatched12.size();
+        std::unordered_map<MapPointT *, int32_t> ids;
+        auto id_of = [&](MapPointT *p) {
+            auto it = ids.find(p);
+            if (it != ids.end()) return it->second;
+            const int32_t id = (int32_t)ids.size();
+            ids.emplace(p, id);
+            const cv::Mat X = p->GetWorldPos();
+            for (int r = 0; r < 3; r++) world_.push_back(X.template at<float>(r, 0));
+            bad_.push_back(p->isBad() ? 1 : 0);
+            return id;
+        };
+        KeyFrameT *kf[2] = {pKF1, pKF2};
+        for (int s = 0; s < 2; s++) {
+            const int n = (int)kf[s]->mvKeysUn.size();
+            n_[s] = n;
+            keys_[s].resize(std::max(n, 1));
+            if (n) std::memcpy((void *)keys_[s].data(), kf[s]->mvKeysUn.data(), (size_t)n * sizeof(plf_keypoint));
+            mps_[s].assign(std::max(n, 1), -1);
+            obs_[s].assign(std::max(n, 1), -1);
+            const cv::Mat Rcw = kf[s]->GetRotation(), tcw = kf[s]->GetTranslation();
+            for (int r = 0; r < 3; r++) {
+                for (int c = 0; c < 3; c++) pose_[s].Rcw[3 * r + c] = Rcw.template at<float>(r, c);
+                pose_[s].tcw[r] = tcw.template at<float>(r, 0);
+                pose_[s].Ow[r] = 0.0f;
+            }
+        }
+        sigma2_.assign(pKF1->mvLevelSigma2.begin(), pKF1->mvLevelSigma2.end());
+        cam_ = plf_camera{};
+        cam_.fx = pKF1->fx; cam_.fy = pKF1->fy; cam_.cx = pKF1->cx; cam_.cy = pKF1->cy;
+        match_.assign(std::max(n_[0], 1), -1);
+        // a key point of keyframe 2 that stands for each matched point: its GetIndexInKeyFrame when that is a key point, else none (the reference skips it)
+        for (int i1 = 0; i1 < mN1 && i1 < n_[0]; i1++) {
+            MapPointT *pMP2 = vpMatched12[i1];
+            if (!pMP2) continue;
+            MapPointT *pMP1 = i1 < (int)vpKeyFrameMP1.size() ? vpKeyFrameMP1[i1] : nullptr;
+            if (!pMP1) continue;
+            const int i2 = pMP2->GetIndexInKeyFrame(pKF2);
+            if (i2 < 0 || i2 >= n_[1]) continue;
+            mps_[0][i1] = id_of(pMP1); obs_[0][i1] = pMP1->GetIndexInKeyFrame(pKF1);
+            mps_[1][i2] = id_of(pMP2); obs_[1][i2] = i2;
+            match_[i1] = i2;
+        }
+        if (world_.empty()) { world_.assign(3, 0.0f); bad_.assign(1, 1); }
+    }
+    void SetRansacParameters(double probability = 0.99, int minInliers = 6, int maxIterations = 300)
+    {
+        prob_ = probability; min_inliers_ = minInliers; max_iterations_ = maxIterations;
+        Draw();
+        batch_.reset();
+        own_.clear();
+    }
+    cv::Mat iterate(int nIterations, bool &bNoMore, std::vector<bool> &vbInliers, int &nInliers)
+    {
+        std::vector<Sim3Solver *> me(1, this);
+        std::vector<cv::Mat> T;
+        std::vector<bool> no_more;
+        if (!batch_) { own_ = me; Prepare(own_, batch_, held_); }
+        Step(own_, *batch_, nIterations, T, no_more);
+        bNoMore = no_more[0];
+        vbInliers = vbInliers_; nInliers = nInliers_;
+        return T[0];
+    }
+    cv::Mat find(std::vector<bool> &vbInliers12, int &nInliers)
+    {
+        bool bFlag;
+        return iterate(max_iterations_, bFlag, vbInliers12, nInliers);
+    }
+    cv::Mat GetEstimatedRotation() { return best_R_; }
+    cv::Mat GetEstimatedTranslation() { return best_t_; }
+    float GetEstimatedScale() { return best_s_; }
+    // what the last Step() / iterate() left for this solver: vbInliers and nInliers of the reference's iterate()
+    const std::vector<bool> &LastInliers() const { return vbInliers_; }
+    int LastInlierCount() const { return nInliers_; }
+
+    // everything a prepared vector of solvers keeps on the device
+    struct Held {
+        std::vector<std::unique_ptr<plf::DeviceArray<plf_keypoint>>> keys;
+        std::vector<std::unique_ptr<plf::DeviceArray<int32_t>>> mps, obs;
+        plf::DeviceArray<const plf_keypoint *> t_keys;
+        plf::DeviceArray<const int32_t *> t_mps, t_obs;
+        plf::DeviceArray<int32_t> kf_n, kf1, kf2, match;
+        plf::DeviceArray<plf_frustum_pose> pose;
+        plf::DeviceArray<float> world, sigma2;
+        plf::DeviceArray<uint8_t> bad;
+    };
+    // the constructor of every solver in one launch (their SetRansacParameters must agree); then Step() is one round of LoopClosing::ComputeSim3
+    static void Prepare(const std::vector<Sim3Solver *> &solvers, std::unique_ptr<plf::Sim3Batch> &batch, Held &h)
+    {
+        for (Sim3Solver *s : solvers) if (s->rand3_.empty()) s->Draw();
+        const int J = (int)solvers.size(), device = solvers[0]->device_;
+        int S = 1, RS = 1;
+        for (Sim3Solver *s : solvers) { S = std::max(S, s->n_[0]); RS = std::max(RS, s->max_iterations_); }
+        std::vector<const plf_keypoint *> t_keys;
+        std::vector<const int32_t *> t_mps, t_obs;
+        std::vector<int32_t> kf_n, kf1, kf2, match((size_t)J * S, -1), rand3((size_t)J * RS * 3, 0);
+        std::vector<plf_frustum_pose> pose;
+        std::vector<float> world;
+        std::vector<uint8_t> bad, fix;
+        h.keys.clear(); h.mps.clear(); h.obs.clear();
+        for (int j = 0; j < J; j++) {
+            Sim3Solver *s = solvers[j];
+            const int32_t base = (int32_t)bad.size();
+            for (int k = 0; k < 2; k++) {
+                std::vector<int32_t> ids = s->mps_[k];
+                for (int32_t &id : ids) if (id >= 0) id += base;
+                h.keys.emplace_back(new plf::DeviceArray<plf_keypoint>(s->keys_[k], device));
+                h.mps.emplace_back(new plf::DeviceArray<int32_t>(ids, device));
+                h.obs.emplace_back(new plf::DeviceArray<int32_t>(s->obs_[k], device));
+                t_keys.push_back(h.keys.back()->get()); t_mps.push_back(h.mps.back()->get()); t_obs.push_back(h.obs.back()->get());
+                kf_n.push_back(s->n_[k]); pose.push_back(s->pose_[k]);
+            }
+            world.insert(world.end(), s->world_.begin(), s->world_.end());
+            bad.insert(bad.end(), s->bad_.begin(), s->bad_.end());
+            kf1.push_back(2 * j); kf2.push_back(2 * j + 1);
+            fix.push_back(s->mbFixScale ? 1 : 0);
+            std::copy(s->match_.begin(), s->match_.begin() + std::min<size_t>(s->match_.size(), (size_t)S), match.begin() + (size_t)j * S);
+            std::copy(s->rand3_.begin(), s->rand3_.end(), rand3.begin() + (size_t)j * RS * 3);
+        }
+        h.t_keys.reset(t_keys.size(), device); h.t_keys.upload(t_keys.data(), t_keys.size());
+        h.t_mps.reset(t_mps.size(), device); h.t_mps.upload(t_mps.data(), t_mps.size());
+        h.t_obs.reset(t_obs.size(), device); h.t_obs.upload(t_obs.data(), t_obs.size());
+        auto up = [&](auto &d, const auto &v) { d.reset(v.size(), device); d.upload(v.data(), v.size()); };
+        up(h.kf_n, kf_n); up(h.kf1, kf1); up(h.kf2, kf2); up(h.match, match); up(h.pose, pose); up(h.world, world); up(h.bad, bad); up(h.sigma2, solvers[0]->sigma2_);
+        batch.reset(new plf::Sim3Batch(J, S, S, RS, 1, device));
+        batch->fix_scale.upload(fix.data(), fix.size());
+        batch->rand3.upload(rand3.data(), rand3.size());
+        batch->SetRansacParameters(solvers[0]->prob_, solvers[0]->min_inliers_, solvers[0]->max_iterations_);
+        plf_sim3_view v = {};
+        v.n_kf = 2 * J; v.kf_keys = h.t_keys.get(); v.kf_n = h.kf_n.get(); v.kf_pose = h.pose.get(); v.kf_mappoints = h.t_mps.get(); v.kf_obs_index = h.t_obs.get();
+        v.world_pos = h.world.get(); v.point_bad = h.bad.get(); v.n_points = (int32_t)bad.size(); v.level_sigma2 = h.sigma2.get();
+        v.nlevels = (int32_t)solvers[0]->sigma2_.size();
+        batch->Pairs(v, solvers[0]->cam_, h.kf1.get(), h.kf2.get(), h.match.get(), nullptr);
+    }
+    // iterate(nIterations) of every solver that has not said bNoMore, in one device call; T[j] is empty where solver j did not return a transform.  A
+    // solver that hits is set back to its hit, where the reference's iterate() returned: its next call goes on from the iteration after.
+    static void Step(const std::vector<Sim3Solver *> &solvers, plf::Sim3Batch &b, int nIterations, std::vector<cv::Mat> &T, std::vector<bool> &bNoMore)
+    {
+        const int J = (int)solvers.size();
+        b.Iterate(nIterations, nullptr, nullptr);
+        const std::vector<int32_t> n_hits = b.n_hits.download(), hit_iter = b.hit_iter.download(), hit_inliers = b.hit_inliers.download(), max_its = b.max_its.download();
+        std::vector<int32_t> done = b.iterations_done.download(), best = b.best_inliers.download(), best_iter = b.best_iter.download();
+        const std::vector<float> hit_sim3 = b.hit_sim3.download();
+        std::vector<float> best_sim3 = b.best_sim3.download();
+        std::vector<uint8_t> no_more = b.no_more.download();
+        const std::vector<uint8_t> rows = b.hit_inlier12.download();
+        T.assign(J, cv::Mat()); bNoMore.assign(J, false);
+        bool patched = false;
+        for (int j = 0; j < J; j++) {
+            Sim3Solver *s = solvers[j];
+            s->vbInliers_.assign(s->mN1, false); s->nInliers_ = 0;
+            if (n_hits[j] > 0) {
+                done[j] = hit_iter[j]; best[j] = hit_inliers[j]; best_iter[j] = hit_iter[j]; no_more[j] = hit_iter[j] >= max_its[j];
+                std::copy(hit_sim3.begin() + (size_t)j * 13, hit_sim3.begin() + (size_t)(j + 1) * 13, best_sim3.begin() + (size_t)j * 13);
+                patched = true;
+                for (int i = 0; i < s->mN1 && i < b.S; i++) s->vbInliers_[i] = rows[(size_t)j * b.S + i] != 0;
+                s->nInliers_ = hit_inliers[j];
+            } else bNoMore[j] = no_more[j] != 0;
+            const float *q = best_sim3.data() + (size_t)j * 13;
+            s->best_R_ = cv::Mat(3, 3, CV_32F); s->best_t_ = cv::Mat(3, 1, CV_32F); s->best_s_ = q[12];
+            for (int r = 0; r < 3; r++) { for (int c = 0; c < 3; c++) s->best_R_.template at<float>(r, c) = q[3 * r + c]; s->best_t_.template at<float>(r, 0) = q[9 + r]; }
+            if (n_hits[j] > 0) {
+                cv::Mat T12(4, 4, CV_32F);
+                for (int r = 0; r < 4; r++) for (int c = 0; c < 4; c++) T12.template at<float>(r, c) = r == c ? 1.0f : 0.0f;
+                for (int r = 0; r < 3; r++) { for (int c = 0; c < 3; c++) T12.template at<float>(r, c) = q[3 * r + c] * q[12] + 0.0f; T12.template at<float>(r, 3) = q[9 + r]; }
+                T[j] = T12;
+            }
+        }
+        if (patched) {
+            b.iterations_done.upload(done.data(), done.size()); b.best_inliers.upload(best.data(), best.size()); b.best_iter.upload(best_iter.data(), best_iter.size());
+            b.best_sim3.upload(best_sim3.data(), best_sim3.size()); b.no_more.upload(no_more.data(), no_more.size());
+        }
+    }
+private:
+    void Draw()
+    {
+        rand3_.resize((size_t)max_iterations_ * 3);
+        for (int32_t &r : rand3_) r = (int32_t)rand();
+    }
+    bool mbFixScale;
+    int device_, mN1 = 0, n_[2] = {0, 0}, min_inliers_ = 6, max_iterations_ = 300, nInliers_ = 0;
+    double prob_ = 0.99;
+    std::vector<plf_keypoint> keys_[2];
+    std::vector<int32_t> mps_[2], obs_[2], match_, rand3_;
+    plf_frustum_pose pose_[2];
+    std::vector<float> world_, sigma2_;
+    std::vector<uint8_t> bad_;
+    plf_camera cam_;
+    std::vector<bool> vbInliers_;
+    cv::Mat best_R_, best_t_;
+    float best_s_ = 1.0f;
+    std::unique_ptr<plf::Sim3Batch> batch_;
+    std::vector<Sim3Solver *> own_;
+    Held held_;
 };
 }  // namespace ORB_SLAM2_PLF
 #endif

@@ -22,3 +22,5 @@ from . import track  # noqa: F401
 from .track import close_points, need_new_keyframe, motion_model, clean_matches, kf_state  # noqa: F401
 from . import triangulate  # noqa: F401
 from .triangulate import triangulate_points, KeyFrameSet  # noqa: F401
+from . import sim3  # noqa: F401
+from .sim3 import sim3_pairs, sim3_iterate, Sim3Solver, Sim3KeyFrames  # noqa: F401

@@ -394,3 +394,37 @@ def tri_prototypes(l, name="plf_triangulate_points"):
     tail = [I, P] if name == "plf_triangulate_points" else []
     getattr(l, name).argtypes = [C.POINTER(TriangulateView), C.POINTER(Camera), C.POINTER(TriangulateJobs), C.POINTER(TriangulateMarks), P, P, P, P, P, P] + tail
     return l
+
+
+class Sim3View(C.Structure):
+    _fields_ = [("n_kf", C.c_int32), ("kf_keys", C.c_void_p), ("kf_n", C.c_void_p), ("kf_pose", C.c_void_p), ("kf_mappoints", C.c_void_p),
+                ("kf_obs_index", C.c_void_p), ("world_pos", C.c_void_p), ("point_bad", C.c_void_p), ("n_points", C.c_int32),
+                ("level_sigma2", C.c_void_p), ("nlevels", C.c_int32)]
+
+
+class Sim3Jobs(C.Structure):
+    _fields_ = [("n_jobs", C.c_int32), ("kp_stride", C.c_int32), ("pair_stride", C.c_int32), ("job_kf1", C.c_void_p), ("job_kf2", C.c_void_p),
+                ("match12", C.c_void_p), ("fix_scale", C.c_void_p)]
+
+
+class Sim3PairSet(C.Structure):
+    _fields_ = [(n, C.c_void_p) for n in ("idx1", "x3dc1", "x3dc2", "max_err1", "max_err2", "p1im1", "p2im2", "n_pairs", "status")]
+
+
+class Sim3State(C.Structure):
+    _fields_ = [(n, C.c_void_p) for n in ("iterations_done", "best_inliers", "best_iter", "max_its", "best_sim3", "no_more")]
+
+
+class Sim3Hits(C.Structure):
+    _fields_ = [("max_hits", C.c_int32)] + [(n, C.c_void_p) for n in ("n_hits", "hit_iter", "hit_inliers", "hit_sim3", "hit_inlier12")]
+
+
+def sim3_prototypes(l, prefix="plf_sim3"):
+    """the device calls; prefix="sim3_cpu": the host loops of tools/sim3_cpu.cpp, the same signatures without device and stream"""
+    P, I = C.c_void_p, C.c_int32
+    tail = [I, P] if prefix == "plf_sim3" else []
+    getattr(l, prefix + "_its_for_n").argtypes = [C.c_double, I, I, I, P]
+    getattr(l, prefix + "_pairs").argtypes = [C.POINTER(Sim3View), C.POINTER(Camera), C.POINTER(Sim3Jobs), P, C.POINTER(Sim3PairSet), C.POINTER(Sim3State)] + tail
+    getattr(l, prefix + "_iterate").argtypes = [C.POINTER(Sim3Jobs), C.POINTER(Camera), C.POINTER(Sim3PairSet), P, I, I, I, P, C.POINTER(Sim3State), P,
+                                                C.POINTER(Sim3Hits)] + tail
+    return l

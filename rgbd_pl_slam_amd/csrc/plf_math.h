@@ -269,6 +269,77 @@ PLF_MATH void plf_sincos_d(double theta, double *sinp, double *cosp)
     *cosp = q == 0 ? c : q == 1 ? -s : q == 2 ? -c : s;
 }
 
+// atan and atan2 of doubles as ONE explicit sequence of IEEE double operations (fdlibm's s_atan.c / e_atan2.c, Sun Microsystems 1993, freely usable),
+// no FMA, no libm call: the rotation angle of Sim3Solver::ComputeSim3 (sim3_common.h), shared by the device, the host loop and the definition
+// (tests/sim3ref.py).  glibc's own atan2 is another algorithm; the last bit is fixed HERE and measured against libm in tests/test_sim3_ref.py.
+PLF_MATH uint64_t plf_double_bits(double x) { uint64_t u; __builtin_memcpy(&u, &x, 8); return u; }
+PLF_MATH double plf_atan_fdlibm_d(double x)
+{
+    const double hi0 = 4.63647609000806093515e-01, hi1 = 7.85398163397448278999e-01, hi2 = 9.82793723247329054082e-01, hi3 = 1.57079632679489655800e+00;
+    const double lo0 = 2.26987774529616870924e-17, lo1 = 3.06161699786838301793e-17, lo2 = 1.39033110312309984516e-17, lo3 = 6.12323399573676603587e-17;
+    const double a0 = 3.33333333333329318027e-01, a1 = -1.99999999998764832476e-01, a2 = 1.42857142725034663711e-01, a3 = -1.11111104054623557880e-01,
+                 a4 = 9.09088713343650656196e-02, a5 = -7.69187620504482999495e-02, a6 = 6.66107313738753120669e-02, a7 = -5.83357013379057348645e-02,
+                 a8 = 4.97687799461593236017e-02, a9 = -3.65315727442169155270e-02, a10 = 1.62858201153657823623e-02;
+    const uint64_t bits = plf_double_bits(x);
+    const uint32_t hx = (uint32_t)(bits >> 32), ix = hx & 0x7fffffffu, lx = (uint32_t)bits;
+    const bool neg = (hx >> 31) != 0;
+    int id;
+    if (ix >= 0x44100000u) {                          // |x| >= 2^66
+        if (ix > 0x7ff00000u || (ix == 0x7ff00000u && lx != 0)) return x + x;   // NaN
+        return neg ? -hi3 - lo3 : hi3 + lo3;
+    }
+    if (ix < 0x3fdc0000u) {                           // |x| < 0.4375
+        if (ix < 0x3e200000u) return x;               // |x| < 2^-29
+        id = -1;
+    } else {
+        x = fabs(x);
+        if (ix < 0x3ff30000u) {                       // |x| < 1.1875
+            if (ix < 0x3fe60000u) { id = 0; x = (2.0 * x - 1.0) / (2.0 + x); }
+            else { id = 1; x = (x - 1.0) / (x + 1.0); }
+        } else {
+            if (ix < 0x40038000u) { id = 2; x = (x - 1.5) / (1.0 + 1.5 * x); }
+            else { id = 3; x = -1.0 / x; }
+        }
+    }
+    const double z = x * x;
+    const double w = z * z;
+    const double s1 = z * (a0 + w * (a2 + w * (a4 + w * (a6 + w * (a8 + w * a10)))));
+    const double s2 = w * (a1 + w * (a3 + w * (a5 + w * (a7 + w * a9))));
+    if (id < 0) return x - x * (s1 + s2);
+    const double hi = id == 0 ? hi0 : id == 1 ? hi1 : id == 2 ? hi2 : hi3;
+    const double lo = id == 0 ? lo0 : id == 1 ? lo1 : id == 2 ? lo2 : lo3;
+    const double r = hi - ((x * (s1 + s2) - lo) - x);
+    return neg ? -r : r;
+}
+
+PLF_MATH double plf_atan2_fdlibm_d(double y, double x)
+{
+    const double tiny = 1.0e-300, pi_o_4 = 7.8539816339744827900e-01, pi_o_2 = 1.5707963267948965580e+00, pi = 3.1415926535897931160e+00,
+                 pi_lo = 1.2246467991473531772e-16;
+    const uint64_t bx = plf_double_bits(x), by = plf_double_bits(y);
+    const uint32_t hx = (uint32_t)(bx >> 32), lx = (uint32_t)bx, hy = (uint32_t)(by >> 32), ly = (uint32_t)by;
+    const uint32_t ix = hx & 0x7fffffffu, iy = hy & 0x7fffffffu;
+    if (ix > 0x7ff00000u || (ix == 0x7ff00000u && lx != 0) || iy > 0x7ff00000u || (iy == 0x7ff00000u && ly != 0)) return x + y;   // NaN
+    if (hx == 0x3ff00000u && lx == 0) return plf_atan_fdlibm_d(y);                // x = 1.0
+    const int m = (int)((hy >> 31) & 1u) | (int)((hx >> 30) & 2u);               // 2 * sign(x) + sign(y)
+    if ((iy | ly) == 0) return m < 2 ? y : m == 2 ? pi + tiny : -pi - tiny;
+    if ((ix | lx) == 0) return (hy >> 31) ? -pi_o_2 - tiny : pi_o_2 + tiny;
+    if (ix == 0x7ff00000u) {
+        if (iy == 0x7ff00000u) return m == 0 ? pi_o_4 + tiny : m == 1 ? -pi_o_4 - tiny : m == 2 ? 3.0 * pi_o_4 + tiny : -3.0 * pi_o_4 - tiny;
+        return m == 0 ? 0.0 : m == 1 ? -0.0 : m == 2 ? pi + tiny : -pi - tiny;
+    }
+    if (iy == 0x7ff00000u) return (hy >> 31) ? -pi_o_2 - tiny : pi_o_2 + tiny;
+    const int k = ((int)iy - (int)ix) >> 20;
+    double z;
+    if (k > 60) z = pi_o_2 + 0.5 * pi_lo;                                         // |y / x| > 2^60
+    else if ((hx >> 31) && k < -60) z = 0.0;                                      // |y| / x < -2^60
+    else z = plf_atan_fdlibm_d(fabs(y / x));
+    if (m == 0) return z;
+    if (m == 1) return -z;
+    if (m == 2) return pi - (z - pi_lo);
+    return (z - pi_lo) - pi;
+}
+
 // Thresholds of the cheap alignment pre-test of region_grow (lsd_kernels.hip): t1 <= tan(prec - delta), t2 >= tan(prec + delta), delta = 0.05 degrees.
 // The pre-test only sorts candidates into "surely aligned", "surely not" and "border" (decided by the reference's own test), so ANY t1 below and
 // t2 above those tangents is sound: single-precision tanf with a 1e-4 relative safety factor (its error is ~1e-7; the band is ~2.5e-3 wide) keeps
