@@ -1496,7 +1496,7 @@ int plf_triangulate_points(const plf_triangulate_view *v, const plf_camera *cam,
 /* ------------------------------------------------------------------------------------------------
  * Sim3 solver -- class Sim3Solver include/Sim3Solver.h as LoopClosing::ComputeSim3 drives it: the constructor (plf_sim3_pairs) and iterate()
  * (plf_sim3_iterate) for any number of solvers per call, between the rows plf_match_bow_kf writes and the transform plf_match_sim3 /
- * plf_match_project_sim3 / plf_match_fuse_sim3 read.  OptimizeSim3 and PnPsolver are not here.
+ * plf_match_project_sim3 / plf_match_fuse_sim3 read.  OptimizeSim3 is the next section ("Sim3 optimisation"); PnPsolver is not here.
  *
  * The definition is tests/sim3ref.py, one float32 / float64 operation per statement.  From the disassembly of the binary (Sim3Solver::Sim3Solver
  * so@0x10e950, SetRansacParameters so@0x10e770, iterate so@0x10d010, ComputeSim3 so@0x104a90, ComputeCentroid so@0x104370, CheckInliers so@0x10bdd0,
@@ -1621,6 +1621,79 @@ int plf_sim3_pairs(const plf_sim3_view *v, const plf_camera *cam, const plf_sim3
 int plf_sim3_iterate(const plf_sim3_jobs *jobs, const plf_camera *cam, const plf_sim3_pairset *pairs, const int32_t *rand3, int32_t rand_stride,
                      int32_t iter_count, int32_t min_inliers, const uint8_t *active, const plf_sim3_state *state, int32_t *count,
                      const plf_sim3_hits *hits, int32_t device, void *stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * Sim3 optimisation -- Optimizer::OptimizeSim3(pKF1, pKF2, vpMatches1, g2oS12, th2, bFixScale) (so@0xb60c0) as LoopClosing::ComputeSim3 calls it
+ * between SearchBySim3 and SearchByProjection, for any number of candidates per call, and the statement before SearchBySim3 that keeps the
+ * solver's inliers (plf_sim3_keep_inliers).
+ *
+ * The definition is tests/sim3optref.py, one double operation per statement.  From the disassembly of the binary:
+ *  - Solver: g2o::LinearSolverDense<MatrixXd> (vtable so@0xb613b) under g2o::BlockSolver<BlockSolverTraits<-1, -1>> (vtable so@0xb61df) under
+ *    OptimizationAlgorithmLevenberg (so@0xb62ab): Eigen's dense LDLT of the one 7x7 block.
+ *  - Graph: one VertexSim3Expmap (so@0xb6341), _fix_scale = bFixScale, estimate g2oS12, the calibration of both keyframes as widened floats.  The loop
+ *    over vpMatches1 (so@0xb65f6): skipped when the match is NULL (so@0xb65fd); GetIndexInKeyFrame(pKF2) of the match (so@0xb65cc) is taken BEFORE the
+ *    point of keyframe 1 is tested for NULL (so@0xb65d1); then pMP1->isBad() (so@0xb6613), pMP2->isBad() (so@0xb661f) and i2 >= 0 as the inverted sign
+ *    bit (so@0xb662a-0xb6631).  Unlike the Sim3Solver constructor, keyframe 1's own index is NOT asked for: the observation is mvKeysUn[i].  The two
+ *    fixed points are R1w * P3D1w + t1w and R2w * P3D2w + t2w as cv::operator* and cv::operator+ (so@0xb667d, 0xb6693; 0xb689b, 0xb68b1) through
+ *    Converter::toVector3d (so@0xb67b6, 0xb69e1); e12 = EdgeSim3ProjectXYZ (so@0xb6aea) on point 2, e21 = EdgeInverseSim3ProjectXYZ (so@0xb6c62) on
+ *    point 1, each with a RobustKernelHuber whose delta is deltaHuber = sqrtf(th2) (vsqrtss so@0xb652a), added in that order (so@0xb6c01, 0xb6d62).
+ *  - Flow: initializeOptimization, optimize(5) (so@0xb6dfc-0xb6e0b); a correspondence is bad when e12->chi2() > th2 || e21->chi2() > th2, compared
+ *    as DOUBLES with th2 widened (vcvtss2sd, vucomisd, jbe / ja so@0xb6ed7-0xb6eeb, 0xb7090-0xb7098: unlike PoseOptimization's float test; a NaN chi2
+ *    is not bad); the match is nulled (so@0xb6f09) and both edges removed (so@0xb6f11, 0xb6f20); nMoreIterations = nBad > 0 ? 10 : 5 (sbb / and / add
+ *    so@0xb6f60-0xb6f6c); nCorrespondences - nBad < 10 returns 0 (cmp $9, jg so@0xb6f7e) with g2oS12 untouched; else initializeOptimization,
+ *    optimize(nMoreIterations) (so@0xb7163-0xb716f), the same test through the virtual chi2() (so@0xb71c8, 0xb7277) nulls matches (so@0xb7202) and
+ *    counts nIn (so@0xb7288); g2oS12 = the vertex' estimate (so@0xb7215-0xb725c).
+ *  - chi2(): g2o::BaseEdge<2, Vector2d>::chi2 is in the binary (so@0xb7d00; inlined at so@0xb6e8e and so@0xb7051) and IS FUSED:
+ *    fma(e1, fma(I11, e1, e0 * I10), fma(I01, e1, e0 * I00) * e0) with the full 2x2 information.  Upstream's _error.dot(information() * _error) has no
+ *    fused operation in its source; the binary wins, for every chi2 of the definition.
+ * The binary agrees with upstream ORB-SLAM2 in control flow and constants; it DIFFERS in the fused chi2.
+ * PARITY UNPINNED -- VertexSim3Expmap::VertexSim3Expmap, the two edge constructors, their computeError, linearizeOplus, constructQuadraticForm,
+ * RobustKernelHuber::robustify, SparseOptimizer and OptimizationAlgorithmLevenberg are `U` symbols of a g2o library that is not in the snapshot.
+ * They are restated from the sources the reference ships, without FMA:
+ *  - types/sim3.h: Sim3(Matrix3d, Vector3d, double) = Quaterniond(R) NOT normalised; Sim3(Vector7d) with all four A / B / C branches at eps = 1e-5,
+ *    Omega * Omega, R = (I + Omega) + Omega^2 below eps (every perturbation takes this), else (I + (sin / theta) Omega) + ((1 - cos) / theta^2) Omega^2,
+ *    W = (A Omega + B Omega^2) + C I, t = W upsilon, r = Quaterniond(R); inverse() = (r*, r* ((-1 / s) t), 1 / s); operator* = (r r', s (r t') + t,
+ *    s s'); map = s (r x) + t.  std::exp is plf_exp_fdlibm_d (csrc/plf_math.h: fdlibm's __ieee754_exp without FMA; its last bit against glibc is
+ *    reported by tests/test_sim3opt_ref.py, not asserted), reached only with a free scale; sin / cos are plf_sincos_d as at plf_pose_optimize.
+ *  - types/types_seven_dof_expmap.h: oplusImpl zeroes update[6] under _fix_scale and sets Sim3(update) * estimate; the errors are
+ *    obs - cam_map(project(S.map(X2))) and obs - cam_map(project(S.inverse().map(X1))), project = (x / z, y / z), cam_map = v f + c.
+ *    Both linearizeOplus are commented out there, so core/base_binary_edge.hpp:131-200 runs: only the free Sim3 vertex, per dimension d the column
+ *    (1 / (2 * 1e-9)) * (e(+1e-9 e_d) - e(-1e-9 e_d)), each a full oplusImpl on a pushed copy.  This is NOT an analytic Jacobian.
+ *  - core/base_binary_edge.hpp:55-120, core/base_edge.h:96, robust_kernel_impl.cpp: rho from chi2(), omega_r = (-Omega e) rho1, b += J^T omega_r,
+ *    H += (J^T (rho1 Omega)) J; the Levenberg loop, Eigen's LDLT order, the sums in edge order, the solver's x before a first successful solve and the
+ *    errors a rejected last trial leaves: as fixed by tests/poseref.py for 6x6, here 7x7 (pose_ldlt_solve_n<7>).  With a fixed scale column 6 of
+ *    every Jacobian is exactly zero, so row and column 6 of H hold only the damping.
+ * DEVIATIONS, as plf_sim3_pairs: an octave outside the table is clamped; an index from kf_obs_index outside [0, kf_n) and a map-point id outside
+ * [0, n_points) count as "none"; entries of match12 >= kf_n[kf2] are skipped.
+ *
+ * plf_sim3_optimize, job j: slots job_kf1[j], job_kf2[j] of the plf_sim3_view (level_sigma2 is not read); match12 + j * kp_stride as plf_match_sim3
+ * left it (vpMatches1: the feature of keyframe 2, < 0 none), IN/OUT: the entry of a culled correspondence becomes -1; i over [0, min(kf_n[kf1],
+ * kp_stride)).  g2oS12 on entry is Sim3(Converter::toMatrix3d(R), Converter::toVector3d(t), s) of sim3_in + 13 j.  sim3_out + 8 j: qx qy qz qw tx ty tz s
+ * of g2oS12 on return; n_inliers[j] the return value; status[j] a mask of PLF_SIM3OPT_FEW (returned 0 at the `< 10` test: sim3_out is the input
+ * converted, the matches nulled so far stay nulled), PLF_SIM3OPT_NONFINITE (an entry of sim3_out is not finite), PLF_SIM3OPT_BAD_SLOT (a slot outside
+ * [0, n_kf): no work, sim3_out is the input converted, match12 untouched, n_inliers 0, scw_out NOT written).  scw_out + 16 j (optional) =
+ * Converter::toCvMat(g2oS12 * g2o::Sim3(R2w, t2w, 1.0)) with the pose of slot job_kf2: the product in double, s * R and t rounded to float, row-major
+ * 4x4 -- the mScw plf_match_project_sim3 / plf_match_fuse_sim3 take; written whatever the inlier count.
+ * plf_sim3_keep_inliers: match12[j][i] = inlier12[j * kp_stride + i] ? match12[j][i] : -1 for i < min(kf_n_of_job[j], kp_stride) (NULL: kp_stride);
+ * inlier12 is the hit_inlier12 row the caller chose (its rows are kp_stride apart).
+ * Stateless; every array is DEVICE memory (the structs are host); asynchronous on `stream`; nothing is read back; no scratch.  PLF_E_BADARG before any
+ * device work: a NULL required array, negative sizes, kp_stride < 1, nlevels < 1, th2 not positive and finite.  NaN / Inf values, slots, ids and
+ * indices out of range fault nowhere.
+ * k_sim3_optimize: one workgroup per job, one edge per lane; csrc/sim3opt_kernels.hip has the schedule.
+ * ---------------------------------------------------------------------------------------------- */
+enum { PLF_SIM3OPT_BAD_SLOT = 2, PLF_SIM3OPT_FEW = 4, PLF_SIM3OPT_NONFINITE = 8 };
+typedef struct {
+    int32_t n_jobs, kp_stride;
+    const int32_t *job_kf1, *job_kf2;                     /* n_jobs: slots of the plf_sim3_view */
+    const float *sim3_in;                                 /* n_jobs x 13: R12 9, t12 3, s12 -- the hit_sim3 / best_sim3 layout of plf_sim3_iterate */
+    const uint8_t *fix_scale;                             /* n_jobs: bFixScale */
+    const float *inv_level_sigma2;                        /* v->nlevels: mvInvLevelSigma2 */
+    float th2;
+} plf_sim3opt_jobs;
+int plf_sim3_optimize(const plf_sim3_view *v, const plf_camera *cam, const plf_sim3opt_jobs *jobs, int32_t *match12, double *sim3_out, float *scw_out,
+                      int32_t *n_inliers, int32_t *status, int32_t device, void *stream);
+int plf_sim3_keep_inliers(int32_t *match12, const uint8_t *inlier12, const int32_t *kf_n_of_job, int32_t n_jobs, int32_t kp_stride, int32_t device,
+                          void *stream);
 
 #ifdef __cplusplus
 }

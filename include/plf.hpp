@@ -800,6 +800,24 @@ public:
         const plf_sim3_hits h = {MH, n_hits.get(), hit_iter.get(), hit_inliers.get(), hit_sim3.get(), hit_inlier12.get()};
         check(plf_sim3_iterate(&jobs, &cam_, &p, rand3.get(), RS, nIterations, min_inliers, active_dev, &st, count.get(), &h, device_, stream), "Sim3Solver::iterate");
     }
+    // ComputeSim3's `vpMapPointMatches[i] = vbInliers[i] ? matches[i] : NULL` for every job, from the FIRST stored hit of the last Iterate(): match12_dev
+    // (J x S, the rows Pairs() read, or a copy of them) is changed in place.  Needs max_hits == 1 (the hit rows are then kp_stride apart).
+    void KeepInliers(int32_t *match12_dev, const int32_t *kf_n_of_job_dev = nullptr, void *stream = nullptr)
+    {
+        if (MH != 1) throw std::runtime_error("Sim3Batch::KeepInliers: max_hits must be 1");
+        check(plf_sim3_keep_inliers(match12_dev, hit_inlier12.get(), kf_n_of_job_dev, J, S, device_, stream), "ComputeSim3: keep inliers");
+    }
+    // Optimizer::OptimizeSim3 of every job in one launch, started from sim3_in_dev (J x 13; default: the first stored hit of the last Iterate(), max_hits
+    // == 1) with the jobs' fix_scale: match12_dev is vpMatches1 IN/OUT; sim3_out_dev J x 8 doubles (g2oS12: qx qy qz qw tx ty tz s), scw_out_dev J x 16
+    // floats or NULL (mScw for plf_match_project_sim3 / plf_match_fuse_sim3), n_inliers_dev and status_dev J.  Only enqueues on `stream`.
+    void Optimize(const plf_sim3_view &keyframes, const plf_camera &cam, const int32_t *job_kf1_dev, const int32_t *job_kf2_dev, int32_t *match12_dev,
+                  const float *inv_level_sigma2_dev, float th2, double *sim3_out_dev, float *scw_out_dev, int32_t *n_inliers_dev, int32_t *status_dev,
+                  const float *sim3_in_dev = nullptr, void *stream = nullptr)
+    {
+        if (!sim3_in_dev && MH != 1) throw std::runtime_error("Sim3Batch::Optimize: give sim3_in_dev, or store one hit per job");
+        const plf_sim3opt_jobs jobs = {J, S, job_kf1_dev, job_kf2_dev, sim3_in_dev ? sim3_in_dev : hit_sim3.get(), fix_scale.get(), inv_level_sigma2_dev, th2};
+        check(plf_sim3_optimize(&keyframes, &cam, &jobs, match12_dev, sim3_out_dev, scw_out_dev, n_inliers_dev, status_dev, device_, stream), "Optimizer::OptimizeSim3");
+    }
     plf_sim3_pairset pairset() const { return {idx1.get(), x3dc1.get(), x3dc2.get(), max_err1.get(), max_err2.get(), p1im1.get(), p2im2.get(), n_pairs.get(), status.get()}; }
     plf_sim3_state state() const { return {iterations_done.get(), best_inliers.get(), best_iter.get(), max_its.get(), best_sim3.get(), no_more.get()}; }
     const int J, S, PS, RS, MH;
@@ -1802,6 +1820,100 @@ struct Optimizer {
             for (int c = 0; c < 4; c++) Tcw.template at<float>(r, c) = r < 3 ? pout.Tcw[4 * r + c] : (c == 3 ? 1.0f : 0.0f);
         pFrame->SetPose(Tcw);
         return dn.download()[0];
+    }
+
+    // Optimizer::OptimizeSim3(pKF1, pKF2, vpMatches1, g2oS12, th2, bFixScale) (so@0xb60c0), the reference's signature over its own KeyFrame / MapPoint and
+    // g2o::Sim3: the two keyframes, the points either sees and the matches go to the device as a plf_sim3_view of two slots, plf_sim3_optimize refines the
+    // transform, and the caller gets what the reference's body leaves: the culled matches NULL in vpMatches1, g2oS12 = the estimate (untouched when the
+    // call returns 0 at its `< 10` test), the return value nIn.  plf_sim3_optimize takes the start as the floats ComputeSim3 has (R, t, s): g2oS12 is
+    // narrowed to them -- rotation().toRotationMatrix() (Eigen's 2x form), translation() and scale() rounded to float -- and widened again on the device,
+    // which for a g2oS12 built from floats as ComputeSim3 builds it differs from it by the rounding of that round trip only.  The camera and
+    // mvInvLevelSigma2 are taken from pKF1 for both keyframes (the reference reads pKF2->mK and pKF2->mvInvLevelSigma2 for the second edge): the same values
+    // for one sensor.  A match whose GetIndexInKeyFrame(pKF2) is no key point of pKF2 is skipped, as in the reference, and stays as it is.  For ONE
+    // candidate the adapter uploads and waits; a loop closer with its keyframes resident calls plf_sim3_optimize on all candidates at once.
+    template <class KeyFrameT, class MapPointT, class Sim3T>
+    static int OptimizeSim3(KeyFrameT *pKF1, KeyFrameT *pKF2, std::vector<MapPointT *> &vpMatches1, Sim3T &g2oS12, const float th2, const bool bFixScale, int device = 0)
+    {
+        const std::vector<MapPointT *> vpMapPoints1 = pKF1->GetMapPointMatches();
+        KeyFrameT *kf[2] = {pKF1, pKF2};
+        const int n1 = (int)pKF1->mvKeysUn.size(), n2 = (int)pKF2->mvKeysUn.size(), N = (int)vpMatches1.size();
+        const int S = std::max(n1, 1);
+        std::vector<plf_keypoint> keys[2];
+        std::vector<int32_t> mps[2], match(S, -1), slots = {n1, n2};
+        plf_frustum_pose pose[2];
+        std::vector<float> world;
+        std::vector<uint8_t> bad;
+        std::unordered_map<MapPointT *, int32_t> ids;
+        auto id_of = [&](MapPointT *p) {
+            auto it = ids.find(p);
+            if (it != ids.end()) return it->second;
+            const int32_t id = (int32_t)ids.size();
+            ids.emplace(p, id);
+            const cv::Mat X = p->GetWorldPos();
+            for (int r = 0; r < 3; r++) world.push_back(X.template at<float>(r, 0));
+            bad.push_back(p->isBad() ? 1 : 0);
+            return id;
+        };
+        for (int s = 0; s < 2; s++) {
+            const int n = slots[s];
+            keys[s].resize(std::max(n, 1));
+            if (n) std::memcpy((void *)keys[s].data(), kf[s]->mvKeysUn.data(), (size_t)n * sizeof(plf_keypoint));
+            mps[s].assign(std::max(n, 1), -1);
+            const cv::Mat Rcw = kf[s]->GetRotation(), tcw = kf[s]->GetTranslation();
+            for (int r = 0; r < 3; r++) {
+                for (int c = 0; c < 3; c++) pose[s].Rcw[3 * r + c] = Rcw.template at<float>(r, c);
+                pose[s].tcw[r] = tcw.template at<float>(r, 0);
+                pose[s].Ow[r] = 0.0f;
+            }
+        }
+        for (int i = 0; i < N && i < n1; i++) {
+            MapPointT *pMP2 = vpMatches1[i];
+            if (!pMP2) continue;
+            const int i2 = pMP2->GetIndexInKeyFrame(pKF2);
+            MapPointT *pMP1 = i < (int)vpMapPoints1.size() ? vpMapPoints1[i] : nullptr;
+            if (!pMP1 || i2 < 0 || i2 >= n2) continue;
+            mps[0][i] = id_of(pMP1);
+            mps[1][i2] = id_of(pMP2);
+            match[i] = i2;
+        }
+        if (world.empty()) { world.assign(3, 0.0f); bad.assign(1, 1); }
+        // the start, narrowed to the floats of the C ABI
+        const double qx = g2oS12.rotation().x(), qy = g2oS12.rotation().y(), qz = g2oS12.rotation().z(), qw = g2oS12.rotation().w();
+        const double tx = 2.0 * qx, ty = 2.0 * qy, tz = 2.0 * qz;
+        const double twx = tx * qw, twy = ty * qw, twz = tz * qw, txx = tx * qx, txy = ty * qx, txz = tz * qx, tyy = ty * qy, tyz = tz * qy, tzz = tz * qz;
+        const std::vector<float> sim3_in = {(float)(1.0 - (tyy + tzz)), (float)(txy - twz), (float)(txz + twy), (float)(txy + twz), (float)(1.0 - (txx + tzz)),
+                                            (float)(tyz - twx), (float)(txz - twy), (float)(tyz + twx), (float)(1.0 - (txx + tyy)), (float)g2oS12.translation()[0],
+                                            (float)g2oS12.translation()[1], (float)g2oS12.translation()[2], (float)g2oS12.scale()};
+        const std::vector<float> inv_sigma2(pKF1->mvInvLevelSigma2.begin(), pKF1->mvInvLevelSigma2.end());
+        plf::DeviceArray<plf_keypoint> dk0(keys[0], device), dk1(keys[1], device);
+        plf::DeviceArray<int32_t> dm0(mps[0], device), dm1(mps[1], device), dn(slots, device), dmatch(match, device), dkf1(std::vector<int32_t>(1, 0), device),
+            dkf2(std::vector<int32_t>(1, 1), device), dnin(1, device), dst(1, device);
+        const std::vector<const plf_keypoint *> t_keys = {dk0.get(), dk1.get()};
+        const std::vector<const int32_t *> t_mps = {dm0.get(), dm1.get()};
+        plf::DeviceArray<const plf_keypoint *> dt_keys(t_keys, device);
+        plf::DeviceArray<const int32_t *> dt_mps(t_mps, device);
+        plf::DeviceArray<plf_frustum_pose> dpose(std::vector<plf_frustum_pose>(pose, pose + 2), device);
+        plf::DeviceArray<float> dworld(world, device), dsig(inv_sigma2, device), din(sim3_in, device);
+        plf::DeviceArray<uint8_t> dbad(bad, device), dfix(std::vector<uint8_t>(1, bFixScale ? 1 : 0), device);
+        plf::DeviceArray<double> dout(8, device);
+        plf_sim3_view v = {};
+        v.n_kf = 2; v.kf_keys = dt_keys.get(); v.kf_n = dn.get(); v.kf_pose = dpose.get(); v.kf_mappoints = dt_mps.get(); v.kf_obs_index = nullptr;
+        v.world_pos = dworld.get(); v.point_bad = dbad.get(); v.n_points = (int32_t)bad.size(); v.level_sigma2 = nullptr; v.nlevels = (int32_t)inv_sigma2.size();
+        plf_camera cam = {};
+        cam.fx = pKF1->fx; cam.fy = pKF1->fy; cam.cx = pKF1->cx; cam.cy = pKF1->cy;
+        const plf_sim3opt_jobs jobs = {1, S, dkf1.get(), dkf2.get(), din.get(), dfix.get(), dsig.get(), th2};
+        plf::check(plf_sim3_optimize(&v, &cam, &jobs, dmatch.get(), dout.get(), nullptr, dnin.get(), dst.get(), device, nullptr), "OptimizeSim3");
+        const std::vector<int32_t> after = dmatch.download();          // a NULL-stream download waits for the device first
+        for (int i = 0; i < N && i < n1; i++)
+            if (match[i] >= 0 && after[i] < 0) vpMatches1[i] = static_cast<MapPointT *>(nullptr);
+        const int status = dst.download()[0];
+        if (!(status & PLF_SIM3OPT_FEW)) {
+            const std::vector<double> o = dout.download();
+            g2oS12.rotation().x() = o[0]; g2oS12.rotation().y() = o[1]; g2oS12.rotation().z() = o[2]; g2oS12.rotation().w() = o[3];
+            g2oS12.translation()[0] = o[4]; g2oS12.translation()[1] = o[5]; g2oS12.translation()[2] = o[6];
+            g2oS12.scale() = o[7];
+        }
+        return dnin.download()[0];
     }
 };
 

@@ -24,3 +24,5 @@ from . import triangulate  # noqa: F401
 from .triangulate import triangulate_points, KeyFrameSet  # noqa: F401
 from . import sim3  # noqa: F401
 from .sim3 import sim3_pairs, sim3_iterate, Sim3Solver, Sim3KeyFrames  # noqa: F401
+from . import sim3opt  # noqa: F401
+from .sim3opt import sim3_optimize, sim3_keep_inliers  # noqa: F401

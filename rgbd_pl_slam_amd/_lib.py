@@ -428,3 +428,18 @@ def sim3_prototypes(l, prefix="plf_sim3"):
     getattr(l, prefix + "_iterate").argtypes = [C.POINTER(Sim3Jobs), C.POINTER(Camera), C.POINTER(Sim3PairSet), P, I, I, I, P, C.POINTER(Sim3State), P,
                                                 C.POINTER(Sim3Hits)] + tail
     return l
+
+
+class Sim3OptJobs(C.Structure):
+    _fields_ = [("n_jobs", C.c_int32), ("kp_stride", C.c_int32), ("job_kf1", C.c_void_p), ("job_kf2", C.c_void_p), ("sim3_in", C.c_void_p),
+                ("fix_scale", C.c_void_p), ("inv_level_sigma2", C.c_void_p), ("th2", C.c_float)]
+
+
+def sim3opt_prototypes(l, prefix="plf_sim3"):
+    """the device calls; prefix="sim3opt_cpu": the host loops of tools/sim3opt_cpu.cpp, the same signatures without device and stream (the optimise
+    loop takes one more pointer: the iteration counts)"""
+    P, I = C.c_void_p, C.c_int32
+    tail = [I, P] if prefix == "plf_sim3" else []
+    getattr(l, prefix + "_optimize").argtypes = [C.POINTER(Sim3View), C.POINTER(Camera), C.POINTER(Sim3OptJobs), P, P, P, P, P] + (tail or [P])
+    getattr(l, prefix + "_keep_inliers").argtypes = [P, P, P, I, I] + tail
+    return l

@@ -340,6 +340,51 @@ PLF_MATH double plf_atan2_fdlibm_d(double y, double x)
     return (z - pi_lo) - pi;
 }
 
+// exp of a double, likewise: fdlibm's e_exp.c (__ieee754_exp) as plain IEEE double operations, no FMA, no libm call: std::exp(sigma) of g2o's
+// Sim3(Vector7d) (sim3opt_common.h), shared by the device, the host loop and the definition (tests/sim3optref.py: exp_d).  The last bit against glibc is
+// fixed HERE and measured in tests/test_sim3opt_ref.py.
+PLF_MATH double plf_bits_double(uint64_t u) { double x; __builtin_memcpy(&x, &u, 8); return x; }
+PLF_MATH double plf_exp_fdlibm_d(double x)
+{
+    const double ln2hi = 6.93147180369123816490e-01, ln2lo = 1.90821492927058770002e-10, invln2 = 1.44269504088896338700e+00,
+                 p1 = 1.66666666666666019037e-01, p2 = -2.77777777770155933842e-03, p3 = 6.61375632143793436117e-05, p4 = -1.65339022054652515390e-06,
+                 p5 = 4.13813679705723846039e-08, twom1000 = 9.33263618503218878990e-302, inf = plf_bits_double(0x7ff0000000000000ull);
+    const uint64_t bits = plf_double_bits(x);
+    const uint32_t lx = (uint32_t)bits;
+    uint32_t hx = (uint32_t)(bits >> 32);
+    const int xsb = (int)(hx >> 31);
+    hx &= 0x7fffffffu;
+    if (hx >= 0x40862E42u) {                          // |x| >= 709.78
+        if (hx >= 0x7ff00000u) {
+            if (((hx & 0xfffffu) | lx) != 0) return x + x;   // NaN
+            return xsb == 0 ? x : 0.0;                       // exp(+-inf)
+        }
+        if (x > 7.09782712893383973096e+02) return inf;      // huge * huge
+        if (x < -7.45133219101941108420e+02) return 0.0;     // twom1000 * twom1000
+    }
+    int k = 0;
+    double hi = 0.0, lo = 0.0;
+    if (hx > 0x3fd62e42u) {                           // |x| > 0.5 ln2
+        if (hx < 0x3FF0A2B2u) {                       // and < 1.5 ln2
+            hi = x - (xsb == 0 ? ln2hi : -ln2hi);
+            lo = xsb == 0 ? ln2lo : -ln2lo;
+            k = 1 - xsb - xsb;
+        } else {
+            k = (int)(invln2 * x + (xsb == 0 ? 0.5 : -0.5));
+            const double t = (double)k;
+            hi = x - t * ln2hi;
+            lo = t * ln2lo;
+        }
+        x = hi - lo;
+    } else if (hx < 0x3e300000u) return 1.0 + x;      // |x| < 2^-28
+    const double t = x * x;
+    const double c = x - t * (p1 + t * (p2 + t * (p3 + t * (p4 + t * p5))));
+    if (k == 0) return 1.0 - ((x * c) / (c - 2.0) - x);
+    const double y = 1.0 - ((lo - (x * c) / (2.0 - c)) - hi);
+    if (k >= -1021) return plf_bits_double(plf_double_bits(y) + ((uint64_t)(int64_t)k << 52));
+    return plf_bits_double(plf_double_bits(y) + ((uint64_t)(int64_t)(k + 1000) << 52)) * twom1000;
+}
+
 // Thresholds of the cheap alignment pre-test of region_grow (lsd_kernels.hip): t1 <= tan(prec - delta), t2 >= tan(prec + delta), delta = 0.05 degrees.
 // The pre-test only sorts candidates into "surely aligned", "surely not" and "border" (decided by the reference's own test), so ANY t1 below and
 // t2 above those tangents is sound: single-precision tanf with a 1e-4 relative safety factor (its error is ~1e-7; the band is ~2.5e-3 wide) keeps

@@ -252,11 +252,13 @@ PLF_MATH void pose_edge_terms(const PoseEdge &e, const PoseEst &est, const PoseC
     }
 }
 
-// LinearSolverDense::solve: Eigen::LDLT<MatrixXd> of the 6x6 whose lower triangle is a (in place), then x = solve(b).  false = not positive, x untouched.
-PLF_MATH bool pose_ldlt_solve(double a[6][6], const double *b, double *x)
+// LinearSolverDense::solve: Eigen::LDLT<MatrixXd> of the N x N whose lower triangle is a (in place), then x = solve(b).  false = not positive, x untouched.
+// (N = 6 here, N = 7 for the Sim3 vertex of sim3opt_common.h: the same statements.)
+template <int N>
+PLF_MATH bool pose_ldlt_solve_n(double a[N][N], const double *b, double *x)
 {
-    const int n = 6;
-    int tr[6];
+    const int n = N;
+    int tr[N];
     bool positive = true;
     for (int k = 0; k < n; k++) {
         int p = k;
@@ -272,7 +274,7 @@ PLF_MATH bool pose_ldlt_solve(double a[6][6], const double *b, double *x)
             for (int i = k + 1; i < p; i++) { sw = a[i][k]; a[i][k] = a[p][i]; a[p][i] = sw; }
         }
         if (k > 0) {
-            double temp[6];
+            double temp[N];
             for (int j = 0; j < k; j++) temp[j] = a[j][j] * a[k][j];
             double s = a[k][0] * temp[0];
             for (int j = 1; j < k; j++) s = s + a[k][j] * temp[j];
@@ -289,7 +291,7 @@ PLF_MATH bool pose_ldlt_solve(double a[6][6], const double *b, double *x)
             for (int i = k + 1; i < n; i++) a[i][k] = a[i][k] / d;
     }
     if (!positive) return false;
-    double y[6];
+    double y[N];
     for (int i = 0; i < n; i++) y[i] = b[i];
     for (int k = 0; k < n; k++) { const double sw = y[k]; y[k] = y[tr[k]]; y[tr[k]] = sw; }
     for (int i = 1; i < n; i++) {
@@ -307,6 +309,8 @@ PLF_MATH bool pose_ldlt_solve(double a[6][6], const double *b, double *x)
     for (int i = 0; i < n; i++) x[i] = y[i];
     return true;
 }
+
+PLF_MATH bool pose_ldlt_solve(double a[6][6], const double *b, double *x) { return pose_ldlt_solve_n<6>(a, b, x); }
 
 PLF_MATH bool pose_isfinite(double v) { return fabs(v) <= 1.7976931348623157e308; }
 

@@ -189,6 +189,20 @@ class Sim3Solver:
         T[:3, 3] = s[9:12].cpu()
         return T, no_more, out.hit_inlier12[0, 0].bool().cpu(), int(out.hit_inliers[0, 0])
 
+    def optimize(self, inv_level_sigma2, th2=10.0):
+        """ComputeSim3's statements after a hit of iterate(): keep the hit's inliers among the matches, then OptimizeSim3 from the hit's transform.
+        Returns (nInliers, sim3 (8,) float64 qx qy qz qw tx ty tz s, Scw (4, 4) float32, matches (kp_stride,) int32 with the culled ones -1), all on
+        the host; the solver's own match row is left as it was."""
+        from .sim3opt import sim3_keep_inliers, sim3_optimize
+        if self._hit is None:
+            raise RuntimeError("Sim3Solver.optimize: no hit of iterate() to start from")
+        kfs, world_pos, point_bad, _, cam = self._a
+        match = self._match.clone()
+        sim3_keep_inliers(match, self._hit.hit_inlier12[:, 0].contiguous(), stream=self._stream)
+        out = sim3_optimize(kfs, self._kf1, self._kf2, match, self._hit.hit_sim3[:, 0].contiguous(), self._fix, world_pos, point_bad, inv_level_sigma2, cam,
+                            th2=th2, stream=self._stream)
+        return int(out.n_inliers[0]), out.sim3[0].cpu(), out.scw[0].reshape(4, 4).cpu(), match[0].cpu()
+
     def find(self):
         T, _, inl, n = self.iterate(int(self._rand3.shape[1]))
         return T, inl, n
