@@ -1695,6 +1695,109 @@ int plf_sim3_optimize(const plf_sim3_view *v, const plf_camera *cam, const plf_s
 int plf_sim3_keep_inliers(int32_t *match12, const uint8_t *inlier12, const int32_t *kf_n_of_job, int32_t n_jobs, int32_t kp_stride, int32_t device,
                           void *stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * Loop correction -- the Sim3 pose propagation and the map-point moves of LoopClosing::CorrectLoop (lib/libORB_SLAM2.so, so@0x67fb0), of the tail of
+ * Optimizer::OptimizeEssentialGraph (so@0xb2ad0) and of the tail of LoopClosing::RunGlobalBundleAdjustment (so@0x657c0), over the arrays the
+ * matchers, the frustum calls, plf_map_update_normal_depth, the culling calls and the local-map gather keep on the device.  Map points only: none
+ * of the three functions has a MapLine call in its call list.
+ * A Sim3 is 8 doubles, qx qy qz qw tx ty tz s: the layout of plf_sim3_optimize's sim3_out; the quaternion is never normalised (g2o::Sim3).
+ *
+ * READ FROM THE BINARY (CorrectLoop's inlined Eigen / g2o double arithmetic is compiled WITH fused operations; upstream's source has plain ones;
+ * fma(a, b, c) below is one rounding):
+ *   cross(l, r)      = (fma(l1, r2, -(l2 r1)), fma(l2, r0, -(l0 r2)), fma(l0, r1, -(l1 r0)))      so@0x698c6 .. 0x69912, 0x696a5 .. 0x696b7
+ *   q * v            : uv = cross(q.xyz, v); uv += uv; c = cross(q.xyz, uv); out_i = fma(q.w, uv_i, v_i) + c_i            so@0x69905 .. 0x6997e
+ *   Sim3::map(X)     = fma(s, (r * X)_i, t_i)                                              so@0x6994f, 0x6998e, 0x6999b; 0x699e0, 0x69a0b, 0x69a1c
+ *   Sim3::inverse()  = (conj(r), conj(r) * ((-1.0 / s) * t), 1.0 / s): one division each, plain products                    so@0x695ca .. 0x696f3
+ *   a * b            : r.x = fma(-az, by, fma(ay, bz, fma(aw, bx, ax bw))), y and z by rotating x -> y -> z -> x,
+ *                      r.w = fma(-az, bz, fma(-ay, by, fma(aw, bw, -(ax bx)))); t_i = fma(a.s, (a.r * b.t)_i, a.t_i); s = a.s b.s
+ *                      (so@0x68a7e .. 0x68bbd with a.s = 1.0; LoopClosing::ComputeSim3's gScm * gSmw at so@0x6bd80 .. 0x6bed0 has the same operations)
+ *   Quaterniond(M)   : Eigen's three-branch rule with trace = m00 + (m11 + m22), plain operations               so@0x68883 .. 0x68a02, 0x69f24 .. 0x69f9e
+ *   toRotationMatrix : tx = x + x ..., tyy = ty y, tyz = tz y, tzz = tz z, txy = ty x, txz = tz x; m00 = 1 - (tyy + tzz), m11 = 1 - fma(tx, x, tzz),
+ *                      m22 = 1 - fma(tx, x, tyy), m01 = fma(-tz, w, txy), m10 = fma(tz, w, txy), m02 = fma(ty, w, txz), m20 = fma(-ty, w, txz),
+ *                      m12 = fma(-tx, w, tyz), m21 = fma(tx, w, tyz)                                                       so@0x69bcb .. 0x69ca9
+ *   eigt *= 1. / s   : the quotient 1.0 / s of inverse() above, three plain products                                        so@0x69cbd .. 0x69cd9
+ *   the walk         : std::map order (so@0x69db2 _Rb_tree_increment); per row null (so@0x69854), isBad() (so@0x69860), mnCorrectedByKF ==
+ *                      mpCurrentKF->mnId (so@0x69877) skip; SetWorldPos (so@0x69a38); the two marks (so@0x69a4a, 0x69a59); UpdateNormalAndDepth
+ *                      (so@0x69a5e); after the row toCvSE3 (so@0x69ce9), SetPose (so@0x69cf8), UpdateConnections (so@0x69d04)
+ * Converter::toMatrix3d / toVector3d / toCvMat / toCvSE3 only widen float to double or round double to float.
+ * PARITY UNPINNED (behind the PLT, restated as elsewhere in the tree): cv::operator* of two 4x4 float matrices (so@0x68386: track_common.h's
+ * small-matrix path, every entry a float sum of four products from the left); KeyFrame::SetPose's Ow = -Rcw.t() * tcw (match_host.hip's transposed
+ * path: double products summed from the left, times -1.0, rounded); the float Rcw * P + tcw and Rwc * Xc + twc of the bundle-adjustment tail
+ * (sim3_common.h's sim3_transform / track_common.h's track_unproject form).
+ * The two tails agree with upstream in control flow.  OptimizeEssentialGraph: toRotationMatrix and t * (1. / s) inlined with the fusions above
+ * (so@0xb5ab6 .. 0xb5bd3), toCvSE3 (so@0xb5bde), SetPose (so@0xb5be9); per point isBad (so@0xb5e6d), GetReferenceKeyFrame (so@0xb5e8d), the two maps
+ * through the out-of-line Eigen _transformVector (so@0xbb7c0: the same operations as q * v above) and fma(s, r_i, t_i) (so@0xb5d8d .. 0xb5e11),
+ * SetWorldPos (so@0xb5e35), UpdateNormalAndDepth (so@0xb5e3d).  RunGlobalBundleAdjustment (so@0x657c0 .. 0x67fb0) has no fused operation and calls
+ * GetChilds, GetPose, GetPoseInverse, SetPose, isBad, GetReferenceKeyFrame, GetWorldPos, SetWorldPos; neither function's call list names a MapLine.
+ *
+ *  0. plf_loop_scw: mg2oScw = gScm * g2o::Sim3(Rmw, tmw, 1.0): scm is a sim3_out row of plf_sim3_optimize, matched_slot the matched keyframe.
+ *  1. plf_loop_sim3_pairs, for the K keyframe slots rank_kf in the caller's CorrectedSim3 iteration order (distinct slots; the order is an input):
+ *     Twc = [Rcw.t() | Ow] of slot cur_slot; for rank r with slot i != cur_slot: Tic = Tiw * Twc, corrected[r] = Sim3(Ric, tic, 1.0) * scw; for the
+ *     current keyframe corrected[r] = scw; for every rank noncorrected[r] = Sim3(Riw, tiw, 1.0).  scw NULL: only noncorrected is written (vScw of
+ *     keyframes outside NonCorrectedSim3).  A slot out of range gives rows of NaN.
+ *  2. plf_loop_correct_points: the point half of the second loop.  Row r of row_start / row_point is mvpMapPoints of rank r.  An entry is skipped when
+ *     it is < 0 or >= n_points, when point_bad, or when corrected_by == cur_kf_id on entry.  Every other point is owned by the LOWEST rank whose row
+ *     holds it -- the keyframe that meets it first in the reference's walk -- and moved once:
+ *     world_pos = float(corrected[o].inverse().map(noncorrected[o].map(double(world_pos)))), corrected_by = cur_kf_id, corrected_ref =
+ *     kf_id[rank_kf[o]]; owner_rank[p] = o, -1 for every point left alone.  A rank whose slot is out of range owns nothing.
+ *  3. plf_loop_new_poses: per rank toCvSE3(R, t * (1. / s)) of corrected[r] and what SetPose derives from it: tcw_new = [Rcw | tcw], ow_new = Ow.
+ *     plf_loop_commit_poses: kf_tcw[rank_kf[r]] = tcw_new[r], kf_ow[rank_kf[r]] = ow_new[r] (slots out of range skipped).
+ *  4. plf_loop_normal_depth: UpdateNormalAndDepth as the walk interleaves it: the rule of plf_map_update_normal_depth over the points with
+ *     owner_rank >= 0, where the centre of keyframe k is ow_new[kf_rank[k]] when 0 <= kf_rank[k] < owner_rank[p] (its SetPose ran before the point
+ *     was met) and kf_ow[k] otherwise; the reference keyframe's centre follows the same test.  Call it between 3's two halves.
+ *  5. plf_loop_correct_points_by_ref, the essential-graph tail: per point that is not bad, slot = corrected_by == cur_kf_id ?
+ *     id_to_slot[corrected_ref] : ref_kf; world_pos = float(swc[slot].map(scw[slot].map(double(world_pos)))); a slot (or id) out of range leaves the
+ *     point alone.  moved[p] (optional) = 1 / 0.  The pose half is plf_loop_new_poses over all keyframes; plf_map_update_normal_depth follows.
+ *  6. plf_gba_propagate_poses: the breadth-first walk of the spanning tree from the origins, in the only form its values allow -- each keyframe's
+ *     mTcwGBA depends on its parent alone: for an unflagged keyframe below an origin, tcw_gba = (Tcw_child * Twc_parent) * tcw_gba_parent along the
+ *     chain up to the first flagged keyframe or origin (old poses throughout); then for every keyframe reachable from an origin tcw_bef = kf_tcw,
+ *     kf_tcw = tcw_gba, kf_ow = its centre, and kf_flag = 1 except for an origin.  Keyframes not reachable from an origin stay untouched.
+ *     plf_gba_correct_points: per point that is not bad: point_flag ? world_pos = pos_gba : (kf_flag[ref_kf] ? world_pos = Rwc * (Rcw_bef * P +
+ *     tcw_bef) + twc : untouched).
+ * Stateless; every array is DEVICE memory (the structs are host); asynchronous on `stream`; nothing is read back; 4 and 6 take scratch from the
+ * stream-ordered pool.  PLF_E_BADARG before any device work: a NULL array that has elements, negative sizes, cur_slot / matched_slot outside [0, n_kf).
+ * Slots, ids and indices out of range, NaN / Inf values fault nowhere.  One point (one keyframe) per lane, the rows of call 2 one workgroup each;
+ * csrc/loopfix_kernels.hip has the schedule.
+ * ---------------------------------------------------------------------------------------------- */
+typedef struct {
+    int32_t K;                                            /* ranks: entries of CorrectedSim3 */
+    const int32_t *rank_kf;                               /* K: keyframe slot of each rank, distinct */
+    const int32_t *row_start, *row_point;                 /* K + 1 / total: mvpMapPoints of each rank, as plf_cull_view's rows */
+    int32_t n_points;
+    const uint8_t *point_bad;                             /* n_points */
+    int32_t n_kf;
+    const int64_t *kf_id;                                 /* n_kf: mnId by slot */
+} plf_loop_view;
+typedef struct {
+    int32_t n_kf;
+    const int32_t *parent;                                /* n_kf: slot of mpParent, < 0: none */
+    const int32_t *origins;                               /* n_origins: slots of mvpKeyFrameOrigins */
+    int32_t n_origins;
+    uint8_t *kf_flag;                                     /* n_kf, in / out: mnBAGlobalForKF == nLoopKF */
+    plf_pose34 *tcw_gba;                                  /* n_kf, in / out: mTcwGBA */
+    plf_pose34 *kf_tcw;                                   /* n_kf, in / out */
+    float *kf_ow;                                         /* n_kf x 3, in / out */
+    plf_pose34 *tcw_bef;                                  /* n_kf, out: mTcwBefGBA */
+} plf_gba_view;
+int plf_loop_scw(const double *scm, const plf_pose34 *kf_tcw, int32_t n_kf, int32_t matched_slot, double *scw_out, int32_t device, void *stream);
+int plf_loop_sim3_pairs(const plf_pose34 *kf_tcw, const float *kf_ow, int32_t n_kf, const int32_t *rank_kf, int32_t K, int32_t cur_slot,
+                        const double *scw, double *corrected, double *noncorrected, int32_t device, void *stream);
+int plf_loop_correct_points(const plf_loop_view *v, const double *corrected, const double *noncorrected, int64_t cur_kf_id, float *world_pos,
+                            int64_t *corrected_by, int64_t *corrected_ref, int32_t *owner_rank, int32_t device, void *stream);
+int plf_loop_new_poses(const double *corrected, int32_t K, plf_pose34 *tcw_new, float *ow_new, int32_t device, void *stream);
+int plf_loop_commit_poses(const int32_t *rank_kf, int32_t K, const plf_pose34 *tcw_new, const float *ow_new, plf_pose34 *kf_tcw, float *kf_ow,
+                          int32_t n_kf, int32_t device, void *stream);
+int plf_loop_normal_depth(const plf_map_geom_view *v, const int32_t *kf_rank, const float *ow_new, int32_t K, const int32_t *owner_rank,
+                          const float *world_pos, float *normal, float *min_distance, float *max_distance, int32_t map_rows, int32_t *n_obs_used,
+                          int32_t device, void *stream);
+int plf_loop_correct_points_by_ref(int32_t n_points, const uint8_t *point_bad, const int32_t *ref_kf, const int64_t *corrected_by,
+                                   const int64_t *corrected_ref, int64_t cur_kf_id, const int32_t *id_to_slot, int64_t n_ids, const double *scw,
+                                   const double *swc, int32_t n_kf, float *world_pos, uint8_t *moved, int32_t device, void *stream);
+int plf_gba_propagate_poses(const plf_gba_view *v, int32_t device, void *stream);
+int plf_gba_correct_points(int32_t n_points, const uint8_t *point_bad, const uint8_t *point_flag, const float *pos_gba, const int32_t *ref_kf,
+                           const uint8_t *kf_flag, const plf_pose34 *tcw_bef, const plf_pose34 *kf_tcw, const float *kf_ow, int32_t n_kf,
+                           float *world_pos, int32_t device, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

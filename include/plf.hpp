@@ -831,6 +831,71 @@ public:
     DeviceArray<uint8_t> no_more, fix_scale, hit_inlier12;
 };
 
+// LoopClosing::CorrectLoop's Sim3 pose propagation and map-point moves over the resident map (plf.h, "Loop correction"): the RAII form over the per-call
+// arrays of the four calls -- K ranks (the entries of CorrectedSim3 in the caller's iteration order), n_points points, n_kf keyframe slots.  Everything a
+// method takes is DEVICE memory; every method only enqueues on `stream`.  After Run(): corrected[r] is the Scw plf_match_fuse_sim3 takes for rank r
+// (Converter::toCvMat of it, a host argument), owner_rank[p] the rank that moved point p (-1: left alone), n_obs_used what its UpdateNormalAndDepth counted.
+// The two tails (OptimizeEssentialGraph, RunGlobalBundleAdjustment) are the static members: stateless calls.
+class LoopCorrection {
+public:
+    LoopCorrection(int K_, int n_points_, int n_kf_, int device = 0)
+        : K(K_), n_points(n_points_), n_kf(n_kf_), device_(device), corrected((size_t)std::max(K_, 1) * 8, device), noncorrected((size_t)std::max(K_, 1) * 8, device),
+          scw(8, device), tcw_new(std::max(K_, 1), device), ow_new((size_t)std::max(K_, 1) * 3, device), owner_rank(std::max(n_points_, 1), device),
+          n_obs_used(std::max(n_points_, 1), device), kf_rank(std::max(n_kf_, 1), device) {}
+    // mg2oScw = gScm * Sim3(Rmw, tmw, 1.0) from a sim3_out row of plf_sim3_optimize, kept in `scw`
+    void Scw(const double *scm_dev, const plf_pose34 *kf_tcw_dev, int matched_slot, void *stream = nullptr)
+    {
+        check(plf_loop_scw(scm_dev, kf_tcw_dev, n_kf, matched_slot, scw.get(), device_, stream), "ComputeSim3: mg2oScw");
+    }
+    // the two loops of CorrectLoop.  rank_kf_host: the host copy of rows.rank_kf (the rank of each slot is built from it and uploaded).
+    void Run(const plf_loop_view &rows, int cur_slot, int64_t cur_kf_id, plf_pose34 *kf_tcw_dev, float *kf_ow_dev, const plf_map_geom_view &observations,
+             float *world_pos_dev, int64_t *corrected_by_dev, int64_t *corrected_ref_dev, float *normal_dev, float *min_distance_dev, float *max_distance_dev,
+             const std::vector<int32_t> &rank_kf_host, void *stream = nullptr)
+    {
+        std::vector<int32_t> rank(std::max(n_kf, 1), -1);
+        for (int r = 0; r < K && r < (int)rank_kf_host.size(); r++)
+            if (rank_kf_host[r] >= 0 && rank_kf_host[r] < n_kf) rank[rank_kf_host[r]] = r;
+        kf_rank.upload(rank.data(), rank.size());             // (synchronous: `rank` is a local)
+        check(plf_loop_sim3_pairs(kf_tcw_dev, kf_ow_dev, n_kf, rows.rank_kf, K, cur_slot, scw.get(), corrected.get(), noncorrected.get(), device_, stream),
+              "CorrectLoop: CorrectedSim3");
+        check(plf_loop_correct_points(&rows, corrected.get(), noncorrected.get(), cur_kf_id, world_pos_dev, corrected_by_dev, corrected_ref_dev, owner_rank.get(), device_,
+                                      stream), "CorrectLoop: map points");
+        check(plf_loop_new_poses(corrected.get(), K, tcw_new.get(), ow_new.get(), device_, stream), "CorrectLoop: poses");
+        if (n_points > 0)
+            check(plf_loop_normal_depth(&observations, kf_rank.get(), ow_new.get(), K, owner_rank.get(), world_pos_dev, normal_dev, min_distance_dev, max_distance_dev,
+                                        n_points, n_obs_used.get(), device_, stream), "CorrectLoop: UpdateNormalAndDepth");
+        check(plf_loop_commit_poses(rows.rank_kf, K, tcw_new.get(), ow_new.get(), kf_tcw_dev, kf_ow_dev, n_kf, device_, stream), "CorrectLoop: SetPose");
+    }
+    // the end of Optimizer::OptimizeEssentialGraph: SetPose of every keyframe from corrected_siw_dev (n_kf x 8), then the point loop.  The UpdateNormalAndDepth()
+    // of that loop is NOT in here: the caller runs plf_map_update_normal_depth (MapPoint::UpdateNormalAndDepth) next, with the new centres.
+    static void EssentialGraphTail(const double *corrected_siw_dev, const double *vScw_dev, const double *vCorrectedSwc_dev, int n_kf, plf_pose34 *kf_tcw_dev,
+                                   float *kf_ow_dev, plf_pose34 *tcw_new_dev, float *ow_new_dev, const int32_t *every_slot_dev, int n_points, const uint8_t *point_bad_dev,
+                                   const int32_t *ref_kf_dev, const int64_t *corrected_by_dev, const int64_t *corrected_ref_dev, int64_t cur_kf_id,
+                                   const int32_t *id_to_slot_dev, int64_t n_ids, float *world_pos_dev, uint8_t *moved_dev = nullptr, int device = 0, void *stream = nullptr)
+    {
+        check(plf_loop_new_poses(corrected_siw_dev, n_kf, tcw_new_dev, ow_new_dev, device, stream), "OptimizeEssentialGraph: poses");
+        check(plf_loop_commit_poses(every_slot_dev, n_kf, tcw_new_dev, ow_new_dev, kf_tcw_dev, kf_ow_dev, n_kf, device, stream), "OptimizeEssentialGraph: SetPose");
+        check(plf_loop_correct_points_by_ref(n_points, point_bad_dev, ref_kf_dev, corrected_by_dev, corrected_ref_dev, cur_kf_id, id_to_slot_dev, n_ids, vScw_dev,
+                                             vCorrectedSwc_dev, n_kf, world_pos_dev, moved_dev, device, stream), "OptimizeEssentialGraph: map points");
+    }
+    // the end of LoopClosing::RunGlobalBundleAdjustment
+    static void GlobalBundleAdjustmentTail(const plf_gba_view &tree, int n_points, const uint8_t *point_bad_dev, const uint8_t *point_flag_dev, const float *pos_gba_dev,
+                                           const int32_t *ref_kf_dev, float *world_pos_dev, int device = 0, void *stream = nullptr)
+    {
+        check(plf_gba_propagate_poses(&tree, device, stream), "RunGlobalBundleAdjustment: poses");
+        check(plf_gba_correct_points(n_points, point_bad_dev, point_flag_dev, pos_gba_dev, ref_kf_dev, tree.kf_flag, tree.tcw_bef, tree.kf_tcw, tree.kf_ow, tree.n_kf,
+                                     world_pos_dev, device, stream), "RunGlobalBundleAdjustment: map points");
+    }
+    const int K, n_points, n_kf;
+private:
+    int device_;
+public:
+    DeviceArray<double> corrected, noncorrected, scw;
+    DeviceArray<plf_pose34> tcw_new;
+    DeviceArray<float> ow_new;
+    DeviceArray<int32_t> owner_rank, n_obs_used, kf_rank;
+};
+
 }  // namespace plf
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -2376,6 +2441,136 @@ private:
     std::unique_ptr<plf::Sim3Batch> batch_;
     std::vector<Sim3Solver *> own_;
     Held held_;
+};
+
+// The two loops of LoopClosing::CorrectLoop (so@0x67fb0) that follow the construction of mvpCurrentConnectedKFs, over the reference's own KeyFrame / MapPoint
+// / g2o::Sim3 and the CALLER'S OWN std::map<KeyFrame*, g2o::Sim3> (KeyFrameAndPose): the maps are filled here, and their iteration order -- the pointer order
+// the caller's allocator produced -- is the rank order of the walk, as in the reference.  Reads GetPose(), GetCameraCenter(), mnId, GetMapPointMatches(),
+// isBad(), GetWorldPos(), mnCorrectedByKF, GetObservations(), GetReferenceKeyFrame(), mvKeysUn, mvScaleFactors, mnScaleLevels; writes SetWorldPos(),
+// mnCorrectedByKF, mnCorrectedReference and SetPose(), and returns per moved point what UpdateNormalAndDepth() leaves (mNormalVector / mfMinDistance /
+// mfMaxDistance are protected in the reference: the forwarder inside MapPoint.cc assigns them).  UpdateConnections() per keyframe stays
+// with the caller.  Uploads and waits: for one loop closure of a map that lives in host objects; a resident map calls plf::LoopCorrection.
+struct LoopClosing {
+    template <class MapPointT> struct Corrected {
+        std::vector<MapPointT *> points;            // every point met in the rows, in order of first occurrence
+        std::vector<int32_t> owner_rank, n;         // the rank that moved it (-1: left alone); observations counted (-1: leave the three members alone)
+        std::vector<float> normal, minDistance, maxDistance;
+    };
+    template <class KeyFrameT, class MapPointT, class Sim3T, class KeyFrameAndPoseT>
+    static Corrected<MapPointT> CorrectLoop(KeyFrameT *mpCurrentKF, const std::vector<KeyFrameT *> &mvpCurrentConnectedKFs, const Sim3T &mg2oScw,
+                                            KeyFrameAndPoseT &CorrectedSim3, KeyFrameAndPoseT &NonCorrectedSim3, int device = 0)
+    {
+        Corrected<MapPointT> out;
+        for (KeyFrameT *pKFi : mvpCurrentConnectedKFs) { CorrectedSim3[pKFi]; NonCorrectedSim3[pKFi]; }
+        CorrectedSim3[mpCurrentKF]; NonCorrectedSim3[mpCurrentKF];
+        std::vector<KeyFrameT *> kfs;               // slots: the K ranks first, in the map's order, then every other keyframe that observes a point
+        std::vector<float> tcw, ow, scale;
+        std::vector<int64_t> kf_id;
+        detail::KeyFrameSlots seen;
+        auto slot_of = [&](KeyFrameT *pKF) {
+            return seen(pKF, [&](KeyFrameT *first) {
+                kfs.push_back(first);
+                const cv::Mat T = first->GetPose(), C = first->GetCameraCenter();
+                for (int r = 0; r < 3; r++) for (int c = 0; c < 4; c++) tcw.push_back(T.template at<float>(r, c));
+                for (int k = 0; k < 3; k++) ow.push_back(C.template at<float>(k));
+                kf_id.push_back((int64_t)first->mnId);
+            });
+        };
+        std::vector<int32_t> rank_kf;
+        for (auto &e : CorrectedSim3) rank_kf.push_back(slot_of(e.first));
+        const int K = (int)rank_kf.size();
+        std::unordered_map<MapPointT *, int32_t> ids;
+        std::vector<int32_t> row_start(1, 0), row_point, obs_start(1, 0), obs_kf, ref, level;
+        std::vector<uint8_t> bad;
+        std::vector<float> pos;
+        std::vector<int64_t> by;
+        for (auto &e : CorrectedSim3) {
+            for (MapPointT *pMP : e.first->GetMapPointMatches()) {
+                if (!pMP) { row_point.push_back(-1); continue; }
+                auto at = ids.emplace(pMP, (int32_t)ids.size());
+                row_point.push_back(at.first->second);
+                if (!at.second) continue;
+                out.points.push_back(pMP);
+                const cv::Mat X = pMP->GetWorldPos();
+                for (int k = 0; k < 3; k++) pos.push_back(X.template at<float>(k));
+                bad.push_back(pMP->isBad() ? 1 : 0);
+                by.push_back((int64_t)pMP->mnCorrectedByKF);
+                const auto observations = pMP->GetObservations();
+                for (const auto &ob : observations) obs_kf.push_back(slot_of(ob.first));
+                obs_start.push_back((int32_t)obs_kf.size());
+                KeyFrameT *pRefKF = pMP->GetReferenceKeyFrame();
+                int32_t r = -1, l = 0;
+                if (pRefKF && !observations.empty()) {
+                    r = slot_of(pRefKF);
+                    const auto it = observations.find(pRefKF);
+                    const size_t idx = it == observations.end() ? 0 : it->second;
+                    l = idx < pRefKF->mvKeysUn.size() ? pRefKF->mvKeysUn[idx].octave : 0;
+                    if (scale.empty()) scale.assign(pRefKF->mvScaleFactors.begin(), pRefKF->mvScaleFactors.begin() + pRefKF->mnScaleLevels);
+                }
+                ref.push_back(r); level.push_back(l);
+            }
+            row_start.push_back((int32_t)row_point.size());
+        }
+        const int P = (int)out.points.size(), S = (int)kfs.size();
+        out.owner_rank.assign(P, -1); out.n.assign(P, -1);
+        out.normal.assign((size_t)P * 3, 0.0f); out.minDistance.assign(P, 0.0f); out.maxDistance.assign(P, 0.0f);
+        if (scale.empty()) scale.assign(1, 1.0f);
+        if (row_point.empty()) row_point.push_back(-1);
+        if (obs_kf.empty()) obs_kf.push_back(-1);
+        const std::vector<double> scw8 = {mg2oScw.rotation().x(), mg2oScw.rotation().y(), mg2oScw.rotation().z(), mg2oScw.rotation().w(), mg2oScw.translation()[0],
+                                          mg2oScw.translation()[1], mg2oScw.translation()[2], mg2oScw.scale()};
+        plf::LoopCorrection lc(K, P, S, device);
+        lc.scw.upload(scw8.data(), 8);
+        plf::DeviceArray<plf_pose34> dtcw(tcw.size() / 12, device);
+        dtcw.upload(tcw.data(), tcw.size() / 12);
+        plf::DeviceArray<float> dow(ow, device), dscale(scale, device), dpos(std::max(P, 1) * 3, device), dnormal(std::max(P, 1) * 3, device), dmin(std::max(P, 1), device),
+            dmax(std::max(P, 1), device);
+        plf::DeviceArray<int32_t> drank(rank_kf, device), drs(row_start, device), drp(row_point, device), dos(obs_start, device), dok(obs_kf, device),
+            dref(std::max(P, 1), device), dlevel(std::max(P, 1), device);
+        plf::DeviceArray<uint8_t> dbad(std::max(P, 1), device);
+        plf::DeviceArray<int64_t> did(kf_id, device), dby(std::max(P, 1), device), dcref(std::max(P, 1), device);
+        dnormal.fill(0); dmin.fill(0); dmax.fill(0); dcref.fill(0);
+        if (P) { dpos.upload(pos.data(), pos.size()); dref.upload(ref.data(), P); dlevel.upload(level.data(), P); dbad.upload(bad.data(), P); dby.upload(by.data(), P); }
+        const plf_loop_view rows = {K, drank.get(), drs.get(), drp.get(), P, dbad.get(), S, did.get()};
+        plf_map_geom_view g = {};
+        g.n_points = P; g.obs_start = dos.get(); g.obs_kf = dok.get(); g.kf_ow = dow.get(); g.n_kf = S; g.ref_kf = dref.get(); g.ref_level = dlevel.get();
+        g.scale_factors = dscale.get(); g.nlevels = (int32_t)scale.size(); g.point_bad = dbad.get(); g.pos_floats = 3;
+        lc.Run(rows, seen(mpCurrentKF, [](KeyFrameT *) {}), (int64_t)mpCurrentKF->mnId, dtcw.get(), dow.get(), g, dpos.get(), dby.get(), dcref.get(), dnormal.get(),
+               dmin.get(), dmax.get(), rank_kf);
+        // ---- back into the caller's objects (a NULL-stream download waits for the device first)
+        const std::vector<double> cor = lc.corrected.download(), non = lc.noncorrected.download();
+        auto put = [](Sim3T &S3, const double *o) {
+            S3.rotation().x() = o[0]; S3.rotation().y() = o[1]; S3.rotation().z() = o[2]; S3.rotation().w() = o[3];
+            S3.translation()[0] = o[4]; S3.translation()[1] = o[5]; S3.translation()[2] = o[6]; S3.scale() = o[7];
+        };
+        int r = 0;
+        for (auto &e : CorrectedSim3) { put(e.second, &cor[8 * (size_t)r]); put(NonCorrectedSim3[e.first], &non[8 * (size_t)r]); r++; }
+        if (P) {
+            const std::vector<float> npos = dpos.download();
+            const std::vector<int64_t> nby = dby.download(), ncref = dcref.download();
+            out.owner_rank = lc.owner_rank.download(); out.n = lc.n_obs_used.download();
+            out.owner_rank.resize(P); out.n.resize(P);
+            out.normal = dnormal.download(); out.minDistance = dmin.download(); out.maxDistance = dmax.download();
+            for (int p = 0; p < P; p++) {
+                if (out.owner_rank[p] < 0) continue;
+                cv::Mat X(3, 1, CV_32F);
+                for (int k = 0; k < 3; k++) X.at<float>(k, 0) = npos[(size_t)p * 3 + k];
+                out.points[p]->SetWorldPos(X);
+                out.points[p]->mnCorrectedByKF = (decltype(out.points[p]->mnCorrectedByKF))nby[p];
+                out.points[p]->mnCorrectedReference = (decltype(out.points[p]->mnCorrectedReference))ncref[p];
+            }
+        }
+        const std::vector<plf_pose34> tn = lc.tcw_new.download();
+        r = 0;
+        for (auto &e : CorrectedSim3) {
+            cv::Mat T(4, 4, CV_32F);
+            for (int i = 0; i < 3; i++) for (int c = 0; c < 4; c++) T.at<float>(i, c) = tn[r].Tcw[4 * i + c];
+            T.at<float>(3, 0) = 0.0f; T.at<float>(3, 1) = 0.0f; T.at<float>(3, 2) = 0.0f; T.at<float>(3, 3) = 1.0f;
+            e.first->SetPose(T);
+            r++;
+        }
+        return out;
+    }
 };
 }  // namespace ORB_SLAM2_PLF
 #endif

@@ -26,3 +26,5 @@ from . import sim3  # noqa: F401
 from .sim3 import sim3_pairs, sim3_iterate, Sim3Solver, Sim3KeyFrames  # noqa: F401
 from . import sim3opt  # noqa: F401
 from .sim3opt import sim3_optimize, sim3_keep_inliers  # noqa: F401
+from . import loopfix  # noqa: F401
+from .loopfix import loop_scw, loop_sim3_pairs, loop_correct, essential_graph_correct, gba_correct  # noqa: F401

@@ -443,3 +443,36 @@ def sim3opt_prototypes(l, prefix="plf_sim3"):
     getattr(l, prefix + "_optimize").argtypes = [C.POINTER(Sim3View), C.POINTER(Camera), C.POINTER(Sim3OptJobs), P, P, P, P, P] + (tail or [P])
     getattr(l, prefix + "_keep_inliers").argtypes = [P, P, P, I, I] + tail
     return l
+
+
+# ---- loop correction (include/plf.h, "Loop correction")
+class LoopView(C.Structure):
+    _fields_ = [("K", C.c_int32), ("rank_kf", C.c_void_p), ("row_start", C.c_void_p), ("row_point", C.c_void_p), ("n_points", C.c_int32),
+                ("point_bad", C.c_void_p), ("n_kf", C.c_int32), ("kf_id", C.c_void_p)]
+
+
+class GbaView(C.Structure):
+    _fields_ = [("n_kf", C.c_int32), ("parent", C.c_void_p), ("origins", C.c_void_p), ("n_origins", C.c_int32), ("kf_flag", C.c_void_p),
+                ("tcw_gba", C.c_void_p), ("kf_tcw", C.c_void_p), ("kf_ow", C.c_void_p), ("tcw_bef", C.c_void_p)]
+
+
+def loopfix_prototypes(l, prefix="plf"):
+    """the device calls; prefix="loopfix_cpu": the host loops of tools/loopfix_cpu.cpp, the same signatures without device and stream"""
+    P, I, Q = C.c_void_p, C.c_int32, C.c_int64
+    dev = prefix == "plf"
+    tail = [I, P] if dev else []
+    lp, gb = (prefix + "_loop_", prefix + "_gba_") if dev else (prefix + "_", prefix + "_gba_")
+    getattr(l, lp + "scw").argtypes = [P, P, I, I, P] + tail
+    getattr(l, lp + "sim3_pairs").argtypes = [P, P, I, P, I, I, P, P, P] + tail
+    getattr(l, lp + "correct_points").argtypes = [C.POINTER(LoopView), P, P, Q, P, P, P, P] + tail
+    getattr(l, lp + "new_poses").argtypes = [P, I, P, P] + tail
+    getattr(l, lp + "commit_poses").argtypes = [P, I, P, P, P, P, I] + tail
+    getattr(l, lp + "normal_depth").argtypes = [C.POINTER(MapGeomView), P, P, I, P, P, P, P, P, I, P] + tail
+    getattr(l, lp + "correct_points_by_ref").argtypes = [I, P, P, P, P, Q, P, Q, P, P, I, P, P] + tail
+    getattr(l, gb + "propagate_poses").argtypes = [C.POINTER(GbaView)] + tail
+    getattr(l, gb + "correct_points").argtypes = [I, P, P, P, P, P, P, P, P, I, P] + tail
+    if not dev:   # the loops as the reference writes them (tools/loopfix_cpu.cpp)
+        l.loopfix_cpu_correct_loop.argtypes = [C.POINTER(LoopView), C.POINTER(MapGeomView), P, P, Q, P, P, P, P, P, P, P, P, P, P]
+        l.loopfix_cpu_gba_children.argtypes = [C.POINTER(GbaView), P, P]
+        l.loopfix_cpu_gba_queue.argtypes = [C.POINTER(GbaView), P, P]
+    return l

@@ -58,6 +58,11 @@ struct MapGeomArgs {
     int64_t map_rows;
     int32_t *n_obs_used;
     MapBins bins;
+    // staged centres (plf_loop_normal_depth; all NULL / 0 for plf_map_update_normal_depth): only points with owner_rank >= 0 are updated, and the centre of
+    // keyframe k is ow_new[kf_rank[k]] when 0 <= kf_rank[k] < owner_rank[point], kf_ow[k] otherwise
+    const float *ow_new;
+    const int32_t *kf_rank, *owner_rank;
+    int32_t n_rank;
 };
 
 __global__ void k_mapgeom_bin(MapGeomArgs a);

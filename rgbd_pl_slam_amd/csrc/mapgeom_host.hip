@@ -4,8 +4,9 @@
 #include "plf_common.h"
 #include "map_common.h"
 
-extern "C" int plf_map_update_normal_depth(const plf_map_geom_view *v, const float *world_pos, float *normal, float *min_distance, float *max_distance,
-                                           int32_t map_rows, int32_t *n_obs_used, int32_t device, void *stream)
+// the checks and launches both entry points share; `staged` carries the four staged-centre fields of MapGeomArgs (all NULL / 0: none)
+static int mapgeom_run(const plf_map_geom_view *v, const float *world_pos, float *normal, float *min_distance, float *max_distance, int32_t map_rows,
+                       int32_t *n_obs_used, const MapGeomArgs &staged, int32_t device, void *stream)
 {
     if (!v || !world_pos || !normal || !n_obs_used || !v->obs_start || !v->obs_kf || !v->kf_ow || !v->ref_kf) return PLF_E_BADARG;
     if (v->n_points < 0 || v->n_kf < 0 || map_rows < 0) return PLF_E_BADARG;
@@ -25,6 +26,7 @@ extern "C" int plf_map_update_normal_depth(const plf_map_geom_view *v, const flo
     MapGeomArgs a;
     a.v = *v; a.world_pos = world_pos; a.normal = normal; a.min_distance = min_distance; a.max_distance = max_distance; a.map_rows = map_rows;
     a.n_obs_used = n_obs_used; a.bins = map_bins_at(scratch.p, n);
+    a.ow_new = staged.ow_new; a.kf_rank = staged.kf_rank; a.owner_rank = staged.owner_rank; a.n_rank = staged.n_rank;
     int st = PLF_OK;
     if (hipMemsetAsync(a.bins.count, 0, 4 * sizeof(int32_t), s) != hipSuccess) st = PLF_E_HIP;
     if (st == PLF_OK) {
@@ -35,4 +37,23 @@ extern "C" int plf_map_update_normal_depth(const plf_map_geom_view *v, const flo
         if (hipGetLastError() != hipSuccess) st = PLF_E_HIP;
     }
     return plf_scratch_release(scratch, s, st);
+}
+
+extern "C" int plf_map_update_normal_depth(const plf_map_geom_view *v, const float *world_pos, float *normal, float *min_distance, float *max_distance,
+                                           int32_t map_rows, int32_t *n_obs_used, int32_t device, void *stream)
+{
+    MapGeomArgs none;
+    none.ow_new = nullptr; none.kf_rank = nullptr; none.owner_rank = nullptr; none.n_rank = 0;
+    return mapgeom_run(v, world_pos, normal, min_distance, max_distance, map_rows, n_obs_used, none, device, stream);
+}
+
+// UpdateNormalAndDepth as LoopClosing::CorrectLoop interleaves it with SetPose (include/plf.h, "Loop correction", call 4)
+extern "C" int plf_loop_normal_depth(const plf_map_geom_view *v, const int32_t *kf_rank, const float *ow_new, int32_t K, const int32_t *owner_rank,
+                                     const float *world_pos, float *normal, float *min_distance, float *max_distance, int32_t map_rows,
+                                     int32_t *n_obs_used, int32_t device, void *stream)
+{
+    if (!kf_rank || !owner_rank || K < 0 || (K > 0 && !ow_new)) return PLF_E_BADARG;
+    MapGeomArgs staged;
+    staged.ow_new = ow_new; staged.kf_rank = kf_rank; staged.owner_rank = owner_rank; staged.n_rank = K;
+    return mapgeom_run(v, world_pos, normal, min_distance, max_distance, map_rows, n_obs_used, staged, device, stream);
 }

@@ -8,6 +8,8 @@
 // The float sum over a point's observations is ONE dependent chain in CSR order: every schedule below computes the terms in parallel (lanes) and
 // then adds them in order on one lane's worth of registers, so all three write the same bits.
 // A binning pre-pass (k_mapgeom_bin) sorts the points into three index lists by observation count, as map_kernels.hip does.
+// plf_loop_normal_depth ("Loop correction") runs the same kernels with the staged-centre fields of MapGeomArgs set: the points the correction did not
+// move are left alone by the pre-pass, and a centre is loaded through geom_ow(); with the fields NULL nothing else differs.
 #include "plf_common.h"
 #include "map_common.h"
 
@@ -27,13 +29,22 @@ __device__ __forceinline__ double geom_norm(float x, float y, float z)
     s += (double)x * (double)x; s += (double)y * (double)y; s += (double)z * (double)z;
     return sqrt(s);
 }
+// the camera centre of keyframe kf as point pt sees it: the staged one where the loop correction's walk had already set that keyframe's pose
+__device__ __forceinline__ const float *geom_ow(const MapGeomArgs &a, int kf, int pt)
+{
+    if (a.owner_rank) {
+        const int r = a.kf_rank[kf];
+        if (r >= 0 && r < a.n_rank && r < a.owner_rank[pt]) return a.ow_new + 3 * (int64_t)r;
+    }
+    return a.v.kf_ow + 3 * (int64_t)kf;
+}
 // normali / cv::norm(normali) as cv::scaleAdd sees it [UPSTREAM]: alpha = (float)(1.0 / d), then one float multiply per element.  false: the
 // observation's keyframe is outside the table, it is skipped and not counted.
-__device__ __forceinline__ bool geom_term(const MapGeomArgs &a, int64_t o, float p0, float p1, float p2, float &t0, float &t1, float &t2)
+__device__ __forceinline__ bool geom_term(const MapGeomArgs &a, int pt, int64_t o, float p0, float p1, float p2, float &t0, float &t1, float &t2)
 {
     const int kf = a.v.obs_kf[o];
     if (kf < 0 || kf >= a.v.n_kf) return false;
-    const float *ow = a.v.kf_ow + 3 * (int64_t)kf;
+    const float *ow = geom_ow(a, kf, pt);
     const float d0 = p0 - ow[0], d1 = p1 - ow[1], d2 = p2 - ow[2];
     const float alpha = (float)(1.0 / geom_norm(d0, d1, d2));
     t0 = d0 * alpha; t1 = d1 * alpha; t2 = d2 * alpha;
@@ -47,7 +58,7 @@ __device__ __forceinline__ void geom_finish(const MapGeomArgs &a, int pt, int64_
     if (n == 0) { a.n_obs_used[pt] = -1; return; }
     if (a.max_distance) {
         const int ref = a.v.ref_kf[pt];
-        const float *ow = a.v.kf_ow + 3 * (int64_t)ref;
+        const float *ow = geom_ow(a, ref, pt);
         const float dist = (float)geom_norm(p0 - ow[0], p1 - ow[1], p2 - ow[2]);
         int level;
         if (a.v.ref_level) level = a.v.ref_level[pt];
@@ -76,7 +87,8 @@ __global__ void __launch_bounds__(256) k_mapgeom_bin(MapGeomArgs a)
             const int n = a.v.obs_start[p + 1] - a.v.obs_start[p];
             const int64_t row = geom_row(a, (int)p);
             const int ref = a.v.ref_kf[p];
-            const bool skip = n <= 0 || (a.v.point_bad && a.v.point_bad[p]) || ref < 0 || ref >= a.v.n_kf || row < 0 || row >= a.map_rows;
+            const bool skip = n <= 0 || (a.v.point_bad && a.v.point_bad[p]) || ref < 0 || ref >= a.v.n_kf || row < 0 || row >= a.map_rows ||
+                              (a.owner_rank && a.owner_rank[p] < 0);
             cls = skip ? 3 : n <= MAP_SMALL_MAX ? 0 : n <= MAP_WAVE_MAX ? 1 : 2;
             if (cls == 3) a.n_obs_used[p] = -1;
         }
@@ -102,7 +114,7 @@ __global__ void __launch_bounds__(256) k_mapgeom_small(MapGeomArgs a)
             geom_pos(a, row, p0, p1, p2);
         }
         float t0 = 0.0f, t1 = 0.0f, t2 = 0.0f;
-        const bool ok = i < n && geom_term(a, s + i, p0, p1, p2, t0, t1, t2);
+        const bool ok = i < n && geom_term(a, pt, s + i, p0, p1, p2, t0, t1, t2);
         s_t[t] = make_float4(t0, t1, t2, 0.0f);
         const uint32_t vm = (uint32_t)(__ballot(ok) >> (t & 48)) & 0xFFFFu;                                    // the group's observations that count
         const uint32_t rm = (uint32_t)(__ballot(i < n && a.v.obs_kf[s + i] == ref) >> (t & 48)) & 0xFFFFu;     // ... and the reference keyframe's
@@ -136,7 +148,7 @@ __global__ void __launch_bounds__(256) k_mapgeom_wave(MapGeomArgs a)
         for (int c = 0; c < n; c += 64) {
             const int p = c + lane;
             float t0 = 0.0f, t1 = 0.0f, t2 = 0.0f;
-            const bool ok = p < n && geom_term(a, s + p, p0, p1, p2, t0, t1, t2);
+            const bool ok = p < n && geom_term(a, pt, s + p, p0, p1, p2, t0, t1, t2);
             const unsigned long long mask = __ballot(ok), rmask = __ballot(p < n && a.v.obs_kf[s + p] == ref);
             if (o_ref < 0 && rmask) o_ref = s + c + (__ffsll((long long)rmask) - 1);
             N += __popcll(mask);
@@ -172,7 +184,7 @@ __global__ void __launch_bounds__(1024) k_mapgeom_block(MapGeomArgs a)
             const int m = min(MAPGEOM_CHUNK, n - c0);
             for (int j = threadIdx.x; j < m; j += blockDim.x) {
                 float t0 = 0.0f, t1 = 0.0f, t2 = 0.0f;
-                const bool ok = geom_term(a, s + c0 + j, p0, p1, p2, t0, t1, t2);
+                const bool ok = geom_term(a, pt, s + c0 + j, p0, p1, p2, t0, t1, t2);
                 s_t[j] = make_float4(t0, t1, t2, ok ? 1.0f : 0.0f);
                 if (a.v.obs_kf[s + c0 + j] == ref) atomicMin(&s_ref, c0 + j);
             }

@@ -80,7 +80,7 @@ def kf_keys_table(buffers, device="cuda"):
 
 def update_normal_and_depth(obs_start, obs_kf, kf_ow, ref_kf, world_pos, normal, min_distance=None, max_distance=None, ref_level=None, obs_idx=None,
                             kf_keys=None, scale_factors=None, point_bad=None, point_id=None, n_obs_used=None, device=0, stream=None, n_points=None,
-                            map_rows=None, n_kf=None, nlevels=None, pos_floats=None):
+                            map_rows=None, n_kf=None, nlevels=None, pos_floats=None, staged=None):
     """obs_start (n_points + 1,), obs_kf (total,) int32: the observation CSR, inside a point in the iteration order of mObservations (the float sum
     depends on it).  kf_ow (n_kf, 3) float32: the camera centres.  ref_kf (n_points,) int32: slot of mpRefKF.  The level of the reference key, in
     exactly one form: packed `ref_level` (n_points,) int32, or indirect `obs_idx` (total,) int32 with `kf_keys` = kf_keys_table(...).
@@ -90,6 +90,7 @@ def update_normal_and_depth(obs_start, obs_kf, kf_ow, ref_kf, world_pos, normal,
     Returns n_obs_used, an int32 device tensor: observations counted per point, -1 for a point left alone (bad, empty, ref_kf or row out of range).
     Every array is a contiguous torch tensor on the GPU of the dtype named above (checked), or an int device address (taken as it is); with
     addresses, `n_points`, `map_rows`, `n_kf`, `nlevels` and `pos_floats` give what a tensor would have carried.
+    staged = (kf_rank (n_kf,) int32, ow_new (K, 3) float32, owner_rank (n_points,) int32): plf_loop_normal_depth instead (rgbd_pl_slam_amd.loopfix).
     Only enqueues, on `stream` (a raw HIP stream) or the null stream."""
     import torch
     lib = L.mapgeom_prototypes(L.lib())
@@ -128,6 +129,17 @@ def update_normal_and_depth(obs_start, obs_kf, kf_ow, ref_kf, world_pos, normal,
     v.pos_floats = pos_floats
     if n_obs_used is None:
         n_obs_used = torch.empty(max(n_points, 0), dtype=torch.int32, device="cuda:%d" % device if isinstance(normal, int) or normal is None else normal.device)
+    if staged is not None:
+        kf_rank, ow_new, owner_rank = staged
+        K = int(ow_new.shape[0])
+        L.loopfix_prototypes(lib)
+        L.check(lib.plf_loop_normal_depth(C.byref(v), _arg(kf_rank, "kf_rank", torch.int32, n_kf), _arg(ow_new, "ow_new", torch.float32, K) if K else None, K,
+                                          _arg(owner_rank, "owner_rank", torch.int32, n_points), _arg(world_pos, "world_pos", torch.float32, map_rows),
+                                          _arg(normal, "normal", torch.float32, map_rows), _arg(min_distance, "min_distance", torch.float32, map_rows),
+                                          _arg(max_distance, "max_distance", torch.float32, map_rows), map_rows,
+                                          _arg(n_obs_used, "n_obs_used", torch.int32, n_points), device, C.c_void_p(stream) if stream else None),
+                "plf_loop_normal_depth")
+        return n_obs_used
     L.check(lib.plf_map_update_normal_depth(C.byref(v), _arg(world_pos, "world_pos", torch.float32, map_rows), _arg(normal, "normal", torch.float32, map_rows),
                                             _arg(min_distance, "min_distance", torch.float32, map_rows), _arg(max_distance, "max_distance", torch.float32, map_rows),
                                             map_rows, _arg(n_obs_used, "n_obs_used", torch.int32, n_points), device, C.c_void_p(stream) if stream else None),
