@@ -287,12 +287,13 @@ template <class T> class DeviceArray {
 public:
     DeviceArray() = default;
     DeviceArray(size_t n, int device = 0) { reset(n, device); }
-    template <class U> DeviceArray(const std::vector<U> &host, int device = 0) { static_assert(sizeof(U) == sizeof(T), "element size"); reset(host.size(), device); upload(host.data(), host.size()); }
+    template <class U> DeviceArray(const std::vector<U> &host, int device = 0) { assign(host, device); }
     ~DeviceArray() { plf_device_free(p_); }
     DeviceArray(const DeviceArray &) = delete;
     DeviceArray &operator=(const DeviceArray &) = delete;
     void reset(size_t n, int device = 0) { plf_device_free(p_); p_ = nullptr; n_ = n; void *q = nullptr; check(plf_device_alloc(device, n * sizeof(T), &q), "plf_device_alloc"); p_ = (T *)q; }
     void upload(const void *host, size_t n) { check(plf_upload(p_, host, n * sizeof(T), nullptr), "plf_upload"); }
+    template <class U> void assign(const std::vector<U> &host, int device = 0) { static_assert(sizeof(U) == sizeof(T), "element size"); reset(host.size(), device); upload(host.data(), host.size()); }
     void fill(int byte, void *stream = nullptr) { check(plf_fill(p_, byte, n_ * sizeof(T), stream), "plf_fill"); }   // NULL: synchronous; else enqueued on `stream`
     std::vector<T> download() const { std::vector<T> v(n_); check(plf_download(v.data(), p_, n_ * sizeof(T), nullptr), "plf_download"); return v; }
     T *get() const { return p_; }
@@ -911,6 +912,7 @@ public:
 #include <cstring>
 #include <memory>
 #include <set>
+#include <type_traits>
 #include <unordered_map>
 #include <utility>
 #include <opencv2/core.hpp>
@@ -975,20 +977,115 @@ inline std::vector<uint8_t> rows32(const cv::Mat &m)   // n x 32 CV_8U, rows pos
     for (int r = 0; r < m.rows; r++) memcpy(&out[(size_t)r * 32], m.data + (size_t)r * m.step, 32);
     return out;
 }
-// keyframe pointer -> slot in order of first appearance; first(pKF) runs once, when the keyframe is met for the first time
-struct KeyFrameSlots {
-    std::unordered_map<const void *, int> slot;
-    size_t size() const { return slot.size(); }
-    template <class KeyFrameT, class First> int operator()(KeyFrameT *pKF, First first)
+// ---- cv::Mat (CV_32F) <-> the float arrays of the C ABI.  A 3-vector is read with at<float>(k): a 3 x 1 or a 1 x 3 matrix.
+inline void put3(float *dst, const cv::Mat &v) { for (int k = 0; k < 3; k++) dst[k] = v.at<float>(k); }
+inline void put3(std::vector<float> &dst, const cv::Mat &v) { dst.resize(dst.size() + 3); put3(&dst[dst.size() - 3], v); }
+inline plf_pose34 pose34(const cv::Mat &Tcw)   // 3 x 4 or 4 x 4
+{
+    plf_pose34 T;
+    for (int r = 0; r < 3; r++) for (int c = 0; c < 4; c++) T.Tcw[4 * r + c] = Tcw.at<float>(r, c);
+    return T;
+}
+inline void pose34(const cv::Mat &Tcw, float *R, float *t)
+{
+    const plf_pose34 T = pose34(Tcw);
+    for (int r = 0; r < 3; r++) { for (int c = 0; c < 3; c++) R[3 * r + c] = T.Tcw[4 * r + c]; t[r] = T.Tcw[4 * r + 3]; }
+}
+inline plf_frustum_pose frustum_pose(const cv::Mat &Rcw, const cv::Mat &tcw, const cv::Mat &Ow = cv::Mat())   // an empty tcw / Ow stays 0
+{
+    plf_frustum_pose p = {};
+    for (int r = 0; r < 3; r++) for (int c = 0; c < 3; c++) p.Rcw[3 * r + c] = Rcw.at<float>(r, c);
+    if (!tcw.empty()) put3(p.tcw, tcw);
+    if (!Ow.empty()) put3(p.Ow, Ow);
+    return p;
+}
+inline cv::Mat mat31(const float *v) { cv::Mat m(3, 1, CV_32F); memcpy(m.data, v, 3 * sizeof(float)); return m; }   // (a new matrix is continuous)
+inline cv::Mat mat44(const plf_pose34 &T)   // [Rcw | tcw] over the row 0 0 0 1
+{
+    const float last[4] = {0.0f, 0.0f, 0.0f, 1.0f};
+    cv::Mat m(4, 4, CV_32F);
+    memcpy(m.data, T.Tcw, sizeof(T.Tcw)); memcpy(m.data + sizeof(T.Tcw), last, sizeof(last));
+    return m;
+}
+
+// ---- rows of map points -> point ids, observation CSR and keyframe slots: the host walk of every adapter that starts from the reference's map objects.
+// Slots and ids are handed out in order of first appearance, so the order in which an adapter calls slot() / point() / row() is part of its result.
+// The adapter's own arrays are filled by three callables, inlined into the one pass: onKeyFrame(pKF) when a keyframe gets its slot, onObservation(pKF, idx)
+// per appended observation, onPoint(gatherer, pMP, observations) when a point gets its id, after its observations are appended.
+struct Ignore { template <class... A> void operator()(A &&...) const {} };
+template <class KeyFrameT> using MapPointOf =
+    typename std::remove_pointer<typename std::decay<decltype(std::declval<KeyFrameT &>().GetMapPointMatches())>::type::value_type>::type;
+template <class PointT> using KeyFrameOf =
+    typename std::remove_pointer<typename std::decay<decltype(std::declval<PointT &>().GetObservations())>::type::key_type>::type;
+// THE rule for empty device arrays: the C ABI accepts them (0 bytes allocate, upload and download fine), and an array that is indexed through a CSR gets one
+// element of padding beyond its ranges, never read, appended here and nowhere else: -1 for indices, 0 for flags and values.
+template <class T, class U> const std::vector<T> &padded(std::vector<T> &v, U pad) { v.push_back((T)pad); return v; }
+template <class KeyFrameT, class MapPointT, class OnKeyFrame = Ignore, class OnPoint = Ignore, class OnObservation = Ignore> struct MapGather {
+    std::vector<KeyFrameT *> kfs;                                   // by slot
+    std::vector<MapPointT *> pts;                                   // by id
+    std::vector<int32_t> row_start{0}, row_point, obs_start{0}, obs_kf;
+    std::vector<uint8_t> point_bad;
+    explicit MapGather(OnKeyFrame k = OnKeyFrame(), OnPoint p = OnPoint(), OnObservation o = OnObservation()) : on_kf_(k), on_point_(p), on_obs_(o) {}
+    int slot(KeyFrameT *pKF)
     {
-        const auto at = slot.emplace((const void *)pKF, (int)slot.size());
-        if (at.second) first(pKF);
+        const auto at = slot_.emplace(pKF, (int)kfs.size());
+        if (at.second) { kfs.push_back(pKF); on_kf_(pKF); }
         return at.first->second;
     }
+    // one range of the observation CSR, in the std::map's order (the point-list adapters, which give no ids, call this per entry)
+    template <class Observations> void observed(const Observations &observations)
+    {
+        for (const auto &ob : observations) { obs_kf.push_back(slot(ob.first)); on_obs_(ob.first, (size_t)ob.second); }
+        obs_start.push_back((int32_t)obs_kf.size());
+    }
+    // with_observations = false: an id and a bad flag only (a point that only fills rows; all such points come after the observed ones)
+    int point(MapPointT *pMP, bool with_observations = true)
+    {
+        const auto at = id_.emplace(pMP, (int)pts.size());
+        if (at.second) {
+            pts.push_back(pMP); point_bad.push_back(pMP->isBad());
+            if (with_observations) { const auto observations = pMP->GetObservations(); observed(observations); on_point_(*this, pMP, observations); }
+        }
+        return at.first->second;
+    }
+    void row(const std::vector<MapPointT *> &points, bool with_observations = true)
+    {
+        for (MapPointT *pMP : points) row_point.push_back(pMP ? point(pMP, with_observations) : -1);
+        row_start.push_back((int32_t)row_point.size());
+    }
+    // the upload: the five arrays as they stand, the indexed ones padded
+    struct Device {
+        plf::DeviceArray<int32_t> row_start, row_point, obs_start, obs_kf;
+        plf::DeviceArray<uint8_t> point_bad;
+        Device(MapGather &g, int device)
+            : row_start(g.row_start, device), row_point(padded(g.row_point, -1), device), obs_start(g.obs_start, device), obs_kf(padded(g.obs_kf, -1), device),
+              point_bad(padded(g.point_bad, 0), device) {}
+    };
+private:
+    std::unordered_map<KeyFrameT *, int> slot_;
+    std::unordered_map<MapPointT *, int> id_;
+    OnKeyFrame on_kf_;
+    OnPoint on_point_;
+    OnObservation on_obs_;
 };
-inline void pose34(const cv::Mat &Tcw, float *R, float *t)   // 4x4 CV_32F
+template <class KeyFrameT, class MapPointT, class OnKeyFrame = Ignore, class OnPoint = Ignore, class OnObservation = Ignore>
+MapGather<KeyFrameT, MapPointT, OnKeyFrame, OnPoint, OnObservation> map_gather(OnKeyFrame k = OnKeyFrame(), OnPoint p = OnPoint(), OnObservation o = OnObservation())
 {
-    for (int r = 0; r < 3; r++) { for (int c = 0; c < 3; c++) R[r * 3 + c] = Tcw.at<float>(r, c); t[r] = Tcw.at<float>(r, 3); }
+    return MapGather<KeyFrameT, MapPointT, OnKeyFrame, OnPoint, OnObservation>(k, p, o);
+}
+// MapPoint::UpdateNormalAndDepth's reference keyframe and level, as its operator[] resolves them: none (-1, level 0) without a reference keyframe or an
+// observation; index 0 for a reference keyframe that does not observe the point; octave 0 for an index beyond mvKeysUn.  The scale table of the first
+// reference keyframe met serves the call (`scale` is filled once): every keyframe of a map carries the same one.
+template <class Gather, class KeyFrameT, class Observations>
+void ref_level(Gather &g, KeyFrameT *pRefKF, const Observations &observations, std::vector<float> &scale, int32_t &ref, int32_t &level)
+{
+    ref = -1; level = 0;
+    if (!pRefKF || observations.empty()) return;
+    ref = g.slot(pRefKF);
+    const auto it = observations.find(pRefKF);
+    const size_t idx = it == observations.end() ? 0 : it->second;
+    level = idx < pRefKF->mvKeysUn.size() ? pRefKF->mvKeysUn[idx].octave : 0;
+    if (scale.empty()) scale.assign(pRefKF->mvScaleFactors.begin(), pRefKF->mvScaleFactors.begin() + pRefKF->mnScaleLevels);
 }
 }  // namespace detail
 
@@ -1053,8 +1150,7 @@ public:
             has[i] = p != nullptr; outl[i] = LastFrame.mvbOutlier[i];
             if (!p) continue;
             obs[i] = p->Observations() > 0;
-            const cv::Mat w = p->GetWorldPos();
-            for (int c = 0; c < 3; c++) xw[(size_t)i * 3 + c] = w.template at<float>(c);
+            detail::put3(&xw[(size_t)i * 3], p->GetWorldPos());
             const cv::Mat d = p->GetDescriptor();
             memcpy(&desc[(size_t)i * 32], d.data, 32);
         }
@@ -1344,33 +1440,30 @@ template <class PointT, class DescOf> DistinctiveDescriptors distinctive(const s
     out.desc.create(P, 32, CV_8U);
     if (P == 0) return out;
     memset(out.desc.data, 0, (size_t)P * 32);
-    std::vector<int32_t> start(P + 1, 0), kf, idx;
+    typedef KeyFrameOf<PointT> KeyFrameT;
+    std::vector<int32_t> idx;
     std::vector<uint8_t> valid;
-    KeyFrameSlots seen;
     std::vector<std::vector<uint8_t>> rows;
-    for (int i = 0; i < P; i++) {
-        if (points[i]) {
-            const auto observations = points[i]->GetObservations();
-            for (const auto &ob : observations) {
-                auto *pKF = ob.first;
-                kf.push_back(seen(pKF, [&](auto *first) { rows.push_back(rows32(descOf(first))); })); idx.push_back((int32_t)ob.second); valid.push_back(!pKF->isBad());
-            }
-        }
-        start[i + 1] = (int32_t)kf.size();
+    auto g = map_gather<KeyFrameT, PointT>([&](KeyFrameT *pKF) { rows.push_back(rows32(descOf(pKF))); }, Ignore(),
+                                           [&](KeyFrameT *pKF, size_t i) { idx.push_back((int32_t)i); valid.push_back(!pKF->isBad()); });
+    for (PointT *p : points) {                                      // one range per entry, a point listed twice included; a null entry: an empty range
+        if (p) g.observed(p->GetObservations());
+        else g.obs_start.push_back(g.obs_start.back());
     }
-    if (kf.empty()) return out;
-    std::vector<plf::DeviceArray<uint8_t>> dkf(seen.size());
-    std::vector<const uint8_t *> table(seen.size());
-    for (size_t k = 0; k < seen.size(); k++) {
+    const size_t n_kf = g.kfs.size();
+    if (g.obs_kf.empty()) return out;
+    std::vector<plf::DeviceArray<uint8_t>> dkf(n_kf);
+    std::vector<const uint8_t *> table(n_kf);
+    for (size_t k = 0; k < n_kf; k++) {
         dkf[k].reset(rows[k].size() + 32, device);
         if (!rows[k].empty()) dkf[k].upload(rows[k].data(), rows[k].size());
         table[k] = dkf[k].get();
     }
-    plf::DeviceArray<int32_t> dstart(start, device), dk(kf, device), di(idx, device), dbo(P, device), dbm(P, device);
+    plf::DeviceArray<int32_t> dstart(g.obs_start, device), dk(g.obs_kf, device), di(idx, device), dbo(P, device), dbm(P, device);
     plf::DeviceArray<uint8_t> dv(valid, device), dmap((size_t)P * 32, device);
     plf::DeviceArray<const uint8_t *> dtab(table, device);
     dmap.fill(0);
-    plf_map_obs_view v = {P, dstart.get(), nullptr, dk.get(), di.get(), dtab.get(), (int32_t)seen.size(), dv.get(), nullptr};
+    plf_map_obs_view v = {P, dstart.get(), nullptr, dk.get(), di.get(), dtab.get(), (int32_t)n_kf, dv.get(), nullptr};
     plf::check(plf_map_distinctive_descriptors(&v, dmap.get(), P, dbo.get(), dbm.get(), device, nullptr), "ComputeDistinctiveDescriptors");
     const std::vector<uint8_t> d = dmap.download();          // a NULL-stream download waits for the device first
     memcpy(out.desc.data, d.data(), d.size());
@@ -1404,39 +1497,28 @@ template <class MapPointT> NormalAndDepth UpdateNormalAndDepth(const std::vector
     const int P = (int)vpMapPoints.size();
     out.normal.assign((size_t)P * 3, 0.0f); out.minDistance.assign(P, 0.0f); out.maxDistance.assign(P, 0.0f); out.n.assign(P, -1);
     if (P == 0) return out;
-    std::vector<int32_t> start(P + 1, 0), kf, ref(P, -1), level(P, 0);
+    typedef detail::KeyFrameOf<MapPointT> KeyFrameT;
+    std::vector<int32_t> ref(P, -1), level(P, 0);
     std::vector<uint8_t> bad(P, 1);
     std::vector<float> pos((size_t)P * 3, 0.0f), ow, scale;
-    detail::KeyFrameSlots seen;
-    auto slot_of = [&](auto *pKF) {
-        return seen(pKF, [&](auto *first) { const cv::Mat Ow = first->GetCameraCenter(); for (int k = 0; k < 3; k++) ow.push_back(Ow.template at<float>(k)); });
-    };
-    for (int i = 0; i < P; i++) {
+    auto g = detail::map_gather<KeyFrameT, MapPointT>([&](KeyFrameT *pKF) { detail::put3(ow, pKF->GetCameraCenter()); });
+    for (int i = 0; i < P; i++) {                                   // one range per entry, a point listed twice included; null or bad: an empty range
         MapPointT *pMP = vpMapPoints[i];
         if (pMP && !pMP->isBad()) {
             bad[i] = 0;
             const auto observations = pMP->GetObservations();
-            auto *pRefKF = pMP->GetReferenceKeyFrame();
-            const cv::Mat Pos = pMP->GetWorldPos();
-            for (int k = 0; k < 3; k++) pos[(size_t)i * 3 + k] = Pos.template at<float>(k);
-            for (const auto &ob : observations) kf.push_back(slot_of(ob.first));
-            if (pRefKF && !observations.empty()) {
-                ref[i] = slot_of(pRefKF);
-                const auto it = observations.find(pRefKF);
-                const size_t idx = it == observations.end() ? 0 : it->second;
-                level[i] = idx < pRefKF->mvKeysUn.size() ? pRefKF->mvKeysUn[idx].octave : 0;
-                if (scale.empty()) scale.assign(pRefKF->mvScaleFactors.begin(), pRefKF->mvScaleFactors.begin() + pRefKF->mnScaleLevels);
-            }
-        }
-        start[i + 1] = (int32_t)kf.size();
+            detail::put3(&pos[(size_t)i * 3], pMP->GetWorldPos());
+            g.observed(observations);
+            detail::ref_level(g, pMP->GetReferenceKeyFrame(), observations, scale, ref[i], level[i]);
+        } else g.obs_start.push_back(g.obs_start.back());
     }
-    if (kf.empty() || scale.empty()) return out;
-    plf::DeviceArray<int32_t> dstart(start, device), dk(kf, device), dref(ref, device), dlevel(level, device), dn(P, device);
+    if (g.obs_kf.empty() || scale.empty()) return out;
+    plf::DeviceArray<int32_t> dstart(g.obs_start, device), dk(g.obs_kf, device), dref(ref, device), dlevel(level, device), dn(P, device);
     plf::DeviceArray<uint8_t> dbad(bad, device);
     plf::DeviceArray<float> dpos(pos, device), dow(ow, device), dscale(scale, device), dnormal(out.normal, device), dmin(out.minDistance, device),
         dmax(out.maxDistance, device);
     plf_map_geom_view v = {};
-    v.n_points = P; v.obs_start = dstart.get(); v.obs_kf = dk.get(); v.kf_ow = dow.get(); v.n_kf = (int32_t)seen.size(); v.ref_kf = dref.get();
+    v.n_points = P; v.obs_start = dstart.get(); v.obs_kf = dk.get(); v.kf_ow = dow.get(); v.n_kf = (int32_t)g.kfs.size(); v.ref_kf = dref.get();
     v.ref_level = dlevel.get(); v.scale_factors = dscale.get(); v.nlevels = (int32_t)scale.size(); v.point_bad = dbad.get(); v.pos_floats = 3;
     plf::check(plf_map_update_normal_depth(&v, dpos.get(), dnormal.get(), dmin.get(), dmax.get(), P, dn.get(), device, nullptr), "UpdateNormalAndDepth");
     out.normal = dnormal.download();                       // a NULL-stream download waits for the device first
@@ -1470,15 +1552,15 @@ public:
     void UpdateConnections(const std::vector<KeyFrameT *> &vpKFs, int th = 15)
     {
         Gather g;
-        for (KeyFrameT *pKF : vpKFs) {
-            g.slot(pKF);
+        std::vector<int32_t> row_self;
+        for (KeyFrameT *pKF : vpKFs) {                  // slots: a row's owner before the observers its row brings
+            row_self.push_back(g.slot(pKF));
             g.row(pKF->GetMapPointMatches());
-            g.self.push_back(g.slot(pKF));
         }
         if (vpKFs.empty()) return;
         const int R = (int)vpKFs.size(), S = (int)g.kfs.size();
         Device d(g, device_);
-        plf::DeviceArray<int32_t> self(g.self, device_), cn(R, device_), on(R, device_), mk(R, device_), mw(R, device_), ck, cw, ok, ow;
+        plf::DeviceArray<int32_t> self(row_self, device_), cn(R, device_), on(R, device_), mk(R, device_), mw(R, device_), ck, cw, ok, ow;
         plf_covis_view v = d.view(R, S);
         v.row_self = self.get();
         // the outputs are R x stride: a first pass with a stride that holds an ordinary neighbourhood, and -- the counts are the true ones -- a second
@@ -1563,49 +1645,21 @@ public:
     }
 
 private:
-    // slots for the keyframes and ids for the points in order of first appearance; the two CSRs as host vectors
-    struct Gather {
-        std::vector<KeyFrameT *> kfs;
-        detail::KeyFrameSlots kf_slot;
-        std::unordered_map<MapPointT *, int> point_id;
-        std::vector<int32_t> row_start{0}, row_point, self, obs_start{0}, obs_kf;
-        std::vector<uint8_t> point_bad;
-        int slot(KeyFrameT *pKF) { return kf_slot(pKF, [&](KeyFrameT *first) { kfs.push_back(first); }); }
-        void row(const std::vector<MapPointT *> &points)
-        {
-            for (MapPointT *pMP : points) {
-                if (!pMP) { row_point.push_back(-1); continue; }
-                const auto at = point_id.emplace(pMP, (int)point_bad.size());
-                if (at.second) {
-                    point_bad.push_back(pMP->isBad());
-                    const auto observations = pMP->GetObservations();
-                    for (const auto &ob : observations) obs_kf.push_back(slot(ob.first));
-                    obs_start.push_back((int32_t)obs_kf.size());
-                }
-                row_point.push_back(at.first->second);
-            }
-            row_start.push_back((int32_t)row_point.size());
-        }
-    };
-    struct Device {
+    typedef detail::MapGather<KeyFrameT, MapPointT> Gather;
+    struct Device : Gather::Device {
         int n_points;
-        plf::DeviceArray<int32_t> row_start, row_point, obs_start, obs_kf;
-        plf::DeviceArray<uint8_t> point_bad;
-        plf::DeviceArray<int64_t> key;
-        // one element of padding each: never an empty allocation; beyond the CSR ranges, never read
-        Device(Gather &g, int device)
-            : n_points((int)g.point_bad.size()), row_start(g.row_start, device), row_point(padded(g.row_point, -1), device), obs_start(g.obs_start, device),
-              obs_kf(padded(g.obs_kf, -1), device), point_bad(padded(g.point_bad, 0), device), key(keys(g.kfs), device) {}
-        template <class T> static const std::vector<T> &padded(std::vector<T> &v, int pad) { v.push_back((T)pad); return v; }
+        plf::DeviceArray<int64_t> key;                  // the keyframes' addresses (padded like the gathered arrays)
+        Device(Gather &g, int device) : Gather::Device(g, device), n_points((int)g.pts.size()), key(keys(g.kfs), device) {}
         static std::vector<int64_t> keys(const std::vector<KeyFrameT *> &kfs)
         {
-            std::vector<int64_t> k(kfs.size() + 1, 0);
-            for (size_t s = 0; s < kfs.size(); s++) k[s] = (int64_t)(intptr_t)kfs[s];
-            return k;
+            std::vector<int64_t> k;
+            for (KeyFrameT *pKF : kfs) k.push_back((int64_t)(intptr_t)pKF);
+            return detail::padded(k, 0);
         }
         plf_covis_view view(int n_rows, int n_kf) const
         {
-            return plf_covis_view{n_rows, row_start.get(), row_point.get(), nullptr, n_points, obs_start.get(), obs_kf.get(), point_bad.get(), n_kf, nullptr, key.get()};
+            return plf_covis_view{n_rows, this->row_start.get(), this->row_point.get(), nullptr, n_points, this->obs_start.get(), this->obs_kf.get(),
+                                  this->point_bad.get(), n_kf, nullptr, key.get()};
         }
     };
     int device_, first_stride_;
@@ -1631,56 +1685,40 @@ template <class KeyFrameT> KeyFrameCullingResult<KeyFrameT> KeyFrameCulling(cons
     const int C = (int)vpLocalKeyFrames.size();
     out.nMPs.assign(C, -1); out.nRedundantObservations.assign(C, -1); out.decision.assign(C, 3);
     if (C == 0) return out;
-    detail::KeyFrameSlots kf_slot;
-    std::unordered_map<const void *, int> point_id;
-    std::vector<int32_t> row_start{0}, row_point, row_kf, row_level, obs_start{0}, obs_kf, obs_level, cand_row(C);
+    std::vector<int32_t> row_kf, row_level, obs_level, cand_row(C);
     std::vector<float> row_depth;
-    std::vector<uint8_t> obs_w, point_bad, cand_flags(C, 0);
-    auto slot_of = [&](auto *pKF) { return kf_slot(pKF, [](auto *) {}); };
+    std::vector<uint8_t> obs_w, cand_flags(C, 0);
+    auto g = detail::map_gather<KeyFrameT, detail::MapPointOf<KeyFrameT>>(detail::Ignore(), detail::Ignore(), [&](KeyFrameT *pKFi, size_t idx) {
+        obs_level.push_back(idx < pKFi->mvKeysUn.size() ? pKFi->mvKeysUn[idx].octave : 0);
+        obs_w.push_back(idx < pKFi->mvuRight.size() && pKFi->mvuRight[idx] >= 0 ? 2 : 1);
+    });
     float th_depth = 0.0f;
     for (int j = 0; j < C; j++) {
         KeyFrameT *pKF = vpLocalKeyFrames[j];
         cand_row[j] = j;
         cand_flags[j] = (uint8_t)((pKF->mnId == 0 ? 1 : 0) | (j < (int)vbNotErase.size() && vbNotErase[j] ? 2 : 0));
         if (j == 0) th_depth = pKF->mThDepth;
-        row_kf.push_back(slot_of(pKF));
+        row_kf.push_back(g.slot(pKF));                              // slots: the candidate before the observers its row brings
         const auto vpMapPoints = pKF->GetMapPointMatches();
-        for (size_t i = 0; i < vpMapPoints.size(); i++) {
-            auto *pMP = vpMapPoints[i];
+        for (size_t i = 0; i < vpMapPoints.size(); i++) {           // per entry of the row, a null one included
             row_level.push_back(i < pKF->mvKeysUn.size() ? pKF->mvKeysUn[i].octave : 0);
             row_depth.push_back(i < pKF->mvDepth.size() ? pKF->mvDepth[i] : 0.0f);
-            if (!pMP) { row_point.push_back(-1); continue; }
-            const auto at = point_id.emplace((const void *)pMP, (int)point_bad.size());
-            if (at.second) {
-                point_bad.push_back(pMP->isBad());
-                const auto observations = pMP->GetObservations();
-                for (const auto &ob : observations) {
-                    auto *pKFi = ob.first;
-                    const size_t idx = ob.second;
-                    obs_kf.push_back(slot_of(pKFi));
-                    obs_level.push_back(idx < pKFi->mvKeysUn.size() ? pKFi->mvKeysUn[idx].octave : 0);
-                    obs_w.push_back(idx < pKFi->mvuRight.size() && pKFi->mvuRight[idx] >= 0 ? 2 : 1);
-                }
-                obs_start.push_back((int32_t)obs_kf.size());
-            }
-            row_point.push_back(at.first->second);
         }
-        row_start.push_back((int32_t)row_point.size());
+        g.row(vpMapPoints);
     }
-    const int P = (int)point_bad.size(), S = (int)kf_slot.size();
-    // one element of padding each: never an empty allocation; beyond the CSR ranges, never read
-    row_point.push_back(-1); row_level.push_back(0); row_depth.push_back(0.0f); obs_kf.push_back(-1); obs_level.push_back(0); obs_w.push_back(1); point_bad.push_back(0);
-    std::vector<uint8_t> gone(S + 1, 0);
-    plf::DeviceArray<int32_t> d_row_start(row_start, device), d_row_point(row_point, device), d_row_kf(row_kf, device), d_row_level(row_level, device),
-        d_obs_start(obs_start, device), d_obs_kf(obs_kf, device), d_obs_level(obs_level, device), d_cand(cand_row, device), d_mps(C, device), d_red(C, device),
-        d_dec(C, device), d_status(2, device);
-    plf::DeviceArray<float> d_row_depth(row_depth, device);
-    plf::DeviceArray<uint8_t> d_obs_w(obs_w, device), d_bad(point_bad, device), d_flags(cand_flags, device), d_gone(gone, device), d_erased(gone, device),
+    const int P = (int)g.pts.size(), S = (int)g.kfs.size();
+    typename decltype(g)::Device d(g, device);
+    std::vector<uint8_t> &point_bad = g.point_bad, gone(S + 1, 0);
+    plf::DeviceArray<int32_t> d_row_kf(row_kf, device), d_row_level(detail::padded(row_level, 0), device), d_obs_level(detail::padded(obs_level, 0), device),
+        d_cand(cand_row, device), d_mps(C, device), d_red(C, device), d_dec(C, device), d_status(2, device);
+    plf::DeviceArray<float> d_row_depth(detail::padded(row_depth, 0.0f), device);
+    plf::DeviceArray<uint8_t> &d_bad = d.point_bad;
+    plf::DeviceArray<uint8_t> d_obs_w(detail::padded(obs_w, 1), device), d_flags(cand_flags, device), d_gone(gone, device), d_erased(gone, device),
         d_went(point_bad.size(), device);
     d_went.fill(0);
     plf_cull_view v = {};
-    v.n_rows = C; v.row_start = d_row_start.get(); v.row_point = d_row_point.get(); v.row_kf = d_row_kf.get(); v.n_points = P; v.obs_start = d_obs_start.get();
-    v.obs_kf = d_obs_kf.get(); v.obs_w = d_obs_w.get(); v.point_bad = d_bad.get(); v.n_kf = S; v.kf_gone = d_gone.get(); v.row_level = d_row_level.get();
+    v.n_rows = C; v.row_start = d.row_start.get(); v.row_point = d.row_point.get(); v.row_kf = d_row_kf.get(); v.n_points = P; v.obs_start = d.obs_start.get();
+    v.obs_kf = d.obs_kf.get(); v.obs_w = d_obs_w.get(); v.point_bad = d_bad.get(); v.n_kf = S; v.kf_gone = d_gone.get(); v.row_level = d_row_level.get();
     v.obs_level = d_obs_level.get(); v.row_depth = mbMonocular ? nullptr : d_row_depth.get(); v.th_depth = th_depth; v.monocular = mbMonocular ? 1 : 0;
     const plf_cull_params p = {PLF_CULL_SEQUENTIAL, 3, max_culls, 0, 0.9};
     for (int done = 0; done < C;) {
@@ -1721,33 +1759,16 @@ LocalMapResult<KeyFrameT, MapPointT> UpdateLocalMap(FrameT &mCurrentFrame, std::
                                                      KeyFrameT *&mpReferenceKF, int device = 0, void *stream = nullptr)
 {
     LocalMapResult<KeyFrameT, MapPointT> out;
-    std::vector<KeyFrameT *> kfs;
-    detail::KeyFrameSlots kf_slot;
-    auto slot_of = [&](KeyFrameT *pKF) { return kf_slot(pKF, [&](KeyFrameT *first) { kfs.push_back(first); }); };
-    std::vector<MapPointT *> pts;
-    std::unordered_map<MapPointT *, int> point_id;
-    std::vector<uint8_t> point_bad;
-    auto id_of = [&](MapPointT *pMP) {
-        const auto at = point_id.emplace(pMP, (int)pts.size());
-        if (at.second) { pts.push_back(pMP); point_bad.push_back(pMP->isBad()); }
-        return at.first->second;
-    };
-    // ---- the frame's own row and the observations of its points: the votes
-    std::vector<int32_t> frame_start{0}, frame_item, obs_start{0}, obs_kf;
-    for (auto &pMP : mCurrentFrame.mvpMapPoints) {
-        if (pMP && pMP->isBad()) pMP = nullptr;
-        if (!pMP) { frame_item.push_back(-1); continue; }
-        const size_t known = pts.size();
-        const int id = id_of(pMP);
-        if (pts.size() != known) {
-            const auto observations = pMP->GetObservations();
-            for (const auto &ob : observations) obs_kf.push_back(slot_of(ob.first));
-            obs_start.push_back((int32_t)obs_kf.size());
-        }
-        frame_item.push_back(id);
-    }
-    frame_start.push_back((int32_t)frame_item.size());
-    const int own_points = (int)pts.size(), S1 = (int)kfs.size();
+    detail::MapGather<KeyFrameT, MapPointT> g;
+    std::vector<KeyFrameT *> &kfs = g.kfs;
+    std::vector<int32_t> &obs_kf = g.obs_kf;
+    auto slot_of = [&](KeyFrameT *pKF) { return g.slot(pKF); };
+    // ---- the frame's own row and the observations of its points: the votes.  The row is set aside; the gatherer's rows are the keyframes' from here on.
+    for (auto &pMP : mCurrentFrame.mvpMapPoints) if (pMP && pMP->isBad()) pMP = nullptr;
+    g.row(mCurrentFrame.mvpMapPoints);
+    std::vector<int32_t> frame_start{0}, frame_item;
+    frame_start.swap(g.row_start); frame_item.swap(g.row_point);
+    const int own_points = (int)g.pts.size(), S1 = (int)kfs.size();
     const bool voted = S1 > 0;
     // ---- the possible seeds with their neighbours, children and parent; without a vote the list that stays
     std::vector<int32_t> covis, n_covis, child_start{0}, child_kf, parent, keep;
@@ -1788,31 +1809,29 @@ LocalMapResult<KeyFrameT, MapPointT> UpdateLocalMap(FrameT &mCurrentFrame, std::
         for (int32_t &k : obs_kf) k = moved(k);
         for (int32_t &k : keep) k = moved(k);
     }
-    // ---- the rows of every keyframe that can end up in the list
-    std::vector<int32_t> row_start{0}, row_item;
+    // ---- the rows of every keyframe that can end up in the list; a point first met here gets an id and a bad flag, no observations: it cannot vote
+    // (the slots were renumbered above, so slot() is not called any more)
     std::vector<uint8_t> kf_bad(S);
     for (int s = 0; s < S; s++) {
         kf_bad[s] = kfs[s]->isBad();
-        const std::vector<MapPointT *> vpMPs = kfs[s]->GetMapPointMatches();
-        for (MapPointT *pMP : vpMPs) row_item.push_back(pMP ? id_of(pMP) : -1);
-        row_start.push_back((int32_t)row_item.size());
+        g.row(kfs[s]->GetMapPointMatches(), false);
     }
+    const std::vector<MapPointT *> &pts = g.pts;
     const int P = (int)pts.size(), kf_stride = std::max(S, (int)keep.size()), item_stride = std::max(P, 1);
-    // one element of padding each: never an empty allocation; beyond the CSR ranges, never read
-    frame_item.push_back(-1); obs_kf.push_back(-1); child_kf.push_back(-1); row_item.push_back(-1); point_bad.push_back(0);
-    plf::DeviceArray<int32_t> d_fs(frame_start, device), d_fi(frame_item, device), d_os(obs_start, device), d_ok(obs_kf, device), d_cov(covis, device), d_ncov(n_covis, device),
-        d_cs(child_start, device), d_ck(child_kf, device), d_par(parent, device), d_rs(row_start, device), d_ri(row_item, device), d_seed(std::max(S1, 1), device),
+    const typename decltype(g)::Device d(g, device);
+    plf::DeviceArray<int32_t> d_fs(frame_start, device), d_fi(detail::padded(frame_item, -1), device), d_cov(covis, device), d_ncov(n_covis, device),
+        d_cs(child_start, device), d_ck(detail::padded(child_kf, -1), device), d_par(parent, device), d_seed(std::max(S1, 1), device),
         d_w(std::max(S1, 1), device), d_nseed(1, device), d_mk(1, device), d_mw(1, device);
-    plf::DeviceArray<uint8_t> d_pbad(point_bad, device), d_kbad(kf_bad, device);
+    plf::DeviceArray<uint8_t> d_kbad(kf_bad, device);
     plf::LocalMap lm(1, kf_stride, item_stride, device);
-    const plf::LocalMap::Rows rows = {d_rs.get(), d_ri.get(), d_pbad.get(), P};
+    const plf::LocalMap::Rows rows = {d.row_start.get(), d.row_point.get(), d.point_bad.get(), P};
     if (voted) {
-        const plf_covis_view v = {1, d_fs.get(), d_fi.get(), nullptr, own_points, d_os.get(), d_ok.get(), d_pbad.get(), S, d_kbad.get(), nullptr};
+        const plf_covis_view v = {1, d_fs.get(), d_fi.get(), nullptr, own_points, d.obs_start.get(), d.obs_kf.get(), d.point_bad.get(), S, d_kbad.get(), nullptr};
         const plf_covis_params p = {PLF_COVIS_VOTES, 1, std::max(S1, 1), 0, 0};
         plf::check(plf_covis_count(&v, &p, d_seed.get(), d_w.get(), d_nseed.get(), nullptr, nullptr, nullptr, d_mk.get(), d_mw.get(), device, stream),
                    "Tracking::UpdateLocalKeyFrames");
-        const plf::LocalMap::Graph g = {d_cov.get(), d_ncov.get(), n_best, d_cs.get(), d_ck.get(), d_par.get(), d_kbad.get(), S};
-        lm.Update(d_seed.get(), d_nseed.get(), std::max(S1, 1), g, rows, d_fs.get(), d_fi.get(), stream, n_best, 80);
+        const plf::LocalMap::Graph graph = {d_cov.get(), d_ncov.get(), n_best, d_cs.get(), d_ck.get(), d_par.get(), d_kbad.get(), S};
+        lm.Update(d_seed.get(), d_nseed.get(), std::max(S1, 1), graph, rows, d_fs.get(), d_fi.get(), stream, n_best, 80);
     } else {
         keep.resize(kf_stride, -1);
         const std::vector<int32_t> n_keep(1, (int32_t)mvpLocalKeyFrames.size());
@@ -1856,14 +1875,11 @@ struct Optimizer {
             flags[i] = pFrame->mvbOutlier[i] ? 1 : 0;
             auto *pMP = pFrame->mvpMapPoints[i];
             if (!pMP) continue;
-            const cv::Mat Xw = pMP->GetWorldPos();
             match[i] = nInitialCorrespondences++;
-            for (int k = 0; k < 3; k++) pos.push_back(Xw.template at<float>(k));
+            detail::put3(pos, pMP->GetWorldPos());
         }
         if (nInitialCorrespondences < 3) return 0;
-        plf_pose34 pin, pout;
-        for (int r = 0; r < 3; r++)
-            for (int c = 0; c < 4; c++) pin.Tcw[4 * r + c] = pFrame->mTcw.template at<float>(r, c);
+        const plf_pose34 pin = detail::pose34(pFrame->mTcw);
         const std::vector<float> sigma2(pFrame->mvInvLevelSigma2.begin(), pFrame->mvInvLevelSigma2.end());
         plf::DeviceArray<plf_keypoint> dkeys(keys, device);
         plf::DeviceArray<float> dur(uright, device), dpos(pos, device), dsig(sigma2, device);
@@ -1876,14 +1892,11 @@ struct Optimizer {
         plf_camera cam = {};
         cam.fx = pFrame->fx; cam.fy = pFrame->fy; cam.cx = pFrame->cx; cam.cy = pFrame->cy; cam.bf = pFrame->mbf;
         plf::check(plf_pose_optimize(&v, &cam, &pin, PLF_MEM_HOST, dout.get(), nullptr, dflags.get(), dn.get(), dst.get(), device, nullptr), "PoseOptimization");
-        pout = dout.download()[0];                            // a NULL-stream download waits for the device first
+        const plf_pose34 pout = dout.download()[0];           // a NULL-stream download waits for the device first
         flags = dflags.download();
         for (int i = 0; i < N; i++)
             if (match[i] >= 0) pFrame->mvbOutlier[i] = flags[i] != 0;
-        cv::Mat Tcw(4, 4, CV_32F);
-        for (int r = 0; r < 4; r++)
-            for (int c = 0; c < 4; c++) Tcw.template at<float>(r, c) = r < 3 ? pout.Tcw[4 * r + c] : (c == 3 ? 1.0f : 0.0f);
-        pFrame->SetPose(Tcw);
+        pFrame->SetPose(detail::mat44(pout));
         return dn.download()[0];
     }
 
@@ -1914,8 +1927,7 @@ struct Optimizer {
             if (it != ids.end()) return it->second;
             const int32_t id = (int32_t)ids.size();
             ids.emplace(p, id);
-            const cv::Mat X = p->GetWorldPos();
-            for (int r = 0; r < 3; r++) world.push_back(X.template at<float>(r, 0));
+            detail::put3(world, p->GetWorldPos());
             bad.push_back(p->isBad() ? 1 : 0);
             return id;
         };
@@ -1924,12 +1936,7 @@ struct Optimizer {
             keys[s].resize(std::max(n, 1));
             if (n) std::memcpy((void *)keys[s].data(), kf[s]->mvKeysUn.data(), (size_t)n * sizeof(plf_keypoint));
             mps[s].assign(std::max(n, 1), -1);
-            const cv::Mat Rcw = kf[s]->GetRotation(), tcw = kf[s]->GetTranslation();
-            for (int r = 0; r < 3; r++) {
-                for (int c = 0; c < 3; c++) pose[s].Rcw[3 * r + c] = Rcw.template at<float>(r, c);
-                pose[s].tcw[r] = tcw.template at<float>(r, 0);
-                pose[s].Ow[r] = 0.0f;
-            }
+            pose[s] = detail::frustum_pose(kf[s]->GetRotation(), kf[s]->GetTranslation());
         }
         for (int i = 0; i < N && i < n1; i++) {
             MapPointT *pMP2 = vpMatches1[i];
@@ -2062,12 +2069,10 @@ private:
             depth[i] = F.mvDepth[i];
             if (F.mvpMapPoints[i]) { match[i] = i; n_obs[i] = F.mvpMapPoints[i]->Observations(); }
         }
-        plf_frustum_pose fp = {};
-        const cv::Mat Rwc = F.GetRotationInverse(), Ow = F.GetCameraCenter();
-        for (int r = 0; r < 3; r++) {
-            for (int c = 0; c < 3; c++) fp.Rcw[3 * r + c] = Rwc.template at<float>(c, r);
-            fp.Ow[r] = Ow.template at<float>(r);
-        }
+        const cv::Mat Rwc = F.GetRotationInverse();
+        cv::Mat Rcw(3, 3, CV_32F);
+        for (int r = 0; r < 3; r++) for (int c = 0; c < 3; c++) Rcw.template at<float>(r, c) = Rwc.template at<float>(c, r);
+        const plf_frustum_pose fp = detail::frustum_pose(Rcw, cv::Mat(), F.GetCameraCenter());   // tcw is not read
         plf_camera cam = {};
         cam.fx = F.fx; cam.fy = F.fy; cam.cx = F.cx; cam.cy = F.cy; cam.bf = F.mbf;
         plf::DeviceArray<plf_keypoint> dkeys(keys, device);
@@ -2082,9 +2087,7 @@ private:
         const std::vector<int32_t> kp = dkp.download();
         const std::vector<float> pos = dpos.download();
         for (int k = 0; k < n_new; k++) {
-            cv::Mat x3D(3, 1, CV_32F);
-            for (int r = 0; r < 3; r++) x3D.template at<float>(r, 0) = pos[3 * (size_t)k + r];
-            F.mvpMapPoints[kp[k]] = make(x3D, kp[k]);
+            F.mvpMapPoints[kp[k]] = make(detail::mat31(&pos[3 * (size_t)k]), kp[k]);
         }
         return n_new;
     }
@@ -2147,20 +2150,9 @@ struct LocalMapping {
             d[s].n = N; d[s].nodes = (int)node_id.size();
             if (node_id.empty()) node_id.push_back(0);
             if (feat.empty()) feat.push_back(0);
-            d[s].keys.reset(cap, device); d[s].keys.upload(keys.data(), cap);
-            d[s].uright.reset(cap, device); d[s].uright.upload(ur.data(), cap);
-            d[s].depth.reset(cap, device); d[s].depth.upload(dep.data(), cap);
-            d[s].desc.reset(cap * 32, device); d[s].desc.upload(desc.data(), cap * 32);
-            d[s].has_mp.reset(cap, device); d[s].has_mp.upload(has.data(), cap);
-            d[s].node_id.reset(node_id.size(), device); d[s].node_id.upload(node_id.data(), node_id.size());
-            d[s].node_start.reset(node_start.size(), device); d[s].node_start.upload(node_start.data(), node_start.size());
-            d[s].feat.reset(feat.size(), device); d[s].feat.upload(feat.data(), feat.size());
-            const cv::Mat Rcw = kf->GetRotation(), tcw = kf->GetTranslation(), Ow = kf->GetCameraCenter();
-            for (int r = 0; r < 3; r++) {
-                for (int c = 0; c < 3; c++) poses[s].Rcw[3 * r + c] = Rcw.template at<float>(r, c);
-                poses[s].tcw[r] = tcw.template at<float>(r, 0);
-                poses[s].Ow[r] = Ow.template at<float>(r, 0);
-            }
+            d[s].keys.assign(keys, device); d[s].uright.assign(ur, device); d[s].depth.assign(dep, device); d[s].desc.assign(desc, device);
+            d[s].has_mp.assign(has, device); d[s].node_id.assign(node_id, device); d[s].node_start.assign(node_start, device); d[s].feat.assign(feat, device);
+            poses[s] = detail::frustum_pose(kf->GetRotation(), kf->GetTranslation(), kf->GetCameraCenter());
             t_keys[s] = d[s].keys.get(); t_ur[s] = d[s].uright.get(); t_depth[s] = d[s].depth.get(); t_has[s] = d[s].has_mp.get(); t_n[s] = N;
             max_n = std::max(max_n, N);
         }
@@ -2189,8 +2181,8 @@ struct LocalMapping {
         plf_camera cam = {};
         cam.fx = cur->fx; cam.fy = cur->fy; cam.cx = cur->cx; cam.cy = cur->cy; cam.bf = cur->mbf;
         plf_triangulate_marks marks = {d_has.get(), nullptr, nullptr};
-        const cv::Mat Ow1 = cur->GetCameraCenter();
-        const float Cw1[3] = {Ow1.template at<float>(0, 0), Ow1.template at<float>(1, 0), Ow1.template at<float>(2, 0)};
+        float Cw1[3];
+        detail::put3(Cw1, cur->GetCameraCenter());
         for (int j = 0; j < J; j++) {
             KeyFrameT *pKF2 = kfs[j + 1];
             const cv::Mat F12 = computeF12(cur, pKF2);
@@ -2222,9 +2214,7 @@ struct LocalMapping {
         for (int j = 0; j < J; j++)
             for (int k = 0; k < n_new[j]; k++) {
                 const size_t o = (size_t)j * N1 + k;
-                cv::Mat x3D(3, 1, CV_32F);
-                for (int r = 0; r < 3; r++) x3D.template at<float>(r, 0) = pos[o * 3 + r];
-                make(x3D, cur, kfs[j + 1], i1[o], i2[o]);
+                make(detail::mat31(&pos[o * 3]), cur, kfs[j + 1], i1[o], i2[o]);
                 nnew++;
             }
         return nnew;
@@ -2254,8 +2244,7 @@ public:
             if (it != ids.end()) return it->second;
             const int32_t id = (int32_t)ids.size();
             ids.emplace(p, id);
-            const cv::Mat X = p->GetWorldPos();
-            for (int r = 0; r < 3; r++) world_.push_back(X.template at<float>(r, 0));
+            detail::put3(world_, p->GetWorldPos());
             bad_.push_back(p->isBad() ? 1 : 0);
             return id;
         };
@@ -2267,12 +2256,7 @@ public:
             if (n) std::memcpy((void *)keys_[s].data(), kf[s]->mvKeysUn.data(), (size_t)n * sizeof(plf_keypoint));
             mps_[s].assign(std::max(n, 1), -1);
             obs_[s].assign(std::max(n, 1), -1);
-            const cv::Mat Rcw = kf[s]->GetRotation(), tcw = kf[s]->GetTranslation();
-            for (int r = 0; r < 3; r++) {
-                for (int c = 0; c < 3; c++) pose_[s].Rcw[3 * r + c] = Rcw.template at<float>(r, c);
-                pose_[s].tcw[r] = tcw.template at<float>(r, 0);
-                pose_[s].Ow[r] = 0.0f;
-            }
+            pose_[s] = detail::frustum_pose(kf[s]->GetRotation(), kf[s]->GetTranslation());
         }
         sigma2_.assign(pKF1->mvLevelSigma2.begin(), pKF1->mvLevelSigma2.end());
         cam_ = plf_camera{};
@@ -2366,11 +2350,9 @@ public:
             std::copy(s->match_.begin(), s->match_.begin() + std::min<size_t>(s->match_.size(), (size_t)S), match.begin() + (size_t)j * S);
             std::copy(s->rand3_.begin(), s->rand3_.end(), rand3.begin() + (size_t)j * RS * 3);
         }
-        h.t_keys.reset(t_keys.size(), device); h.t_keys.upload(t_keys.data(), t_keys.size());
-        h.t_mps.reset(t_mps.size(), device); h.t_mps.upload(t_mps.data(), t_mps.size());
-        h.t_obs.reset(t_obs.size(), device); h.t_obs.upload(t_obs.data(), t_obs.size());
-        auto up = [&](auto &d, const auto &v) { d.reset(v.size(), device); d.upload(v.data(), v.size()); };
-        up(h.kf_n, kf_n); up(h.kf1, kf1); up(h.kf2, kf2); up(h.match, match); up(h.pose, pose); up(h.world, world); up(h.bad, bad); up(h.sigma2, solvers[0]->sigma2_);
+        h.t_keys.assign(t_keys, device); h.t_mps.assign(t_mps, device); h.t_obs.assign(t_obs, device);
+        h.kf_n.assign(kf_n, device); h.kf1.assign(kf1, device); h.kf2.assign(kf2, device); h.match.assign(match, device); h.pose.assign(pose, device);
+        h.world.assign(world, device); h.bad.assign(bad, device); h.sigma2.assign(solvers[0]->sigma2_, device);
         batch.reset(new plf::Sim3Batch(J, S, S, RS, 1, device));
         batch->fix_scale.upload(fix.data(), fix.size());
         batch->rand3.upload(rand3.data(), rand3.size());
@@ -2406,13 +2388,12 @@ public:
                 s->nInliers_ = hit_inliers[j];
             } else bNoMore[j] = no_more[j] != 0;
             const float *q = best_sim3.data() + (size_t)j * 13;
-            s->best_R_ = cv::Mat(3, 3, CV_32F); s->best_t_ = cv::Mat(3, 1, CV_32F); s->best_s_ = q[12];
-            for (int r = 0; r < 3; r++) { for (int c = 0; c < 3; c++) s->best_R_.template at<float>(r, c) = q[3 * r + c]; s->best_t_.template at<float>(r, 0) = q[9 + r]; }
+            s->best_R_ = cv::Mat(3, 3, CV_32F); s->best_t_ = detail::mat31(q + 9); s->best_s_ = q[12];
+            for (int r = 0; r < 3; r++) for (int c = 0; c < 3; c++) s->best_R_.template at<float>(r, c) = q[3 * r + c];
             if (n_hits[j] > 0) {
-                cv::Mat T12(4, 4, CV_32F);
-                for (int r = 0; r < 4; r++) for (int c = 0; c < 4; c++) T12.template at<float>(r, c) = r == c ? 1.0f : 0.0f;
-                for (int r = 0; r < 3; r++) { for (int c = 0; c < 3; c++) T12.template at<float>(r, c) = q[3 * r + c] * q[12] + 0.0f; T12.template at<float>(r, 3) = q[9 + r]; }
-                T[j] = T12;
+                plf_pose34 sRt;                                      // T12 = [s R | t]
+                for (int r = 0; r < 3; r++) { for (int c = 0; c < 3; c++) sRt.Tcw[4 * r + c] = q[3 * r + c] * q[12] + 0.0f; sRt.Tcw[4 * r + 3] = q[9 + r]; }
+                T[j] = detail::mat44(sRt);
             }
         }
         if (patched) {
@@ -2463,80 +2444,44 @@ struct LoopClosing {
         Corrected<MapPointT> out;
         for (KeyFrameT *pKFi : mvpCurrentConnectedKFs) { CorrectedSim3[pKFi]; NonCorrectedSim3[pKFi]; }
         CorrectedSim3[mpCurrentKF]; NonCorrectedSim3[mpCurrentKF];
-        std::vector<KeyFrameT *> kfs;               // slots: the K ranks first, in the map's order, then every other keyframe that observes a point
-        std::vector<float> tcw, ow, scale;
-        std::vector<int64_t> kf_id;
-        detail::KeyFrameSlots seen;
-        auto slot_of = [&](KeyFrameT *pKF) {
-            return seen(pKF, [&](KeyFrameT *first) {
-                kfs.push_back(first);
-                const cv::Mat T = first->GetPose(), C = first->GetCameraCenter();
-                for (int r = 0; r < 3; r++) for (int c = 0; c < 4; c++) tcw.push_back(T.template at<float>(r, c));
-                for (int k = 0; k < 3; k++) ow.push_back(C.template at<float>(k));
-                kf_id.push_back((int64_t)first->mnId);
-            });
-        };
-        std::vector<int32_t> rank_kf;
-        for (auto &e : CorrectedSim3) rank_kf.push_back(slot_of(e.first));
-        const int K = (int)rank_kf.size();
-        std::unordered_map<MapPointT *, int32_t> ids;
-        std::vector<int32_t> row_start(1, 0), row_point, obs_start(1, 0), obs_kf, ref, level;
-        std::vector<uint8_t> bad;
-        std::vector<float> pos;
-        std::vector<int64_t> by;
-        for (auto &e : CorrectedSim3) {
-            for (MapPointT *pMP : e.first->GetMapPointMatches()) {
-                if (!pMP) { row_point.push_back(-1); continue; }
-                auto at = ids.emplace(pMP, (int32_t)ids.size());
-                row_point.push_back(at.first->second);
-                if (!at.second) continue;
-                out.points.push_back(pMP);
-                const cv::Mat X = pMP->GetWorldPos();
-                for (int k = 0; k < 3; k++) pos.push_back(X.template at<float>(k));
-                bad.push_back(pMP->isBad() ? 1 : 0);
+        std::vector<plf_pose34> tcw;
+        std::vector<float> ow, scale, pos;
+        std::vector<int64_t> kf_id, by;
+        std::vector<int32_t> ref, level;
+        auto g = detail::map_gather<KeyFrameT, MapPointT>(
+            [&](KeyFrameT *pKF) { tcw.push_back(detail::pose34(pKF->GetPose())); detail::put3(ow, pKF->GetCameraCenter()); kf_id.push_back((int64_t)pKF->mnId); },
+            [&](auto &gather, MapPointT *pMP, const auto &observations) {
+                detail::put3(pos, pMP->GetWorldPos());
                 by.push_back((int64_t)pMP->mnCorrectedByKF);
-                const auto observations = pMP->GetObservations();
-                for (const auto &ob : observations) obs_kf.push_back(slot_of(ob.first));
-                obs_start.push_back((int32_t)obs_kf.size());
-                KeyFrameT *pRefKF = pMP->GetReferenceKeyFrame();
-                int32_t r = -1, l = 0;
-                if (pRefKF && !observations.empty()) {
-                    r = slot_of(pRefKF);
-                    const auto it = observations.find(pRefKF);
-                    const size_t idx = it == observations.end() ? 0 : it->second;
-                    l = idx < pRefKF->mvKeysUn.size() ? pRefKF->mvKeysUn[idx].octave : 0;
-                    if (scale.empty()) scale.assign(pRefKF->mvScaleFactors.begin(), pRefKF->mvScaleFactors.begin() + pRefKF->mnScaleLevels);
-                }
-                ref.push_back(r); level.push_back(l);
-            }
-            row_start.push_back((int32_t)row_point.size());
-        }
-        const int P = (int)out.points.size(), S = (int)kfs.size();
+                ref.push_back(-1); level.push_back(0);
+                detail::ref_level(gather, pMP->GetReferenceKeyFrame(), observations, scale, ref.back(), level.back());
+            });
+        std::vector<int32_t> rank_kf;               // slots: the K ranks first, in the map's order, then every other keyframe that observes a point
+        for (auto &e : CorrectedSim3) rank_kf.push_back(g.slot(e.first));
+        const int K = (int)rank_kf.size();
+        for (auto &e : CorrectedSim3) g.row(e.first->GetMapPointMatches());
+        out.points = g.pts;                         // every point met in the rows, in order of first occurrence
+        const int P = (int)out.points.size(), S = (int)g.kfs.size();
         out.owner_rank.assign(P, -1); out.n.assign(P, -1);
         out.normal.assign((size_t)P * 3, 0.0f); out.minDistance.assign(P, 0.0f); out.maxDistance.assign(P, 0.0f);
         if (scale.empty()) scale.assign(1, 1.0f);
-        if (row_point.empty()) row_point.push_back(-1);
-        if (obs_kf.empty()) obs_kf.push_back(-1);
         const std::vector<double> scw8 = {mg2oScw.rotation().x(), mg2oScw.rotation().y(), mg2oScw.rotation().z(), mg2oScw.rotation().w(), mg2oScw.translation()[0],
                                           mg2oScw.translation()[1], mg2oScw.translation()[2], mg2oScw.scale()};
         plf::LoopCorrection lc(K, P, S, device);
         lc.scw.upload(scw8.data(), 8);
-        plf::DeviceArray<plf_pose34> dtcw(tcw.size() / 12, device);
-        dtcw.upload(tcw.data(), tcw.size() / 12);
-        plf::DeviceArray<float> dow(ow, device), dscale(scale, device), dpos(std::max(P, 1) * 3, device), dnormal(std::max(P, 1) * 3, device), dmin(std::max(P, 1), device),
-            dmax(std::max(P, 1), device);
-        plf::DeviceArray<int32_t> drank(rank_kf, device), drs(row_start, device), drp(row_point, device), dos(obs_start, device), dok(obs_kf, device),
-            dref(std::max(P, 1), device), dlevel(std::max(P, 1), device);
-        plf::DeviceArray<uint8_t> dbad(std::max(P, 1), device);
-        plf::DeviceArray<int64_t> did(kf_id, device), dby(std::max(P, 1), device), dcref(std::max(P, 1), device);
-        dnormal.fill(0); dmin.fill(0); dmax.fill(0); dcref.fill(0);
-        if (P) { dpos.upload(pos.data(), pos.size()); dref.upload(ref.data(), P); dlevel.upload(level.data(), P); dbad.upload(bad.data(), P); dby.upload(by.data(), P); }
-        const plf_loop_view rows = {K, drank.get(), drs.get(), drp.get(), P, dbad.get(), S, did.get()};
-        plf_map_geom_view g = {};
-        g.n_points = P; g.obs_start = dos.get(); g.obs_kf = dok.get(); g.kf_ow = dow.get(); g.n_kf = S; g.ref_kf = dref.get(); g.ref_level = dlevel.get();
-        g.scale_factors = dscale.get(); g.nlevels = (int32_t)scale.size(); g.point_bad = dbad.get(); g.pos_floats = 3;
-        lc.Run(rows, seen(mpCurrentKF, [](KeyFrameT *) {}), (int64_t)mpCurrentKF->mnId, dtcw.get(), dow.get(), g, dpos.get(), dby.get(), dcref.get(), dnormal.get(),
-               dmin.get(), dmax.get(), rank_kf);
+        const typename decltype(g)::Device d(g, device);
+        plf::DeviceArray<plf_pose34> dtcw(tcw, device);
+        plf::DeviceArray<float> dow(ow, device), dscale(scale, device), dpos(pos, device), dnormal(out.normal, device), dmin(out.minDistance, device),
+            dmax(out.maxDistance, device);
+        plf::DeviceArray<int32_t> drank(rank_kf, device), dref(ref, device), dlevel(level, device);
+        plf::DeviceArray<int64_t> did(kf_id, device), dby(by, device), dcref(P, device);
+        dcref.fill(0);
+        const plf_loop_view rows = {K, drank.get(), d.row_start.get(), d.row_point.get(), P, d.point_bad.get(), S, did.get()};
+        plf_map_geom_view geom = {};
+        geom.n_points = P; geom.obs_start = d.obs_start.get(); geom.obs_kf = d.obs_kf.get(); geom.kf_ow = dow.get(); geom.n_kf = S; geom.ref_kf = dref.get();
+        geom.ref_level = dlevel.get(); geom.scale_factors = dscale.get(); geom.nlevels = (int32_t)scale.size(); geom.point_bad = d.point_bad.get(); geom.pos_floats = 3;
+        lc.Run(rows, g.slot(mpCurrentKF), (int64_t)mpCurrentKF->mnId, dtcw.get(), dow.get(), geom, dpos.get(), dby.get(), dcref.get(), dnormal.get(), dmin.get(),
+               dmax.get(), rank_kf);
         // ---- back into the caller's objects (a NULL-stream download waits for the device first)
         const std::vector<double> cor = lc.corrected.download(), non = lc.noncorrected.download();
         auto put = [](Sim3T &S3, const double *o) {
@@ -2553,22 +2498,14 @@ struct LoopClosing {
             out.normal = dnormal.download(); out.minDistance = dmin.download(); out.maxDistance = dmax.download();
             for (int p = 0; p < P; p++) {
                 if (out.owner_rank[p] < 0) continue;
-                cv::Mat X(3, 1, CV_32F);
-                for (int k = 0; k < 3; k++) X.at<float>(k, 0) = npos[(size_t)p * 3 + k];
-                out.points[p]->SetWorldPos(X);
+                out.points[p]->SetWorldPos(detail::mat31(&npos[(size_t)p * 3]));
                 out.points[p]->mnCorrectedByKF = (decltype(out.points[p]->mnCorrectedByKF))nby[p];
                 out.points[p]->mnCorrectedReference = (decltype(out.points[p]->mnCorrectedReference))ncref[p];
             }
         }
         const std::vector<plf_pose34> tn = lc.tcw_new.download();
         r = 0;
-        for (auto &e : CorrectedSim3) {
-            cv::Mat T(4, 4, CV_32F);
-            for (int i = 0; i < 3; i++) for (int c = 0; c < 4; c++) T.at<float>(i, c) = tn[r].Tcw[4 * i + c];
-            T.at<float>(3, 0) = 0.0f; T.at<float>(3, 1) = 0.0f; T.at<float>(3, 2) = 0.0f; T.at<float>(3, 3) = 1.0f;
-            e.first->SetPose(T);
-            r++;
-        }
+        for (auto &e : CorrectedSim3) e.first->SetPose(detail::mat44(tn[r++]));
         return out;
     }
 };

@@ -11,10 +11,8 @@
 #include <vector>
 #include <ORB_SLAM2/mock_sim3opt.h>
 #include "plf.hpp"
+#include "scenario_io.h"
 
-static float rdf(FILE *f) { unsigned u = 0; if (fscanf(f, "%x", &u) != 1) throw std::runtime_error("scenario: float"); float v; memcpy(&v, &u, 4); return v; }
-static double rdd(FILE *f) { unsigned long long u = 0; if (fscanf(f, "%llx", &u) != 1) throw std::runtime_error("scenario: double"); double v; memcpy(&v, &u, 8); return v; }
-static long long rdi(FILE *f) { long long v = 0; if (fscanf(f, "%lld", &v) != 1) throw std::runtime_error("scenario: int"); return v; }
 static cv::Mat rdm(FILE *f, int r, int c) { cv::Mat m(r, c, CV_32F); for (int i = 0; i < r; i++) for (int j = 0; j < c; j++) m.at<float>(i, j) = rdf(f); return m; }
 static unsigned long long bits(double v) { unsigned long long u; memcpy(&u, &v, 8); return u; }
 

@@ -9,9 +9,8 @@
 #include <vector>
 #include <ORB_SLAM2/mock_track.h>
 #include "plf.hpp"
+#include "scenario_io.h"
 
-static float rdf(FILE *f) { unsigned u = 0; if (fscanf(f, "%x", &u) != 1) throw std::runtime_error("scenario: float"); float v; memcpy(&v, &u, 4); return v; }
-static long long rdi(FILE *f) { long long v = 0; if (fscanf(f, "%lld", &v) != 1) throw std::runtime_error("scenario: int"); return v; }
 
 int main(int argc, char **argv)
 {

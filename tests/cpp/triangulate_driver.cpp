@@ -11,9 +11,8 @@
 #include <vector>
 #include <ORB_SLAM2/mock_triangulate.h>
 #include "plf.hpp"
+#include "scenario_io.h"
 
-static float rdf(FILE *f) { unsigned u = 0; if (fscanf(f, "%x", &u) != 1) throw std::runtime_error("scenario: float"); float v; memcpy(&v, &u, 4); return v; }
-static long long rdi(FILE *f) { long long v = 0; if (fscanf(f, "%lld", &v) != 1) throw std::runtime_error("scenario: int"); return v; }
 static cv::Mat rdm(FILE *f, int r, int c) { cv::Mat m(r, c, CV_32F); for (int i = 0; i < r; i++) for (int j = 0; j < c; j++) m.at<float>(i, j) = rdf(f); return m; }
 
 int main(int argc, char **argv)

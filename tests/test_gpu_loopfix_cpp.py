@@ -4,7 +4,6 @@ rank order is the pointer order, and what it leaves in the objects -- both maps,
 returns -- equals the sequential definition tests/loopfixref.py bit for bit, with the keyframes laid out in ascending and in descending address order.
 (The host loop tools/loopfix_cpu.cpp is compared with the definition in tests/test_loopfix_ref.py: it needs no GPU.)"""
 import os
-import struct
 import subprocess
 import sys
 
@@ -17,10 +16,6 @@ import loopfixgen as G  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 F32 = np.float32
-
-
-def _hex(a):
-    return " ".join("%x" % v for v in np.ascontiguousarray(a, F32).view(np.uint32).ravel())
 
 
 def _scene(reverse):
@@ -43,18 +38,18 @@ def _scene(reverse):
 
 def _write(sc, reverse, path):
     with open(path, "w") as fh:
-        fh.write("%d %d %d %d %s\n" % (reverse, sc["n_kf"], sc["n_points"], G.NLEVELS, _hex(sc["scale_factors"])))
+        fh.write("%d %d %d %d %s\n" % (reverse, sc["n_kf"], sc["n_points"], G.NLEVELS, cppbuild.hex32(sc["scale_factors"])))
         for k in range(sc["n_kf"]):
-            fh.write("%d %s %s\n" % (sc["kf_id"][k], _hex(sc["kf_tcw"][k]), _hex(sc["kf_ow"][k])))
+            fh.write("%d %s %s\n" % (sc["kf_id"][k], cppbuild.hex32(sc["kf_tcw"][k]), cppbuild.hex32(sc["kf_ow"][k])))
         for p in range(sc["n_points"]):
             s, e = sc["obs_start"][p], sc["obs_start"][p + 1]
-            fh.write("%s %d %d %d %d %d %d %s\n" % (_hex(sc["world_pos"][p]), sc["point_bad"][p], sc["corrected_by"][p], sc["corrected_ref"][p], sc["ref_kf"][p],
+            fh.write("%s %d %d %d %d %d %d %s\n" % (cppbuild.hex32(sc["world_pos"][p]), sc["point_bad"][p], sc["corrected_by"][p], sc["corrected_ref"][p], sc["ref_kf"][p],
                                                     sc["ref_level"][p], e - s, " ".join(str(k) for k in sc["obs_kf"][s:e])))
         fh.write("%d %d\n" % (len(sc["rank_kf"]), sc["cur_slot"]))
         for r, k in enumerate(sc["rank_kf"][::-1]):                        # (listed in the opposite order: the map, not the list, orders the walk)
             row = sc["rows"][len(sc["rank_kf"]) - 1 - r]
             fh.write("%d %d %s\n" % (k, len(row), " ".join(str(p) for p in row)))
-        fh.write(" ".join("%x" % struct.unpack("<Q", struct.pack("<d", v))[0] for v in sc["scw"]) + "\n")
+        fh.write(cppbuild.hex64(sc["scw"]) + "\n")
 
 
 @pytest.mark.parametrize("reverse", [0, 1])

@@ -21,27 +21,23 @@ def _need_gpu():
         pytest.fail("no GPU visible: the -m gpu tests need a real MI355X")
 
 
-def _hex(v):
-    return "%x" % int(np.float32(v).view(np.uint32))
-
-
 def test_cpp_driver_gives_the_recorded_bits(tmp_path):
     with open(os.path.join(ROOT, "tests", "golden", "pose_tiny.json")) as fh:
         doc = json.load(fh)
     exe = cppbuild.build_driver("pose_driver", tmp_path, "-O1", "-Wall")
     before = []
-    lines = [" ".join(_hex(v) for v in doc["cam"]), "%d %s" % (len(doc["inv_level_sigma2"]), " ".join(_hex(v) for v in doc["inv_level_sigma2"])),
+    lines = [cppbuild.hex32(doc["cam"]), "%d %s" % (len(doc["inv_level_sigma2"]), cppbuild.hex32(doc["inv_level_sigma2"])),
              str(len(doc["frames"]))]
     for fr in doc["frames"]:
         n = len(fr["match"])
         flags = [(7 * i + 3) % 2 for i in range(n)]                 # what the frame holds before the call
         before.append(flags)
         lines.append(str(n))
-        lines.append(" ".join(_hex(v) for v in fr["tcw_init"]))
+        lines.append(cppbuild.hex32(fr["tcw_init"]))
         for i in range(n):
             m = fr["match"][i]
-            pt = " ".join(_hex(v) for v in fr["world_pos"][3 * m:3 * m + 3]) if m >= 0 else ""
-            lines.append("%s %s %s %d %d %d %s" % (_hex(fr["x"][i]), _hex(fr["y"][i]), _hex(fr["uright"][i]), fr["octave"][i], flags[i], int(m >= 0), pt))
+            pt = cppbuild.hex32(fr["world_pos"][3 * m:3 * m + 3]) if m >= 0 else ""
+            lines.append("%s %s %s %d %d %d %s" % (cppbuild.hex32(fr["x"][i]), cppbuild.hex32(fr["y"][i]), cppbuild.hex32(fr["uright"][i]), fr["octave"][i], flags[i], int(m >= 0), pt))
     (tmp_path / "scenario.txt").write_text("\n".join(lines) + "\n")
     run = subprocess.run([str(exe), str(tmp_path)], text=True, capture_output=True)
     assert run.returncode == 0 and "pose driver ok" in run.stdout, "driver failed (rc %d)\n%s\n%s" % (run.returncode, run.stdout, run.stderr[-2000:])

@@ -33,10 +33,6 @@ def _leave_no_cached_device_memory():
     torch.cuda.empty_cache()
 
 
-def _hex(a):
-    return " ".join("%x" % v for v in np.ascontiguousarray(a, F32).view(np.uint32).ravel())
-
-
 def _scene():
     jobs = [dict(n1=70, pairs=50, outliers=0.4, null=3, bad=4), dict(n1=40, pairs=24, outliers=0.6, fix_scale=True), dict(n1=64, pairs=48, outliers=0.5, scale=1.25)]
     return G.make_scene(91, jobs, min_inliers=MIN_INLIERS, max_iterations=MAX_ITS, max_hits=1, obs_index=True)
@@ -45,16 +41,16 @@ def _scene():
 def _write(sc, path):
     J = len(sc["job_kf1"])
     with open(path, "w") as fh:
-        fh.write("%d %d %d\n%s\n%d %s\n%d\n" % (SEED, MIN_INLIERS, MAX_ITS, _hex(sc["cam"][:4]), len(sc["level_sigma2"]), _hex(sc["level_sigma2"]), J))
+        fh.write("%d %d %d\n%s\n%d %s\n%d\n" % (SEED, MIN_INLIERS, MAX_ITS, cppbuild.hex32(sc["cam"][:4]), len(sc["level_sigma2"]), cppbuild.hex32(sc["level_sigma2"]), J))
         for j in range(J):
             s1, s2 = 2 * j, 2 * j + 1
             ids = np.concatenate([sc["kf_mappoints"][s1], sc["kf_mappoints"][s2]])
             base, top = ids[ids >= 0].min(), ids.max()
             fh.write("%d %d\n" % (sc["fix_scale"][j], top - base + 1))
             for p in range(base, top + 1):
-                fh.write("%s %d\n" % (_hex(sc["world_pos"][p]), sc["point_bad"][p]))
+                fh.write("%s %d\n" % (cppbuild.hex32(sc["world_pos"][p]), sc["point_bad"][p]))
             for s in (s1, s2):
-                fh.write("%s %s %d\n" % (_hex(sc["kf_pose"][s][:9]), _hex(sc["kf_pose"][s][9:12]), sc["kf_n"][s]))
+                fh.write("%s %s %d\n" % (cppbuild.hex32(sc["kf_pose"][s][:9]), cppbuild.hex32(sc["kf_pose"][s][9:12]), sc["kf_n"][s]))
                 for i in range(sc["kf_n"][s]):
                     mp = sc["kf_mappoints"][s][i]
                     fh.write("%d %d %d\n" % (sc["kf_octave"][s][i], mp - base if mp >= 0 else -1, sc["kf_obs_index"][s][i]))

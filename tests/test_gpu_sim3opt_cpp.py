@@ -3,7 +3,6 @@ g2o::Sim3 of tests/mock/ORB_SLAM2/mock_sim3opt.h, driven by tests/cpp/sim3opt_dr
 every candidate equal tests/sim3optref.py bit for bit.  The start g2oS12 is built as LoopClosing::ComputeSim3 builds it -- Quaterniond of the float
 rotation --, and the definition is given the floats the adapter narrows it to."""
 import os
-import struct
 import subprocess
 import sys
 
@@ -19,10 +18,6 @@ pytestmark = pytest.mark.gpu
 F32 = np.float32
 
 
-def _hex(a):
-    return " ".join("%x" % v for v in np.ascontiguousarray(a, F32).view(np.uint32).ravel())
-
-
 def _scene():
     jobs = [dict(n1=70, pairs=50, outliers=0.3, null=3, bad=4, noobs=3), dict(n1=40, pairs=24, fix_scale=True), dict(n1=30, pairs=12, outliers=0.3),
             dict(n1=50, pairs=30, scale=1.25, off_s=1.04, off_deg=10.0)]
@@ -32,26 +27,26 @@ def _scene():
 def _write(sc, starts, path):
     J = len(sc["job_kf1"])
     with open(path, "w") as fh:
-        fh.write("%s\n%s\n%d %s\n%d\n" % (_hex([sc["th2"]]), _hex(sc["cam"][:4]), len(sc["inv_level_sigma2"]), _hex(sc["inv_level_sigma2"]), J))
+        fh.write("%s\n%s\n%d %s\n%d\n" % (cppbuild.hex32([sc["th2"]]), cppbuild.hex32(sc["cam"][:4]), len(sc["inv_level_sigma2"]), cppbuild.hex32(sc["inv_level_sigma2"]), J))
         for j in range(J):
             s1, s2 = 2 * j, 2 * j + 1
             ids = np.concatenate([sc["kf_mappoints"][s1], sc["kf_mappoints"][s2]])
             base, top = ids[ids >= 0].min(), ids.max()
             fh.write("%d %d\n" % (sc["fix_scale"][j], top - base + 1))
             for p in range(base, top + 1):
-                fh.write("%s %d\n" % (_hex(sc["world_pos"][p]), sc["point_bad"][p]))
+                fh.write("%s %d\n" % (cppbuild.hex32(sc["world_pos"][p]), sc["point_bad"][p]))
             for s in (s1, s2):
-                fh.write("%s %s %d\n" % (_hex(sc["kf_pose"][s][:9]), _hex(sc["kf_pose"][s][9:12]), sc["kf_n"][s]))
+                fh.write("%s %s %d\n" % (cppbuild.hex32(sc["kf_pose"][s][:9]), cppbuild.hex32(sc["kf_pose"][s][9:12]), sc["kf_n"][s]))
                 for i in range(sc["kf_n"][s]):
                     mp = sc["kf_mappoints"][s][i]
-                    fh.write("%s %d %d %d\n" % (_hex(sc["kf_keys"][s][i, :2]), sc["kf_octave"][s][i], mp - base if mp >= 0 else -1, sc["kf_obs_index"][s][i]))
+                    fh.write("%s %d %d %d\n" % (cppbuild.hex32(sc["kf_keys"][s][i, :2]), sc["kf_octave"][s][i], mp - base if mp >= 0 else -1, sc["kf_obs_index"][s][i]))
             n1 = sc["kf_n"][s1]
             fh.write("%d\n" % n1)
             for i1 in range(n1):
                 i2 = sc["match12"][j, i1]
                 mp = sc["kf_mappoints"][s2][i2] if i2 >= 0 else -1
                 fh.write("%d\n" % (mp - base if mp >= 0 else -1))
-            fh.write(" ".join("%x" % struct.unpack("<Q", struct.pack("<d", v))[0] for v in starts[j]) + "\n")
+            fh.write(cppbuild.hex64(starts[j]) + "\n")
 
 
 def test_exact_signature_adapter(tmp_path):
